@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — y = A*x throughput of the HIP TileSpMV engine on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W [--workload laplacian4096] [--dtype f64]
+    python bench.py --gpus N --steps K --warmup W [--workload laplacian4096] [--dtype f64] [--dump-outputs DIR] [--full]
 
 A "step" is one SpMV over the whole (row-partitioned) matrix.  Inputs are resident in HBM when
 the timed region starts.  Rank 0 prints ONE JSON line.  Metric/config follow BASELINE.json:
 fp64 SpMV GFLOP/s + achieved (algorithmic) HBM GB/s as a fraction of the 8 TB/s roofline.
+A plain run only sets up, runs the W warm-up steps and the K timed steps, writes y with --dump-outputs and prints
+the line (its `check` is "skipped").  --full adds everything else measured or checked beside the headline: the
+whole-block parity check, steady state, reference-style timing, device state, measured HBM ceilings, the other
+preparation path, the y combines (N > 1), the other workloads, population and reorder tables, the CPU baseline.
 
 Workloads (synthetic stand-ins unless $TILESPMV_MATRIX_DIR/<name>.mtx exists):
   laplacian4096  5-pt Laplacian on a 4096^2 grid, 16.7 M rows, 83.9 M nnz  (config 4; default —
@@ -16,7 +20,7 @@ Workloads (synthetic stand-ins unless $TILESPMV_MATRIX_DIR/<name>.mtx exists; SU
 Multi-GPU: contiguous nnz-balanced tile-row blocks, one rank per GPU, x replicated, y left
 sharded (the SpMV needs no collective: SURVEY.md §8e) => "scaling": "strong" on the fixed matrix;
 --combine allgather|allreduce adds the RCCL y combine to every step, --combine halo runs the sharded-x form
-(HaloSpMV: only the halo of x travels); the default run also reports all three beside the headline value when N > 1.
+(HaloSpMV: only the halo of x travels); a --full run also reports all three beside the headline value when N > 1.
 Every rank generates (or reads) and preprocesses ONLY its own row block where the workload has a row-block generator
 (the stencil workloads, incl. the headline) — `generated` in the line says which.
 --data real: vals, x ~ U(-1, 1), seed 12345 (SURVEY.md S8(d) data mode ii), whole-y tolerance check instead of the exact one.
@@ -318,6 +322,34 @@ def device_state_under_load(run_async, sync, samples=6, gap=0.04):
     return out
 
 
+DUMP_BUDGET = 48 << 20   # bytes of y that --dump-outputs writes at most
+DUMP_SEED = 12345
+
+
+def dump_rows(rows, itemsize):
+    """Rows of y that --dump-outputs writes: None = all of them (y fits DUMP_BUDGET), else a fixed seeded sample, ascending,
+    of DUMP_BUDGET / itemsize rows — the same for every run with the same workload and dtype."""
+    if rows * itemsize <= DUMP_BUDGET:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, DUMP_BUDGET // itemsize, replace=False))
+
+
+def dump_outputs(out_dir, y_own, r0, rows, rank, world, dist):
+    """y of the last timed step as a caller receives it: every rank's own rows [r0, r0 + len(y_own)), gathered on rank 0 in row
+    order, written as out_dir/y.npy (the whole vector) or out_dir/y_sample.npy (the rows dump_rows picks), in the run's dtype."""
+    pick = dump_rows(rows, y_own.dtype.itemsize)
+    if pick is not None:
+        lo, hi = np.searchsorted(pick, [r0, r0 + len(y_own)])
+        y_own = y_own[pick[lo:hi] - r0]
+    parts = [y_own]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, y_own)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "y.npy" if pick is None else "y_sample.npy"), np.concatenate(parts))
+
+
 LINE_BUDGET = 4096   # bytes of the final stdout line (the driver parses the LAST line; the reference's own record is one short line: src/tilespmv_cuda.h:1139-1147)
 
 
@@ -340,9 +372,10 @@ def compact_line(out, full_path):
     else:
         line["cpu_baseline"] = None
     line["check"] = out["check"]
+    line["run"] = out.get("run")
     if out.get("steady_state"):
         line["steady_state"] = out["steady_state"]
-    line["reference_style_ms"] = out["reference_style_timing"]["ms_per_spmv"]
+    line["reference_style_ms"] = (out.get("reference_style_timing") or {}).get("ms_per_spmv")
     line["ranks"] = out["ranks"]; line["backend"] = out["backend"]; line["launched_by"] = out["launched_by"]
     if out["n_gpus"] > 1:
         line["rank_devices"] = out.get("rank_devices")
@@ -493,8 +526,17 @@ def main():
                     help="the complete record (every plan parameter, preparation seconds, per-workload detail) is written here; stdout carries one compact line (< 4 KB) that names this file")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (one GPU per rank); gloo only to rehearse the N>1 path on a single GPU")
-    ap.add_argument("--phase-timeout-scale", type=float, default=1.0, help="multiplies the hard per-phase limits (init 300 s, prepare 900 s, check 300 s, timed 300 s, each combine 300 s, extras 1500 s, cpu baseline 600 s)")
+    ap.add_argument("--phase-timeout-scale", type=float, default=1.0, help="multiplies the hard per-phase limits (init 300 s, prepare 900 s, check 300 s, timed 300 s, dump 300 s, each combine 300 s, extras 1500 s, cpu baseline 600 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what lies beside the headline (off by default: a plain run sets up, warms up, times the K steps and prints the line): "
+                         "process warm-up before the timed preparation, whole-block parity check, steady state, reference-style timing, device state, measured HBM ceilings, "
+                         "the other preparation path, the y combines (N > 1), other workloads + population + reorder (headline workload, N = 1), CPU baseline; "
+                         "--no-prep-warm-up, --no-check, --no-extras, --no-cpu-baseline and --setup-launches trim it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write y of the last timed step to DIR/y.npy in the run's dtype; when y is larger than %d MB, a fixed seeded sample of its rows "
+                         "(bench.dump_rows) to DIR/y_sample.npy instead" % (DUMP_BUDGET >> 20))
     args = ap.parse_args()
+    do_check = args.full and not args.no_check
     phase.scale = args.phase_timeout_scale
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # before anything touches the GPU: this pool's host driver only supports dmabuf IPC (RCCL fails with hipIpcGetMemHandle: invalid argument without it)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -558,7 +600,8 @@ def main():
     # 150-280 ms in a fresh process, the same copy 19 ms afterwards — scripts/archive/rounds/r5b_upload_first_touch2.py), the host thread pool.  A small matrix goes through both preparation paths here,
     # untimed, so that `prep_seconds` below is what preparing THIS matrix costs a running process; the one-time part is reported as `process_warm_up_seconds`.
     t0 = time.time()
-    if not args.no_prep_warm_up:
+    warm_process = args.full and not args.no_prep_warm_up
+    if warm_process:
         wm, wn, wrp, wci = G.laplacian5pt(1536)
         wv = G.compat_values(len(wci), dtype)
         wtm = api.Tile_create(wm, wn, int(wrp[wm]), wrp, wci, wv, dtype=dtype)
@@ -644,7 +687,7 @@ def main():
     # data; for real-valued data |y - y_ref| <= tol * sum_j |a_ij x_j| with tol 1e-12 (fp64) / 1e-5 (fp32) (SURVEY S8(d) ii;
     # the reference's own GPU check is 1 % relative, src/main.cu:186-197)
     import scipy.sparse as sp
-    A64 = sp.csr_matrix((vals_b.astype(np.float64), ci_b, rp_b), shape=(sh.r1 - sh.r0, n)) if not args.no_check else None
+    A64 = sp.csr_matrix((vals_b.astype(np.float64), ci_b, rp_b), shape=(sh.r1 - sh.r0, n)) if do_check else None
 
     def check_rows(got, what):
         want = A64 @ x.astype(np.float64)
@@ -659,12 +702,12 @@ def main():
 
     check = "skipped"
     with phase("parity check", 300):
-        if not args.no_check:
+        if do_check:
             step("none"); torch.cuda.synchronize()
             check = check_rows(yd[sh.r0:sh.r1].cpu().numpy(), "sharded SpMV")
         if args.combine == "halo":
             halo = make_halo()
-            if not args.no_check:
+            if do_check:
                 step("halo"); torch.cuda.synchronize()
                 check_rows(halo.y_own[:halo.nloc].cpu().numpy(), "halo SpMV")
 
@@ -672,9 +715,15 @@ def main():
     with phase("timed steps", 300):
         wall, dev_ms = timed(args.combine, args.steps, args.warmup)
     main_per_rank = timed.per_rank
+    if args.dump_outputs:   # y of the last timed step, before anything else runs on the device
+        with phase("dump outputs", 300):
+            if args.combine == "halo":
+                dump_outputs(args.dump_outputs, halo.y_own[:halo.nloc].cpu().numpy(), halo.r0, rows, rank, world, dist)
+            else:
+                dump_outputs(args.dump_outputs, yd[sh.r0:sh.r1].cpu().numpy(), sh.r0, rows, rank, world, dist)
     # beside it (never `value`): steady state — `setup_launches` untimed SpMVs first (reference: 200 warm-up launches, src/tilespmv_cuda.h:1059-1082), then the same W + K
     steady = None
-    if args.setup_launches > 0:
+    if args.full and args.setup_launches > 0:
         run("none", args.setup_launches)
         sync_all()
         wall_s, dev_ms_s = timed(args.combine, args.steps, args.warmup)
@@ -710,8 +759,10 @@ def main():
     # the reference's own timing protocol (src/tilespmv_cuda.h:1112-1137): wall clock around launch + synchronize, one SpMV at
     # a time, as a C loop (tilespmv_plan_time_reference_style); its cudaMemset of y is not needed: the kernel overwrites y
     nref = min(1000, max(args.steps, 50))
-    sync_all()
-    ref_style_ms = sh.local.time_reference_style(xd.data_ptr(), yd.data_ptr() + sh.r0 * yd.element_size(), stream.cuda_stream, nref)
+    ref_style_ms = None
+    if args.full:
+        sync_all()
+        ref_style_ms = sh.local.time_reference_style(xd.data_ptr(), yd.data_ptr() + sh.r0 * yd.element_size(), stream.cuda_stream, nref)
     roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
                 "kernel": "k_units" if info["kernel"] == 2 else "k_tiles_direct", "kernel_ms": round(kernel_ms, 5), "algorithmic_bytes_per_launch": int(b_alg_launch),
@@ -728,8 +779,11 @@ def main():
                         "Read `frac_min_bytes` (values + x + y only: bounded by 1), `frac_by_plan_bytes` and, when present, actual_traffic_gbps (counter bytes) as efficiencies"
                         % (100.0 * info["stream_bytes"] / b_alg_launch))
 
+    if rank == 0 and world == 1 and traffic:
+        roofline["actual_traffic_gbps"] = round(traffic / (kernel_ms * 1e-3) * 1e-9, 1)
+
     device_state = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             n_load = max(200, int(0.3 / max(kernel_ms * 1e-3, 1e-6)))
             device_state = device_state_under_load(lambda: sh.spmv(xd, yd, stream.cuda_stream, count=n_load), sync_all)
@@ -737,7 +791,7 @@ def main():
             device_state = {"error": repr(e)}
 
     # measured device ceilings beside the 8 TB/s spec figure: read-only and copy streams of 1 GiB buffers
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             big = torch.ones(1 << 27, dtype=torch.float64, device="cuda"); dst = torch.empty_like(big)
             def _bw(f, nbytes):
@@ -748,21 +802,20 @@ def main():
             rd = _bw(lambda: torch.sum(big), big.numel() * 8); cp = _bw(lambda: dst.copy_(big), 2 * big.numel() * 8)
             roofline["measured_ceilings_gbps"] = {"read_only_stream": round(rd, 0), "copy_stream_read_plus_write": round(cp, 0)}
             if traffic:
-                roofline["actual_traffic_gbps"] = round(traffic / (kernel_ms * 1e-3) * 1e-9, 1)
                 roofline["actual_traffic_over_read_ceiling"] = round(traffic / (kernel_ms * 1e-3) * 1e-9 / rd, 4)
             del big, dst
         except Exception as e:
             roofline["measured_ceilings_gbps"] = {"error": repr(e)}
 
     extra = {}
-    if world > 1 and args.combine == "none":
+    if args.full and world > 1 and args.combine == "none":
         ksteps = max(5, args.steps // 10)
         for mode in ("allgather", "allreduce", "halo"):
             try:
               with phase("y combine: " + mode, 300):
                 if mode == "halo":
                     halo = make_halo()
-                elif not args.no_check:
+                elif do_check:
                     # the first rows of every rank's block as that rank computed them, BEFORE any combine (its whole block was checked against the CSR golden above):
                     # what the neighbours' rows of the combined y are compared with below — a rank-consistent misplacement in the combine cannot pass
                     step("none"); torch.cuda.synchronize()
@@ -774,7 +827,7 @@ def main():
                 if mode == "halo":
                     extra[mode]["halo_bytes_per_rank"] = int(halo.halo_bytes())
                     extra[mode]["note"] = "x sharded like y: one all_to_all_single of the halo per SpMV, no full-length vector anywhere"
-                if not args.no_check:
+                if do_check:
                     if mode == "halo":   # every rank: its own rows, whole block
                         okv = 1.0
                         try:
@@ -796,9 +849,9 @@ def main():
                 extra[mode] = {"error": repr(e)}
 
     # per-rank preprocessing seconds (every rank prepares only its own block)
-    prep_mine = dict({"generate": round(t_gen, 3), "process_warm_up_seconds": round(t_warm_process, 3), "total_tile_create_plus_plan": round(t_prep, 3)}, **{k: (round(v, 3) if isinstance(v, float) else v) for k, v in sh.seconds.items()})
+    prep_mine = dict({"generate": round(t_gen, 3), "process_warm_up_seconds": round(t_warm_process, 3) if warm_process else None, "total_tile_create_plus_plan": round(t_prep, 3)}, **{k: (round(v, 3) if isinstance(v, float) else v) for k, v in sh.seconds.items()})
     # the other way of preparing the same plan, timed beside it: its streams must be the measured plan's, byte for byte (per-stream digests read back from the device)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             t0 = time.time()
             if prep_on_device:
@@ -850,8 +903,9 @@ def main():
         "per_rank_ms_per_step": {"wall": [round(r[1], 5) for r in main_per_rank], "device": [round(r[2], 5) for r in main_per_rank],
                                  "min": round(min(r[1] for r in main_per_rank), 5), "max": round(max(r[1] for r in main_per_rank), 5)},
         "launched_by": "self (child torch.distributed.run)" if os.environ.get("TILESPMV_BENCH_SELF_LAUNCHED") else ("torch.distributed.run" if world > 1 else "direct"),
-        "reference_style_timing": {"ms_per_spmv": round(ref_style_ms, 5), "gflops": round(2.0 * sh.local_nnz / (ref_style_ms * 1e-3) * 1e-9, 2), "reps": nref,
+        "reference_style_timing": None if ref_style_ms is None else {"ms_per_spmv": round(ref_style_ms, 5), "gflops": round(2.0 * sh.local_nnz / (ref_style_ms * 1e-3) * 1e-9, 2), "reps": nref,
                                    "protocol": "C loop: gettimeofday around one launch + stream synchronize (reference src/tilespmv_cuda.h:1112-1137), this rank's shard"},
+        "run": "full" if args.full else "plain",   # plain: set-up, warm-up and the timed steps only (--full adds the checks and side measurements)
         "prep_seconds": prep_mine, "prep_seconds_per_rank": prep_all, "host_threads_per_rank": host_threads, "usable_host_cores": usable_cores(),
     }
     if extra:
@@ -861,7 +915,7 @@ def main():
     vals, rowptr, colidx = vals_b, rp_b, ci_b   # (world == 1 below: the block is the whole matrix)
     # the other BASELINE configs (stand-ins) at one GPU, reported beside the headline; never `value`:
     # configs 2-3 are cache-resident (launch/latency-bound), config 5 is the fp32 HBM-roofline case
-    if rank == 0 and world == 1 and args.workload == "laplacian4096" and not args.no_extras:
+    if rank == 0 and world == 1 and args.workload == "laplacian4096" and args.full and not args.no_extras:
         sh.close()  # the headline plan is done: give its 1 GB back before the other matrices are measured
         del xd, yd
         torch.cuda.empty_cache()
@@ -1038,7 +1092,7 @@ def main():
         except Exception as e:
             out["reorder"] = {"error": repr(e)}
         ph_extras.__exit__(None, None, None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         with phase("cpu baseline", 600):
             out["cpu_baseline"] = cpu_baseline(rows, n, rowptr, colidx, vals, x, dtype)
     elif rank == 0:

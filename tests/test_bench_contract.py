@@ -34,10 +34,10 @@ def _full(line):
 
 
 def test_headline_command_line_is_short_and_complete(tmp_path):
-    """The driver's own command (`python bench.py --gpus 1 --steps 20 --warmup 5`: headline workload, every extra, population, CPU baseline) prints ONE line under 4 KB
+    """The driver's own command with --full (`python bench.py --gpus 1 --steps 20 --warmup 5 --full`: headline workload, every extra, population, CPU baseline) prints ONE line under 4 KB
     that carries the contract keys, `roofline` and `cpu_baseline`; everything else sits in the sidecar."""
     full = str(tmp_path / "full.json")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full-json", full], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--full-json", full], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -56,7 +56,7 @@ def test_headline_command_line_is_short_and_complete(tmp_path):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "laplacian512", "--steps", "10", "--warmup", "3"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "laplacian512", "--steps", "10", "--warmup", "3", "--full"], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = _last_json(r.stdout)
@@ -87,7 +87,7 @@ def test_single_gpu_line():
 
 def test_single_gpu_line_real_valued_data(tmp_path):
     """--data real: U(-1, 1) values and x (seed 12345), whole-y tolerance check; --cache: the second run reads the Tile_matrix cache."""
-    cmd = [sys.executable, "bench.py", "--workload", "laplacian512", "--steps", "10", "--warmup", "3", "--data", "real", "--no-cpu-baseline",
+    cmd = [sys.executable, "bench.py", "--workload", "laplacian512", "--steps", "10", "--warmup", "3", "--data", "real", "--full", "--no-cpu-baseline",
            "--no-extras", "--cache", str(tmp_path)]
     lines = []
     for _ in range(2):
@@ -110,7 +110,7 @@ def test_single_gpu_line_real_valued_data(tmp_path):
 
 def test_two_rank_rehearsal_over_gloo():
     # the driver's command shape, bare: bench.py starts its own ranks (child torch.distributed.run) and relays the line
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "3", "--backend", "gloo", "--workload", "laplacian512"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "3", "--backend", "gloo", "--workload", "laplacian512", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -129,7 +129,7 @@ def test_two_rank_rehearsal_over_gloo():
 
 def test_two_rank_halo_mode_over_gloo():
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--backend", "gloo", "--workload", "laplacian512", "--combine", "halo",
-           "--data", "real"]
+           "--data", "real", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -140,7 +140,7 @@ def test_two_rank_halo_mode_over_gloo():
 def test_one_rank_through_the_launcher_equals_the_bare_run(tmp_path):
     """The SCALE N = 1 point (driver: `python -m torch.distributed.run --nproc-per-node 1 ... bench.py --gpus 1`) must agree with BENCH (`python bench.py`):
     same code path (no process group at world size 1), same line, same value within run-to-run noise."""
-    args = ["--gpus", "1", "--steps", "100", "--warmup", "10", "--workload", "laplacian2048", "--no-cpu-baseline", "--no-extras"]
+    args = ["--gpus", "1", "--steps", "100", "--warmup", "10", "--workload", "laplacian2048", "--full", "--no-cpu-baseline", "--no-extras"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     bare = subprocess.run([sys.executable, "bench.py"] + args + ["--full-json", str(tmp_path / "bare.json")], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert bare.returncode == 0, bare.stderr[-2000:]
@@ -166,7 +166,7 @@ def test_four_rank_rehearsal_over_gloo():
     """More than two ranks through the driver's command shape, all on device 0 over gloo (the GPU box lets 6 processes of one job use its card at once: this test process +
     4 ranks stay below that; scripts/archive/rounds/r4_rehearsal.sh runs 6 ranks bare): the plumbing of an 8-rank run — per-rank generation and preprocessing with a share of the host cores
     each, the three y combines with the neighbours' rows checked, max-over-ranks timing — before there is an 8-GPU node."""
-    cmd = [sys.executable, "bench.py", "--gpus", "4", "--steps", "10", "--warmup", "3", "--backend", "gloo", "--workload", "laplacian1024"]
+    cmd = [sys.executable, "bench.py", "--gpus", "4", "--steps", "10", "--warmup", "3", "--backend", "gloo", "--workload", "laplacian1024", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -179,3 +179,83 @@ def test_four_rank_rehearsal_over_gloo():
     assert all(v["check_full_y_on_every_rank"] == "pass" for k, v in d["with_y_combine"].items() if k != "halo"), d["with_y_combine"]
     assert d["with_y_combine"]["halo"]["check_own_rows_on_every_rank"] == "pass"
     assert 1 <= d["host_threads_per_rank"] <= 16
+
+
+def _csr_rows_compat(rp, ci, pick):
+    """y at rows `pick` of A x on the reference driver's data (val[k] = k % 10, x[j] = j % 10), from the CSR arrays alone: exact in float64."""
+    import numpy as np
+    lens = (rp[pick + 1] - rp[pick]).astype(np.int64)
+    first = np.cumsum(lens) - lens
+    k = np.repeat(rp[pick].astype(np.int64), lens) + np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(first, lens)
+    return np.add.reduceat(((k % 10) * (ci[k].astype(np.int64) % 10)).astype(np.float64), first)
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_y(tmp_path):
+    """A plain run (no --full): set-up, W warm-ups, K timed steps, the line — no parity check, no side measurement.  --dump-outputs writes y of the
+    last timed step; the same arguments give the same inputs, so two runs write the same y, and on the reference driver's data it is the CSR product exactly."""
+    import numpy as np
+    from tilespmv_amd import generators as G
+    ys = []
+    for rep in range(2):
+        out = tmp_path / ("out%d" % rep)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "laplacian512", "--dump-outputs", str(out),
+                            "--full-json", str(tmp_path / "full.json")], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _last_json(r.stdout)
+        for k in REQUIRED:
+            assert k in line, k
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["run"] == "plain" and line["check"] == "skipped"
+        assert line["cpu_baseline"] is None and line["reference_style_ms"] is None and "steady_state" not in line and "other_workloads" not in line
+        assert abs(line["value"] - 2 * line["config"]["nnz"] / (line["ms_per_step"] * 1e-3) * 1e-9) / line["value"] < 0.02
+        f = _full(line)
+        assert f["device_state_under_load"] is None and "measured_ceilings_gbps" not in f["roofline"] and "other_path" not in f["prep_seconds"]
+        assert f["prep_seconds"]["process_warm_up_seconds"] is None and set(f["phase_seconds"]) == {"prepare (Tile_create + plan)", "parity check", "timed steps", "dump outputs"}
+        assert os.listdir(out) == ["y.npy"]
+        ys.append(np.load(out / "y.npy"))
+    m, n, rp, ci = G.laplacian5pt(512)
+    rows = (m // 16) * 16
+    assert ys[0].dtype == np.float64 and ys[0].shape == (rows,)
+    assert np.array_equal(ys[0], _csr_rows_compat(rp, ci, np.arange(rows))) and np.array_equal(ys[0], ys[1])
+
+
+def test_plain_headline_run_is_lean_and_dumps_a_fixed_sample(tmp_path):
+    """The benchmark's own command, plain, with --dump-outputs: at most 30 s outside its W + K steps, from start to exit; y of the headline (134 MB)
+    is written as the fixed seeded sample of bench.dump_rows (< 64 MB), equal to the CSR product at those rows."""
+    import time
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from tilespmv_amd import generators as G
+    out = tmp_path / "out"
+    t0 = time.time()
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out), "--full-json", str(tmp_path / "full.json")],
+                       cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _last_json(r.stdout)
+    assert line["config"]["workload"] == "laplacian4096" and line["steps"] == 20 and line["run"] == "plain"
+    assert wall - 25 * line["ms_per_step"] * 1e-3 <= 30.0, wall
+    assert os.listdir(out) == ["y_sample.npy"] and os.path.getsize(out / "y_sample.npy") <= 64 << 20
+    y = np.load(out / "y_sample.npy")
+    m, n, rp, ci = G.laplacian5pt(4096)
+    pick = bench.dump_rows(line["config"]["rows"], 8)
+    assert y.dtype == np.float64 and y.shape == pick.shape
+    assert np.array_equal(y, _csr_rows_compat(rp, ci, pick))
+
+
+def test_two_rank_dump_holds_every_ranks_rows(tmp_path):
+    """--dump-outputs with two ranks (over gloo on the one GPU): rank 0 writes the whole y, every rank's block in row order — with y left sharded and with the halo form."""
+    import numpy as np
+    from tilespmv_amd import generators as G
+    m, n, rp, ci = G.laplacian5pt(512)
+    want = _csr_rows_compat(rp, ci, np.arange((m // 16) * 16))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    for combine in ("none", "halo"):
+        out = tmp_path / combine
+        cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--backend", "gloo", "--workload", "laplacian512", "--combine", combine,
+               "--dump-outputs", str(out), "--full-json", str(tmp_path / "full.json")]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _last_json(r.stdout)
+        assert line["ranks"] == 2 and line["steps"] == 4 and "with_y_combine" not in line
+        assert np.array_equal(np.load(out / "y.npy"), want), combine

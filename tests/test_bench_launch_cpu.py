@@ -81,3 +81,25 @@ def test_launcher_kills_ranks_that_do_not_finish():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--workload", "laplacian64", "--steps", "2", "--warmup", "1"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
     assert r.returncode == 124 and "did not finish within" in r.stderr
+
+
+def test_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """--dump-outputs: y whole while it fits the budget, else the same seeded sample of rows every time (ascending, distinct, < 64 MB in either dtype)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_rows(4096, 8) is None and bench.dump_rows(bench.DUMP_BUDGET // 8, 8) is None
+    for itemsize in (8, 4):
+        rows = 2 * bench.DUMP_BUDGET // itemsize + 5
+        a, b = bench.dump_rows(rows, itemsize), bench.dump_rows(rows, itemsize)
+        assert np.array_equal(a, b) and len(a) * itemsize == bench.DUMP_BUDGET <= 64 << 20
+        assert a[0] >= 0 and a[-1] < rows and np.all(np.diff(a) > 0)
+    y = np.arange(1000, dtype=np.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "small"), y, 0, len(y), 0, 1, None)
+    got = np.load(tmp_path / "small" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y)
+    rows = bench.DUMP_BUDGET // 8 + 16
+    y = np.arange(rows, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "big"), y, 0, rows, 0, 1, None)
+    assert os.listdir(tmp_path / "big") == ["y_sample.npy"]
+    assert np.array_equal(np.load(tmp_path / "big" / "y_sample.npy"), y[bench.dump_rows(rows, 8)])

@@ -394,7 +394,7 @@ def test_bench_takes_any_mtx_file(torch_cuda, tmp_path):
     G.write_mtx(str(gen), m2, n2, rp2, ci2)
     for path, rows, nnz in ((sym, m, A.nnz), (gen, m2, len(ci2))):
         for rep in range(2):     # second run: CSR cache hit
-            r = subprocess.run([sys.executable, "bench.py", "--workload", str(path), "--steps", "10", "--warmup", "3", "--no-extras", "--no-cpu-baseline", "--cache", str(tmp_path / "cache"),
+            r = subprocess.run([sys.executable, "bench.py", "--workload", str(path), "--steps", "10", "--warmup", "3", "--full", "--no-extras", "--no-cpu-baseline", "--cache", str(tmp_path / "cache"),
                                 "--full-json", str(tmp_path / "full.json")], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
             assert r.returncode == 0, r.stderr[-2000:]
             line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
