@@ -122,6 +122,10 @@ void Tile_create(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA,
  * to 12 entries, ELL at row-length variation <= 0.2: src/csr2tile.h:150,159,267-270; COO_NNZ_TH src/common.h:45-47).  The result is
  * still a valid Tile_matrix for tilespmv_cpu and every plan; profiles/r03_selection_cdna4.txt has what it changes. */
 #define TILESPMV_CREATE_CDNA4 4u
+/* TILESPMV_CREATE_VALUE_MAP (opt-in; tilespmv_plan_create_from_csr / _from_device_csr only, Tile_create_device ignores it): the plan also keeps a device-resident VALUE MAP — for every
+ * value slot of its streams the position of the source nonzero in the CSR arrays — so that tilespmv_plan_update_values (below) can rewrite every value the plan holds from a new value
+ * array of the same pattern.  See tilespmv_plan_update_values for the contract. */
+#define TILESPMV_CREATE_VALUE_MAP 8u
 void Tile_create_ex(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA,
                     const MAT_PTR_TYPE *csrRowPtrA, const int *csrColIdxA,
                     const MAT_VAL_TYPE *csrValA, unsigned flags);
@@ -363,7 +367,9 @@ void tilespmv_plan_destroy(tilespmv_plan *plan);
  * Tile_create's output (same streams, same y).  Not every option has a device path: returns -4 (and builds nothing) for the first-generation kernel, the CSR fallback
  * mode and whole CSR tiles (csr_split = 0) — use Tile_create + tilespmv_plan_create for those (HYB tiles, TILESPMV_CREATE_HYB in `create_flags`, are served since round 6).  autotune = 1 is served: every candidate plan is built from the one device-resident tiled
  * matrix (the CSR-fallback candidate, which has no device path, is not among them).  Other return codes as above.
- * Peak device memory during the call: the CSR arrays + the tiled matrix + the sort's key buffers (about 40 bytes per nonzero in fp64) beside the plan. */
+ * Peak device memory during the call: the CSR arrays + the tiled matrix + the sort's key buffers (about 40 bytes per nonzero in fp64) beside the plan.  With TILESPMV_CREATE_VALUE_MAP add
+ * the value map (4 bytes per value slot of the plan — about 4.5 to 6 bytes per nonzero; it stays with the plan) and, for tilespmv_plan_create_from_device_csr, one more value array
+ * (sizeof(MAT_VAL_TYPE) bytes per nonzero, freed before the call returns). */
 int Tile_create_device(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA, const MAT_PTR_TYPE *csrRowPtrA,
                        const int *csrColIdxA, const MAT_VAL_TYPE *csrValA, unsigned flags);
 int tilespmv_plan_create_from_csr(tilespmv_plan **plan, int rowA, int colA, MAT_PTR_TYPE nnzA, const MAT_PTR_TYPE *csrRowPtrA,
@@ -374,6 +380,22 @@ int tilespmv_plan_create_from_csr(tilespmv_plan **plan, int rowA, int colA, MAT_
 int tilespmv_plan_create_from_device_csr(tilespmv_plan **plan, int rowA, int colA, MAT_PTR_TYPE nnzA, const MAT_PTR_TYPE *d_csrRowPtrA,
                                          const int *d_csrColIdxA, const MAT_VAL_TYPE *d_csrValA, unsigned create_flags,
                                          const tilespmv_plan_options *opts);
+
+/* New values, same pattern (a solver that reassembles its matrix: interior-point KKT systems, Newton on a nonlinear FEM problem, variable-coefficient time steps).
+ * The plan must have been created with TILESPMV_CREATE_VALUE_MAP by tilespmv_plan_create_from_csr or tilespmv_plan_create_from_device_csr.  d_csrVal is DEVICE memory holding the values
+ * of the CSR the plan was created from, in the same order — same row pointer, same column indices, same duplicates, indexed like the creation's value argument (a shard,
+ * tilerow_begin / tilerow_end, takes the full array too and reads only its own tile-rows' values).  Every value of the plan is rewritten in one asynchronous pass on `stream`:
+ * nothing is rebuilt, allocated or copied to or from the host, no synchronisation — safe to capture into a hipGraph; the single-stream rule of tilespmv_plan_spmv holds (an SpMV of
+ * this plan and an update must not run at the same time on two streams).
+ * Contract: a plan created with the flag from values v1 and updated to v2 holds exactly the bytes a plan created with the flag from v2 holds (tilespmv_plan_stream_digests agree,
+ * the facts agree, y agrees bit for bit where TILESPMV_INFO_ENTRY_ORDERED is 1).  To make that possible a flagged plan's layout follows the PATTERN alone: an explicit zero of
+ * the CSR is a stored entry like any other (an unflagged plan treats an ELL slot that holds 0 at column nibble 0 as padding, and a packed entry record of value 0, offset 0 and
+ * destination 0 as null).  On data without explicit zeros a flagged and an unflagged plan of the same matrix and options have identical SpMV streams.
+ * The pattern is the caller's promise: a changed pattern cannot be detected.  Values must be finite, like every value a plan multiplies.
+ * Returns a hipError_t value (0 = success, hipErrorInvalidValue for a NULL argument), or TILESPMV_ERR_NO_VALUE_MAP (-4) — plan untouched — for a plan created without the flag or
+ * by tilespmv_plan_create (a host Tile_matrix has no link back to CSR order).  TILESPMV_INFO_VALUE_MAP_BYTES is the map's size. */
+#define TILESPMV_ERR_NO_VALUE_MAP (-4)
+int tilespmv_plan_update_values(tilespmv_plan *plan, const MAT_VAL_TYPE *d_csrVal, void *stream);
 
 /* Values: x (and the matrix values) must be FINITE.  Zero-padded payload is multiplied by real x entries — the padding
  * slots of ELL / HYB tiles exactly as in the reference (src/tilespmv_cpu.h:173-192 walks all `width` slots), and in
@@ -480,7 +502,8 @@ enum {
     TILESPMV_INFO_TIMED_CHOICES_US = 31,  /* microseconds of plan creation spent TIMING candidates (placement retry, column panels / slices); part of build_us; 0 = nothing was timed */
     TILESPMV_INFO_DEVICE_BUILD = 32,      /* 1: built by tilespmv_plan_create_from_csr (Tile_create, COUNT / EMIT / ENCODE on the device) */
     TILESPMV_INFO_TILE_CREATE_US = 33,    /* ... microseconds of its device Tile_create, the upload of the CSR arrays included (0 otherwise) */
-    TILESPMV_INFO_COUNT = 34
+    TILESPMV_INFO_VALUE_MAP_BYTES = 34,   /* bytes of the value map (TILESPMV_CREATE_VALUE_MAP; 0 without it) — not part of TILESPMV_INFO_DEVICE_BYTES, which stays the SpMV plan's */
+    TILESPMV_INFO_COUNT = 35
 };
 void tilespmv_plan_info(const tilespmv_plan *plan, long long *out /* [TILESPMV_INFO_COUNT] */);
 /* Test / audit aid: one (member offset in the plan object, bytes, FNV-1a-64 of the bytes read back from the device) triple per stream of the plan, at most max_streams of them

@@ -18,7 +18,8 @@ _CACHE = {}
 
 INFO_NAMES = ["device_bytes", "stream_bytes", "nnz", "rows", "tiles", "coo_mode", "dense_mode", "kernel",
               "num_tasks", "num_split_rows", "fallback_nnz", "build_us", "upload_us", "entry_mode", "entry_ordered", "strip_cost",
-              "wg_strips", "list_entries", "derived_units", "brick_order", "desc_bytes", "nt_stream", "retired_22", "retired_23", "placement_tries", "retired_25", "x_panels", "x_panel_merge", "scattered_entries", "x_slice_passes", "csr_form", "timed_choices_us", "device_build", "tile_create_us"]
+              "wg_strips", "list_entries", "derived_units", "brick_order", "desc_bytes", "nt_stream", "retired_22", "retired_23", "placement_tries", "retired_25", "x_panels", "x_panel_merge", "scattered_entries", "x_slice_passes", "csr_form", "timed_choices_us", "device_build", "tile_create_us",
+              "value_map_bytes"]
 
 
 KNOB_DEFAULT = -1
@@ -88,6 +89,8 @@ def load(dtype=np.float64):
     lib.tilespmv_plan_create_from_csr.restype = C.c_int
     lib.tilespmv_plan_create_from_device_csr.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(PlanOptions)]
     lib.tilespmv_plan_create_from_device_csr.restype = C.c_int
+    lib.tilespmv_plan_update_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_plan_update_values.restype = C.c_int
     lib.tilespmv_plan_stream_digests.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_longlong]
     lib.tilespmv_plan_stream_digests.restype = C.c_longlong
     lib.Tile_destroy.argtypes = [TP]
@@ -172,4 +175,5 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_csr_save", "tilespmv_csr_load", "mmio_allinone_cached", "tilespmv_mtx_write",
                     "tilespmv_plan_time_reference_style", "tilespmv_plan_reserve_spmm", "tilespmv_plan_options_layout", "tilespmv_plan_layout_stages",
                     "Tile_create_device", "tilespmv_plan_create_from_csr", "tilespmv_plan_stream_digests", "tilespmv_plan_create_from_device_csr",
-                    "tilespmv_reorder_rcm", "tilespmv_csr_permute", "tilespmv_csr_bandwidth", "tilespmv_permute_vector"]
+                    "tilespmv_reorder_rcm", "tilespmv_csr_permute", "tilespmv_csr_bandwidth", "tilespmv_permute_vector",
+                    "tilespmv_plan_update_values"]

@@ -18,7 +18,8 @@ _I, _U = _lib._I, _lib._U
 COO_AUTO, COO_IN_TILE, COO_FALLBACK = 0, 1, 2
 DENSE_AUTO, DENSE_MFMA, DENSE_VALU = 0, 1, 2
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_STREAM = 0, 1, 2
-CREATE_HYB, CREATE_QUIET, CREATE_CDNA4 = 1, 2, 4
+CREATE_HYB, CREATE_QUIET, CREATE_CDNA4, CREATE_VALUE_MAP = 1, 2, 4, 8
+ERR_NO_VALUE_MAP = -4   # tilespmv_plan_update_values on a plan without a value map
 
 
 def _p(a, t):
@@ -256,9 +257,11 @@ class Plan:
         self.h = h
 
     @classmethod
-    def from_csr(cls, rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, cdna4=False, hyb=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, autotune=False, **knobs):
+    def from_csr(cls, rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, cdna4=False, hyb=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, autotune=False,
+                 value_map=False, **knobs):
         """``tilespmv_plan_create_from_csr``: the tiled matrix and the plan's streams are built on the device; only the CSR arrays cross the bus.
-        Raises ``NotImplementedError`` for the options that have no device path (rc -4: first-generation kernel, CSR fallback, csr_split=0).  ``autotune=True``: every candidate is built from the one device-resident tiled matrix."""
+        Raises ``NotImplementedError`` for the options that have no device path (rc -4: first-generation kernel, CSR fallback, csr_split=0).  ``autotune=True``: every candidate is built from the one device-resident tiled matrix.
+        ``value_map=True`` (TILESPMV_CREATE_VALUE_MAP): the plan keeps a value map, so that ``update_values`` can give it new values of the same pattern."""
         dtype = np.dtype(dtype or np.asarray(csrValA).dtype)
         lib = _lib.load(dtype)
         rp, ci, v = _csr(lib, csrRowPtrA, csrColIdxA, csrValA)
@@ -267,7 +270,7 @@ class Plan:
         self.rowA, self.colA, self.nnzA = rowA, colA, nnzA
         opts = _lib.PlanOptions(coo_mode, dense_mode, kernel, tilerow_begin, tilerow_end, autotune, **knobs)
         h = C.c_void_p()
-        rc = lib.tilespmv_plan_create_from_csr(C.byref(h), rowA, colA, nnzA, _p(rp, C.c_int), _p(ci, C.c_int), _p(v, lib._vt), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_HYB if hyb else 0), C.byref(opts))
+        rc = lib.tilespmv_plan_create_from_csr(C.byref(h), rowA, colA, nnzA, _p(rp, C.c_int), _p(ci, C.c_int), _p(v, lib._vt), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_HYB if hyb else 0) | (CREATE_VALUE_MAP if value_map else 0), C.byref(opts))
         if rc == -4:
             raise NotImplementedError("tilespmv_plan_create_from_csr: these options have no device path")
         if rc != 0 or not h:
@@ -276,7 +279,7 @@ class Plan:
         return self
 
     @classmethod
-    def from_device_csr(cls, rowA, colA, nnzA, d_rowptr, d_colidx, d_vals, dtype, cdna4=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, **knobs):
+    def from_device_csr(cls, rowA, colA, nnzA, d_rowptr, d_colidx, d_vals, dtype, cdna4=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, value_map=False, **knobs):
         """``tilespmv_plan_create_from_device_csr``: like ``from_csr`` with the CSR arrays already in device memory — ``d_rowptr`` / ``d_colidx`` (int32) and ``d_vals`` are device
         ADDRESSES (e.g. ``tensor.data_ptr()`` of the crow / col / values tensors of a torch CSR tensor cast to int32); borrowed for the call."""
         dtype = np.dtype(dtype)
@@ -286,13 +289,22 @@ class Plan:
         self.rowA, self.colA, self.nnzA = rowA, colA, nnzA
         opts = _lib.PlanOptions(coo_mode, dense_mode, kernel, tilerow_begin, tilerow_end, False, **knobs)
         h = C.c_void_p()
-        rc = lib.tilespmv_plan_create_from_device_csr(C.byref(h), rowA, colA, nnzA, C.c_void_p(d_rowptr), C.c_void_p(d_colidx), C.c_void_p(d_vals), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0), C.byref(opts))
+        rc = lib.tilespmv_plan_create_from_device_csr(C.byref(h), rowA, colA, nnzA, C.c_void_p(d_rowptr), C.c_void_p(d_colidx), C.c_void_p(d_vals), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_VALUE_MAP if value_map else 0), C.byref(opts))
         if rc == -4:
             raise NotImplementedError("tilespmv_plan_create_from_device_csr: these options have no device path")
         if rc != 0 or not h:
             raise RuntimeError("tilespmv_plan_create_from_device_csr failed (%d)" % rc)
         self.h = h
         return self
+
+    def update_values(self, d_vals, stream=0):
+        """``tilespmv_plan_update_values``: every value of the plan rewritten from ``d_vals`` (device ADDRESS of the CSR value array the plan was created from, same pattern,
+        new values), asynchronously on ``stream``.  The plan must have been created with ``value_map=True``."""
+        rc = self.lib.tilespmv_plan_update_values(self.h, C.c_void_p(d_vals), C.c_void_p(stream))
+        if rc == ERR_NO_VALUE_MAP:
+            raise RuntimeError("tilespmv_plan_update_values: the plan has no value map (create it with value_map=True)")
+        if rc != 0:
+            raise RuntimeError("tilespmv_plan_update_values: HIP error %d" % rc)
 
     def spmv(self, d_x, d_y, stream=0):
         rc = self.lib.tilespmv_plan_spmv(self.h, C.c_void_p(d_x), C.c_void_p(d_y), C.c_void_p(stream))

@@ -863,7 +863,8 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
         return -4;
     const double t0 = now_us();
     DevTile *D = nullptr;
-    int rc = devtile_create(&D, rowA, colA, rowptr, colidx, val, create_flags, false, csr_on_device);
+    const bool value_map = (create_flags & TILESPMV_CREATE_VALUE_MAP) != 0;   // built from stand-in values, the caller's written in afterwards (hip_value_map.hip)
+    int rc = devtile_create(&D, rowA, colA, rowptr, colidx, val, create_flags, false, csr_on_device, value_map);
     if (rc != 0) return rc;
     const double t1 = now_us();
     // the tile LIST on the host (what CHOOSE / CUT / the stride detection read); everything else of the tiled matrix stays where it is
@@ -889,6 +890,19 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
     const double t2 = now_us();
     rc = Kd.autotune ? plan_create_tuned(out, &H, rowA, colA, nnzA, Kd, D) : plan_create_one(out, &H, rowA, colA, nnzA, Kd, D);   // (measured selection: every candidate from the same device-resident tiled matrix)
     const double t3 = now_us();
+    if (rc == 0 && *out && value_map) {
+        // the plan's placement is final: the map is allocated now, outside the arena, and never moves.  The caller's values: their device array, or (host CSR) the DevTile's
+        // value array, which held the stand-ins, refilled from the host
+        const val_t *d_src = val;
+        if (!csr_on_device) {
+            d_src = D->val - D->val_base;   // (indexed like the caller's array: the map holds positions from the row pointer's first entry on)
+            if (D->nnz > 0 && hipMemcpy(const_cast<val_t *>(D->val), val + D->val_base, (size_t)D->nnz * sizeof(val_t), hipMemcpyHostToDevice) != hipSuccess) {
+                fprintf(stderr, "tilespmv: value map: values to the device failed\n"); (void)hipGetLastError(); rc = -3;
+            }
+        }
+        if (rc == 0) rc = value_map_attach(*out, D->val_base + D->nnz, d_src);
+        if (rc != 0) { tilespmv_plan_destroy(*out); *out = nullptr; }
+    }
     devtile_destroy(D);
     if (getenv("TILESPMV_PLAN_VERBOSE")) fprintf(stderr, "tilespmv: plan from CSR: plan build %.1f ms, tiled matrix released in %.1f ms\n", (t3 - t2) * 1e-3, (now_us() - t3) * 1e-3);
     if (rc == 0 && *out) {

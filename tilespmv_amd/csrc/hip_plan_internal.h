@@ -131,6 +131,15 @@ struct tilespmv_plan {
         auto it = std::find(allocs.begin(), allocs.end(), p);
         if (it != allocs.end()) allocs.erase(it);
     }
+    // value map (TILESPMV_CREATE_VALUE_MAP, hip_value_map.hip): per value slot of the value-carrying streams, the CSR position its value comes from (-1: padding); one
+    // allocation of its own outside the arena, made after the placement was chosen.  vmap_slot[k] = the plan member that points at stream k, vmap_n[k] its slots, vmap_off[k]
+    // where its part of the map begins; vmap_erec[k]: the stream holds entry records (only their value words are written)
+    static constexpr int VMAP_STREAMS = 5;
+    int *vmap = nullptr;
+    int vmap_streams = 0;
+    const void **vmap_slot[VMAP_STREAMS] = {};
+    long long vmap_n[VMAP_STREAMS] = {}, vmap_off[VMAP_STREAMS] = {};
+    bool vmap_erec[VMAP_STREAMS] = {};
     size_t arena_used = 0;              // bytes handed out by upload() so far
     char *arena_at = nullptr; size_t arena_left = 0, arena_block = (size_t)256 << 20, arena_next = (size_t)1 << 20, size_hint = 0;   // bump allocator of upload(); size_hint = the builder's estimate of the plan's bytes
     bool dry = false;                   // layout-digest build: no HIP call, streams are hashed instead of uploaded
@@ -319,6 +328,10 @@ inline bool pack_list(const std::vector<PEnt> &ents, int dest_bits, std::vector<
 
 // the value pass of the ENCODE stage on the device (hip_kernels.hip k_pair_values)
 hipError_t launch_pair_values(const val_t *src, val_t *dst, const int4 *map, int ntasks);
+
+// hip_value_map.hip: reads the value map off the streams of a plan built from stand-in values (hip_tile_create.h vmap_encode), positions below `limit`, then writes the values of
+// d_val in (d_val indexed by those positions).  Returns 0, -3 HIP error, -6 a slot names a position outside [0, limit) (internal error)
+int value_map_attach(tilespmv_plan *plan, long long limit, const val_t *d_val);
 
 
 // Second-generation layout (hip_plan_stream.hip): fills plan->st / plan->dn / the whole-tile pass of plan->dev for tile-rows [tr0, tr1).

@@ -17,6 +17,8 @@ struct DevTile {
     long long nnz = 0;                     // rowptr[rowA]
     const int *rowptr = nullptr, *colidx = nullptr;   // the uploaded CSR (device)
     const val_t *val = nullptr;
+    long long val_base = 0;                // the row pointer's first entry (host CSR that is a row block of a larger matrix): position j of the arrays above is position val_base + j of the caller's
+    bool val_owned = false;                // val is an array of the DevTile's own (not the caller's device array)
     const unsigned long long *key = nullptr;   // per nonzero, tile order: tile-row << (8 + cb_bits) | column block << 8 | local row << 4 | local column
     const int *ent = nullptr;              // per nonzero, tile order: its position in the CSR arrays
     const int *tile_bi = nullptr;          // per tile: its tile-row
@@ -30,9 +32,29 @@ struct DevTile {
     double ms_upload = 0, ms_sort = 0, ms_tiles = 0, ms_select = 0, ms_pack = 0;
 };
 
+// Value-map builds (TILESPMV_CREATE_VALUE_MAP): the tiled matrix and the plan are built from STAND-IN values — the value of the nonzero at CSR position j is the number whose bit
+// pattern is that of the smallest positive normal number plus j — instead of the caller's.  The builders only move values, so every value slot of the finished plan names its
+// source (bits 0: padding), and the two layout rules that look at a value (an ELL row's length for absorbed entries, plan_tile_ops.h; null records of the packed lists, erec_is_null)
+// see a nonzero wherever a nonzero is stored: they follow the pattern, never the values (hip_value_map.hip reads the map off the streams, then writes the caller's values in).
+#if defined(TILESPMV_F32)
+typedef unsigned vmap_bits_t;
+constexpr vmap_bits_t VMAP_BIAS = 0x00800000u;                // FLT_MIN
+constexpr long long VMAP_MAX_INDEX = 0x7F7FFFFFll - 0x00800000ll;   // ... + j stays finite (FLT_MAX) up to here
+#else
+typedef unsigned long long vmap_bits_t;
+constexpr vmap_bits_t VMAP_BIAS = 0x0010000000000000ull;      // DBL_MIN
+constexpr long long VMAP_MAX_INDEX = 0x7FFFFFFFll;           // (int32 CSR positions)
+#endif
+static_assert(sizeof(vmap_bits_t) == sizeof(val_t), "stand-in values are bit patterns of val_t");
+__host__ __device__ inline val_t vmap_encode(long long j) { const vmap_bits_t b = VMAP_BIAS + (vmap_bits_t)j; val_t v; __builtin_memcpy(&v, &b, sizeof(v)); return v; }
+__host__ __device__ inline long long vmap_decode(val_t v) { vmap_bits_t b; __builtin_memcpy(&b, &v, sizeof(b)); return b == 0 ? -1 : (long long)(b - VMAP_BIAS); }
+
 // rc 0, -1 no device, -2 int32 offsets of Tile_matrix exceeded, -3 HIP error / out of device memory
 // csr_on_device: the three CSR arrays are DEVICE pointers already (row pointer based at 0; borrowed, not freed): no upload at all
-int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device = false);
+// stand_in_values: DevTile::val holds vmap_encode(position in the caller's value array) instead of the caller's values (a device array of its own, whichever side the CSR came from;
+// nothing of the caller's values is read)
+int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device = false,
+                   bool stand_in_values = false);
 void devtile_destroy(DevTile *D);
 // every member array into freshly malloc'd host arrays (Tile_destroy frees them)
 int devtile_download(const DevTile *D, Tile_matrix *host);

@@ -284,6 +284,11 @@ __global__ void k_tc_widen(long long n, const int *__restrict__ a, long long *__
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = a[i];
 }
+__global__ void k_tc_stand_in(long long n, long long base, val_t *__restrict__ v)   // (hip_tile_create.h vmap_encode)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = vmap_encode(base + i);
+}
 __global__ void k_tc_iota(int n, int *__restrict__ a)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -346,7 +351,7 @@ inline void dfree(DevTile *D, const void *p)   // (an array carved from a pool i
 }
 inline unsigned blocks_for(long long n, int per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
 
-int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device)
+int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device, bool stand_in)
 {
     const bool verbose = getenv("TILESPMV_CREATE_VERBOSE") != nullptr, cdna4 = flags & TILESPMV_CREATE_CDNA4, allow_hyb = flags & TILESPMV_CREATE_HYB;
     pool_end();   // (no pool left over from a build that failed on this thread)
@@ -365,7 +370,8 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
         for (int r = 0; r <= rowA; r++) rebased[(size_t)r] = (int)(h_rowptr[r] - base);
         h_rowptr = rebased.data(); h_colidx += base; h_val += base;
     }
-    D->rowA = rowA; D->colA = colA; D->nnz = nnz;
+    D->rowA = rowA; D->colA = colA; D->nnz = nnz; D->val_base = base;
+    if (stand_in && nnz > 0 && base + nnz - 1 > VMAP_MAX_INDEX) { fprintf(stderr, "tilespmv: value map: %lld value positions exceed what a stand-in value can name\n", base + nnz); return -2; }
     T.tilem = tilem; T.tilen = tilen;
     const int cb_bits = bits_for(tilen), bi_bits = bits_for(tilem);
     D->cb_bits = cb_bits;
@@ -379,14 +385,17 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     ValueUpload values;   // (joined on every way out of this function, before anybody frees d_val)
     double t0 = now_ms();
     int *d_rowptr = nullptr, *d_colidx = nullptr; val_t *d_val = nullptr;
-    if (csr_on_device) { d_rowptr = const_cast<int *>(h_rowptr); d_colidx = const_cast<int *>(h_colidx); d_val = const_cast<val_t *>(h_val); }   // (borrowed: never in D->allocs)
-    else {
+    if (csr_on_device) {   // (borrowed: never in D->allocs)
+        d_rowptr = const_cast<int *>(h_rowptr); d_colidx = const_cast<int *>(h_colidx); d_val = const_cast<val_t *>(h_val);
+        if (stand_in) { if (dalloc(D, &d_val, (size_t)nnz, false)) return -3; D->val_owned = true; }
+    } else {
         if (dalloc(D, &d_rowptr, (size_t)rowA + 1, false) || dalloc(D, &d_colidx, (size_t)nnz, false) || dalloc(D, &d_val, (size_t)nnz, false)) return -3;
+        D->val_owned = true;
         TC_TRY(hipMemcpy(d_rowptr, h_rowptr, ((size_t)rowA + 1) * sizeof(int), hipMemcpyHostToDevice));
         if (nnz) TC_TRY(hipMemcpy(d_colidx, h_colidx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
         // the values follow on a stream of their own, fed by a helper thread (a copy from pageable memory holds its caller until the last chunk is staged), while this thread sorts the
         // keys, lists the tiles and selects their formats: nothing before the packing reads a value (config 4: 0.67 GB = 12.6 ms of bus time behind 7 ms of kernels)
-        if (nnz) {
+        if (nnz && !stand_in) {
             int dev = 0;
             TC_TRY(hipGetDevice(&dev));
             bool started = false;
@@ -394,6 +403,10 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
             if (started) t_free_later = &later;
             else TC_TRY(hipMemcpy(d_val, h_val, (size_t)nnz * sizeof(val_t), hipMemcpyHostToDevice));
         }
+    }
+    if (stand_in && nnz > 0) {   // the stand-in values instead of the caller's (hip_tile_create.h): nothing of theirs is read
+        hipLaunchKernelGGL(k_tc_stand_in, dim3(blocks_for(nnz, 256)), dim3(256), 0, 0, nnz, base, d_val);
+        TC_TRY(hipGetLastError());
     }
     D->rowptr = d_rowptr; D->colidx = d_colidx; D->val = d_val;
     D->ms_upload = now_ms() - t0; t0 = now_ms();
@@ -608,13 +621,13 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
 
 }  // namespace
 
-int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device)
+int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device, bool stand_in_values)
 {
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); fprintf(stderr, "tilespmv: no HIP device visible — the device Tile_create has no CPU fallback (use Tile_create)\n"); return -1; }
     DevTile *D = new DevTile();
-    const int rc = create_impl(D, rowA, colA, h_rowptr, h_colidx, h_val, flags, want_deferred, csr_on_device);
+    const int rc = create_impl(D, rowA, colA, h_rowptr, h_colidx, h_val, flags, want_deferred, csr_on_device, stand_in_values);
     pool_end();
     if (rc != 0) { devtile_destroy(D); return rc; }
     *out = D;

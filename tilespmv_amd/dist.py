@@ -60,24 +60,29 @@ class ShardedSpMV:
     exercised without a GPU.
     """
 
-    def __init__(self, rank, world, rows, cols, rowptr, colidx, vals, dtype=np.float64, make_local=None, bounds=None, tile_cache=None, hyb=False, device_build=False, **plan_kw):
+    def __init__(self, rank, world, rows, cols, rowptr, colidx, vals, dtype=np.float64, make_local=None, bounds=None, tile_cache=None, hyb=False, device_build=False, value_map=False, **plan_kw):
         """``bounds`` given: ``rowptr / colidx / vals`` are THIS RANK'S row block only (row pointer rebased to 0, global
         column ids) and ``bounds`` the row partition everybody agreed on — a rank then never holds the whole matrix.
         ``tile_cache``: path of a Tile_matrix cache for this rank's block (read when present and of the right shape, written
         otherwise: api.matrix_load / matrix_save).  ``device_build``: the tiled matrix and the plan are built on the device from the CSR block
-        (``Plan.from_csr``: nothing but the CSR arrays crosses the bus; no host Tile_matrix, no tile cache, no HYB tiles)."""
+        (``Plan.from_csr``: nothing but the CSR arrays crosses the bus; no host Tile_matrix, no tile cache, no HYB tiles).  ``value_map`` (with ``device_build``): the local plan keeps a
+        value map, and ``update_values`` gives it new values of the same pattern."""
         from . import api
         self.rank, self.world, self.rows, self.cols = rank, world, rows, cols
         self.dtype = np.dtype(dtype)
+        if value_map and not device_build and make_local is None:
+            raise ValueError("value_map needs device_build=True (a plan built from a host Tile_matrix has no link back to CSR order)")
         if bounds is None:
             self.bounds = partition_rows(rowptr, rows, world)
             self.r0, self.r1 = int(self.bounds[rank]), int(self.bounds[rank + 1])
             rp, ci, v = shard_csr(rowptr, colidx, vals, self.r0, self.r1)
+            self.val_range = (int(rowptr[self.r0]), int(rowptr[self.r1]))   # this rank's block in the full value array
         else:
             self.bounds = np.asarray(bounds, dtype=np.int64)
             self.r0, self.r1 = int(self.bounds[rank]), int(self.bounds[rank + 1])
             rp, ci, v = rowptr, colidx, vals
             assert len(rp) == self.r1 - self.r0 + 1 and int(rp[0]) == 0
+            self.val_range = (0, int(rp[-1]))
         self.local_rows, self.local_nnz = self.r1 - self.r0, int(rp[-1])
         self.seconds = {}
         if make_local is not None:
@@ -88,7 +93,7 @@ class ShardedSpMV:
             t0 = time.perf_counter()
             self.tm, self.tile_cache = None, None
             self.tile_cache = "unused (device build)" if tile_cache is not None else None
-            self.local = api.Plan.from_csr(self.local_rows, cols, self.local_nnz, rp, ci, v, dtype=self.dtype, hyb=hyb, **plan_kw)
+            self.local = api.Plan.from_csr(self.local_rows, cols, self.local_nnz, rp, ci, v, dtype=self.dtype, hyb=hyb, value_map=value_map, **plan_kw)
             t1 = time.perf_counter()
             info = self.local.info()
             self.tiles = int(info["tiles"])
@@ -145,6 +150,22 @@ class ShardedSpMV:
             self.local.spmv(x.data_ptr(), yp, stream)
         else:
             self.local.spmv_n(x.data_ptr(), yp, stream, count)
+
+    def update_values(self, vals, stream=0):
+        """New values of the same pattern (plans created with ``value_map=True``): ``vals`` is the full CSR value array — or, when ``bounds`` was given, this rank's
+        block — in the order the rank was created from.  The local multiplier gets this rank's slice: a HIP ``Plan`` as a device array (a torch tensor on the GPU of the
+        plan's value type; asynchronous on ``stream``), an injected multiplier as the slice itself."""
+        lo, hi = self.val_range
+        block = vals[lo:hi]
+        from . import api
+        if not isinstance(self.local, api.Plan):
+            self.local.update_values(block)
+            return
+        if not getattr(block, "is_cuda", False) or block.element_size() != self.dtype.itemsize:
+            raise TypeError("update_values: a contiguous device tensor of %s values is needed" % self.dtype.name)
+        block = block.contiguous()
+        self._vals_held = block   # (kept alive until the asynchronous update has read it: the next call replaces it)
+        self.local.update_values(block.data_ptr(), stream)
 
     def combine(self, y_full, mode, force=False):
         """``force``: run the collective even in a 1-rank group (a no-op numerically) — lets a single-GPU box push the real y
