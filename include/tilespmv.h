@@ -126,6 +126,13 @@ void Tile_create(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA,
  * value slot of its streams the position of the source nonzero in the CSR arrays — so that tilespmv_plan_update_values (below) can rewrite every value the plan holds from a new value
  * array of the same pattern.  See tilespmv_plan_update_values for the contract. */
 #define TILESPMV_CREATE_VALUE_MAP 8u
+/* TILESPMV_CREATE_TRANSPOSE (opt-in; Tile_create_ex, Tile_create_device, tilespmv_plan_create_from_csr / _from_device_csr): build the tiled matrix or plan of A^T instead of A.
+ * rowA, colA, nnzA and the CSR arrays still describe A; the result is that of tilespmv_csr_transpose's output (below) — a colA x rowA matrix — and a plan of it computes
+ * y[0 .. colA) = A^T x with x of rowA elements.  tilerow_begin / tilerow_end count tile-rows of A^T (column blocks of A), and the refusals (-4) apply to the transposed shape.
+ * The transposition runs on the device for the device entry points (tilespmv_csr_transpose_device) and on the host for Tile_create_ex; either way the result is byte for byte
+ * what the unflagged entry point builds from the transposed CSR.  With TILESPMV_CREATE_VALUE_MAP as well, the plan's value map names positions of A's value array:
+ * tilespmv_plan_update_values(plan_of_AT, d_csrVal_of_A, stream) refreshes it from the same array that refreshes the plan of A.  Without the flag nothing changes. */
+#define TILESPMV_CREATE_TRANSPOSE 16u
 void Tile_create_ex(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA,
                     const MAT_PTR_TYPE *csrRowPtrA, const int *csrColIdxA,
                     const MAT_VAL_TYPE *csrValA, unsigned flags);
@@ -369,7 +376,8 @@ void tilespmv_plan_destroy(tilespmv_plan *plan);
  * matrix (the CSR-fallback candidate, which has no device path, is not among them).  Other return codes as above.
  * Peak device memory during the call: the CSR arrays + the tiled matrix + the sort's key buffers (about 40 bytes per nonzero in fp64) beside the plan.  With TILESPMV_CREATE_VALUE_MAP add
  * the value map (4 bytes per value slot of the plan — about 4.5 to 6 bytes per nonzero; it stays with the plan) and, for tilespmv_plan_create_from_device_csr, one more value array
- * (sizeof(MAT_VAL_TYPE) bytes per nonzero, freed before the call returns). */
+ * (sizeof(MAT_VAL_TYPE) bytes per nonzero, freed before the call returns).  With TILESPMV_CREATE_TRANSPOSE add the transposed CSR (about 4 + sizeof(MAT_VAL_TYPE) bytes per
+ * nonzero) and, while it is being made, the transposer's scratch (about 16 bytes per nonzero + the radix sort's temporary storage); all freed before the call returns. */
 int Tile_create_device(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA, const MAT_PTR_TYPE *csrRowPtrA,
                        const int *csrColIdxA, const MAT_VAL_TYPE *csrValA, unsigned flags);
 int tilespmv_plan_create_from_csr(tilespmv_plan **plan, int rowA, int colA, MAT_PTR_TYPE nnzA, const MAT_PTR_TYPE *csrRowPtrA,
@@ -543,6 +551,23 @@ int tilespmv_csr_permute(int n, const MAT_PTR_TYPE *csrRowPtr, const int *csrCol
                          MAT_PTR_TYPE *outRowPtr /* [n + 1] */, int *outColIdx, MAT_VAL_TYPE *outVal);
 long long tilespmv_csr_bandwidth(int n, const MAT_PTR_TYPE *csrRowPtr, const int *csrColIdx);   /* max |i - j| over the leading n x n block */
 int tilespmv_permute_vector(const MAT_VAL_TYPE *d_in, MAT_VAL_TYPE *d_out, const int *d_perm, long long n, int scatter, void *stream);   /* hipError_t value */
+
+/* ---- Transposed CSR (new).  The transpose of a rowA x colA CSR (rp, ci, v) is the colA x rowA CSR whose entries are A's in CSR order, STABLY sorted by column:
+ *   order = stable argsort of ci[rp[0] .. rp[rowA]);  rpT = the column counts, scanned (rpT[0] = 0);  ciT[k] = the row of entry order[k];  vT[k] = v[rp[0] + order[k]];
+ *   srcT[k] = rp[0] + order[k], the entry's position in the caller's arrays.
+ * Every row of A^T comes out in ascending column order whatever the order inside A's rows (what the dense-row / dense-col tiles need); duplicates keep their relative order.
+ * rp[0] != 0 is allowed (a row block of a larger CSR): ci and v are then read from position rp[0] on, and srcT names positions of the caller's arrays.  v / vT and srcT may be
+ * NULL (no values gathered, no positions written).  Output sizes: rpT[colA + 1], ciT / vT / srcT[rp[rowA] - rp[0]].
+ *   tilespmv_csr_transpose         host, threaded like the other host passes.  Returns 0, or -1 for a bad argument (NULL array, a decreasing row pointer, a column index
+ *                                  outside [0, colA)) — nothing meaningful is written then.
+ *   tilespmv_csr_transpose_device  the same on DEVICE arrays: a column histogram (int atomics), one exclusive scan into rpT, the row of every entry, ONE stable radix sort of
+ *                                  (column, position) pairs over ceil(log2(colA)) key bits, then the gathers.  Allocates its own scratch (about 16 bytes per nonzero plus the sort's
+ *                                  temporary storage) and synchronises `stream` before it returns: it cannot be captured into a hipGraph.  Returns a hipError_t value
+ *                                  (hipErrorInvalidValue for a bad argument or a column index outside [0, colA)). */
+int tilespmv_csr_transpose(int rowA, int colA, const MAT_PTR_TYPE *csrRowPtr, const int *csrColIdx, const MAT_VAL_TYPE *csrVal /* may be NULL */,
+                           MAT_PTR_TYPE *rowPtrT /* [colA + 1] */, int *colIdxT, MAT_VAL_TYPE *valT /* may be NULL */, int *srcT /* may be NULL */);
+int tilespmv_csr_transpose_device(int rowA, int colA, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal /* may be NULL */,
+                                  MAT_PTR_TYPE *d_rowPtrT, int *d_colIdxT, MAT_VAL_TYPE *d_valT /* may be NULL */, int *d_srcT /* may be NULL */, void *stream);
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

@@ -154,6 +154,10 @@ def load(dtype=np.float64):
     lib.tilespmv_csr_bandwidth.restype = C.c_longlong
     lib.tilespmv_permute_vector.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
     lib.tilespmv_permute_vector.restype = C.c_int
+    lib.tilespmv_csr_transpose.argtypes = [C.c_int, C.c_int, _I, _I, VP, _I, _I, VP, _I]
+    lib.tilespmv_csr_transpose.restype = C.c_int
+    lib.tilespmv_csr_transpose_device.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_csr_transpose_device.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -176,4 +180,4 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_plan_time_reference_style", "tilespmv_plan_reserve_spmm", "tilespmv_plan_options_layout", "tilespmv_plan_layout_stages",
                     "Tile_create_device", "tilespmv_plan_create_from_csr", "tilespmv_plan_stream_digests", "tilespmv_plan_create_from_device_csr",
                     "tilespmv_reorder_rcm", "tilespmv_csr_permute", "tilespmv_csr_bandwidth", "tilespmv_permute_vector",
-                    "tilespmv_plan_update_values"]
+                    "tilespmv_plan_update_values", "tilespmv_csr_transpose", "tilespmv_csr_transpose_device"]

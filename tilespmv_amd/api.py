@@ -19,6 +19,7 @@ COO_AUTO, COO_IN_TILE, COO_FALLBACK = 0, 1, 2
 DENSE_AUTO, DENSE_MFMA, DENSE_VALU = 0, 1, 2
 KERNEL_AUTO, KERNEL_DIRECT, KERNEL_STREAM = 0, 1, 2
 CREATE_HYB, CREATE_QUIET, CREATE_CDNA4, CREATE_VALUE_MAP = 1, 2, 4, 8
+CREATE_TRANSPOSE = 16   # the tiled matrix / plan of A^T, built from A's CSR (include/tilespmv.h)
 ERR_NO_VALUE_MAP = -4   # tilespmv_plan_update_values on a plan without a value map
 
 
@@ -40,32 +41,77 @@ def _csr(lib, rowptr, colidx, vals):
             np.ascontiguousarray(vals, dtype=lib._dtype))
 
 
-def Tile_create(rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, hyb=False, quiet=True, cdna4=False):
+def Tile_create(rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, hyb=False, quiet=True, cdna4=False, transpose=False):
+    """``transpose=True`` (TILESPMV_CREATE_TRANSPOSE): the tiled matrix of A^T (colA x rowA), transposed on the host; the arguments still describe A."""
     dtype = np.dtype(dtype or np.asarray(csrValA).dtype)
     lib = _lib.load(dtype)
     rp, ci, v = _csr(lib, csrRowPtrA, csrColIdxA, csrValA)
+    if transpose:
+        _check_csr(rowA, colA, rp, ci)
     tm = lib._TM()
-    flags = (CREATE_HYB if hyb else 0) | (CREATE_QUIET if quiet else 0) | (CREATE_CDNA4 if cdna4 else 0)
+    flags = (CREATE_HYB if hyb else 0) | (CREATE_QUIET if quiet else 0) | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_TRANSPOSE if transpose else 0)
     lib.Tile_create_ex(C.byref(tm), rowA, colA, nnzA, _p(rp, C.c_int), _p(ci, C.c_int), _p(v, lib._vt), flags)
     tm._keep = (rp, ci, v)
     tm._lib = lib
     return tm
 
 
-def Tile_create_device(rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, quiet=True, cdna4=False, hyb=False):
+def Tile_create_device(rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, quiet=True, cdna4=False, hyb=False, transpose=False):
     """``Tile_create`` computed on the GPU (hip_tile_create.hip): the CSR arrays go up, the tiled matrix comes back, byte for byte what ``Tile_create`` builds
-    (``hyb=True``: with the reference's dormant HYB rule switched on, as ``Tile_create(hyb=True)``).  No CPU fallback: raises when no device is visible (rc -1)."""
+    (``hyb=True``: with the reference's dormant HYB rule switched on, as ``Tile_create(hyb=True)``).  No CPU fallback: raises when no device is visible (rc -1).
+    ``transpose=True``: the tiled matrix of A^T, transposed on the device — byte for byte ``Tile_create(transpose=True)``."""
     dtype = np.dtype(dtype or np.asarray(csrValA).dtype)
     lib = _lib.load(dtype)
     rp, ci, v = _csr(lib, csrRowPtrA, csrColIdxA, csrValA)
     tm = lib._TM()
-    flags = (CREATE_QUIET if quiet else 0) | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_HYB if hyb else 0)
+    flags = (CREATE_QUIET if quiet else 0) | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_HYB if hyb else 0) | (CREATE_TRANSPOSE if transpose else 0)
     rc = lib.Tile_create_device(C.byref(tm), rowA, colA, nnzA, _p(rp, C.c_int), _p(ci, C.c_int), _p(v, lib._vt), flags)
     if rc != 0:
         raise RuntimeError("Tile_create_device failed (%d): no usable HIP device / extension, or offsets beyond int32" % rc)
     tm._keep = (rp, ci, v)
     tm._lib = lib
     return tm
+
+
+def _check_csr(rows, cols, rp, ci):
+    if rows < 0 or cols < 0 or len(rp) < rows + 1:
+        raise ValueError("not a %d x %d CSR: the row pointer needs %d entries" % (rows, cols, rows + 1))
+    lo, hi = int(rp[0]), int(rp[rows])
+    if lo < 0 or hi < lo or len(ci) < hi or (rows and np.any(np.diff(rp[:rows + 1]) < 0)):
+        raise ValueError("not a %d x %d CSR: the row pointer decreases or points past the column indices" % (rows, cols))
+    if hi > lo and (int(ci[lo:hi].min()) < 0 or int(ci[lo:hi].max()) >= cols):
+        raise ValueError("not a %d x %d CSR: a column index outside [0, %d)" % (rows, cols, cols))
+
+
+def csr_transpose(rows, cols, rp, ci, v=None, dtype=None):
+    """A^T of a ``rows x cols`` CSR (``tilespmv_csr_transpose``, host, threaded): ``(rpT, ciT, vT, srcT)``, the entries of A in CSR order stably sorted by column —
+    ``srcT[k]`` is the position of entry k of A^T in the caller's arrays (``rp[0] != 0`` allowed: a row block of a larger CSR).  ``vT`` is ``None`` when ``v`` is."""
+    dtype = np.dtype(dtype if dtype is not None else (np.asarray(v).dtype if v is not None else np.float64))
+    lib = _lib.load(dtype)
+    rp = np.ascontiguousarray(rp, dtype=np.int32)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    _check_csr(rows, cols, rp, ci)
+    nnz = int(rp[rows]) - int(rp[0])
+    vv = None if v is None else np.ascontiguousarray(v, dtype=lib._dtype)
+    if vv is not None and len(vv) < int(rp[rows]):
+        raise ValueError("csr_transpose: %d values for %d positions" % (len(vv), int(rp[rows])))
+    rpT, ciT, srcT = np.zeros(cols + 1, np.int32), np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1), np.int32)
+    vT = None if vv is None else np.zeros(max(nnz, 1), lib._dtype)
+    rc = lib.tilespmv_csr_transpose(rows, cols, _p(rp, C.c_int), _p(ci, C.c_int), None if vv is None else _p(vv, lib._vt), _p(rpT, C.c_int), _p(ciT, C.c_int),
+                                    None if vT is None else _p(vT, lib._vt), _p(srcT, C.c_int))
+    if rc != 0:
+        raise ValueError("tilespmv_csr_transpose failed (%d): not a valid CSR" % rc)
+    return rpT, ciT[:nnz], None if vT is None else vT[:nnz], srcT[:nnz]
+
+
+def csr_transpose_device(rows, cols, d_rp, d_ci, d_v, d_rpT, d_ciT, d_vT=None, d_srcT=None, dtype=np.float64, stream=0):
+    """``tilespmv_csr_transpose_device``: the same on DEVICE arrays (addresses, as ``Plan.from_device_csr`` takes them; ``d_rpT`` has cols + 1 int32 elements, ``d_ciT`` /
+    ``d_vT`` / ``d_srcT`` one per nonzero; ``d_v`` / ``d_vT`` / ``d_srcT`` may be 0 / None).  Allocates scratch and synchronises ``stream``: not for graph capture."""
+    lib = _lib.load(dtype)
+    rc = lib.tilespmv_csr_transpose_device(rows, cols, C.c_void_p(d_rp), C.c_void_p(d_ci), C.c_void_p(d_v or None), C.c_void_p(d_rpT), C.c_void_p(d_ciT),
+                                           C.c_void_p(d_vT or None), C.c_void_p(d_srcT or None), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("tilespmv_csr_transpose_device failed (hipError %d): bad argument, a column index outside [0, cols), or no usable device" % rc)
 
 
 def Tile_destroy(tm):
@@ -249,6 +295,7 @@ class Plan:
         ``_lib.KNOB_NAMES``).  An unset knob falls back to its TILESPMV_* environment variable, then to the built-in default."""
         self.lib = tm._lib
         self.rowA, self.colA, self.nnzA = rowA, colA, nnzA
+        self.shape = (rowA, colA)
         opts = _lib.PlanOptions(coo_mode, dense_mode, kernel, tilerow_begin, tilerow_end, autotune, **knobs)
         h = C.c_void_p()
         rc = self.lib.tilespmv_plan_create(C.byref(h), C.byref(tm), rowA, colA, nnzA, C.byref(opts))
@@ -258,19 +305,24 @@ class Plan:
 
     @classmethod
     def from_csr(cls, rowA, colA, nnzA, csrRowPtrA, csrColIdxA, csrValA, dtype=None, cdna4=False, hyb=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, autotune=False,
-                 value_map=False, **knobs):
+                 value_map=False, transpose=False, **knobs):
         """``tilespmv_plan_create_from_csr``: the tiled matrix and the plan's streams are built on the device; only the CSR arrays cross the bus.
         Raises ``NotImplementedError`` for the options that have no device path (rc -4: first-generation kernel, CSR fallback, csr_split=0).  ``autotune=True``: every candidate is built from the one device-resident tiled matrix.
-        ``value_map=True`` (TILESPMV_CREATE_VALUE_MAP): the plan keeps a value map, so that ``update_values`` can give it new values of the same pattern."""
+        ``value_map=True`` (TILESPMV_CREATE_VALUE_MAP): the plan keeps a value map, so that ``update_values`` can give it new values of the same pattern.
+        ``transpose=True`` (TILESPMV_CREATE_TRANSPOSE): the plan of A^T, transposed on the device — ``spmv`` computes y[0 .. colA) = A^T x with x of rowA elements
+        (``shape`` = (colA, rowA)); tilerow_begin / tilerow_end count tile-rows of A^T; with ``value_map`` the map indexes A's value array."""
         dtype = np.dtype(dtype or np.asarray(csrValA).dtype)
         lib = _lib.load(dtype)
         rp, ci, v = _csr(lib, csrRowPtrA, csrColIdxA, csrValA)
+        if transpose:
+            _check_csr(rowA, colA, rp, ci)
         self = cls.__new__(cls)
         self.lib = lib
         self.rowA, self.colA, self.nnzA = rowA, colA, nnzA
+        self.shape = (colA, rowA) if transpose else (rowA, colA)
         opts = _lib.PlanOptions(coo_mode, dense_mode, kernel, tilerow_begin, tilerow_end, autotune, **knobs)
         h = C.c_void_p()
-        rc = lib.tilespmv_plan_create_from_csr(C.byref(h), rowA, colA, nnzA, _p(rp, C.c_int), _p(ci, C.c_int), _p(v, lib._vt), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_HYB if hyb else 0) | (CREATE_VALUE_MAP if value_map else 0), C.byref(opts))
+        rc = lib.tilespmv_plan_create_from_csr(C.byref(h), rowA, colA, nnzA, _p(rp, C.c_int), _p(ci, C.c_int), _p(v, lib._vt), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_HYB if hyb else 0) | (CREATE_VALUE_MAP if value_map else 0) | (CREATE_TRANSPOSE if transpose else 0), C.byref(opts))
         if rc == -4:
             raise NotImplementedError("tilespmv_plan_create_from_csr: these options have no device path")
         if rc != 0 or not h:
@@ -279,17 +331,19 @@ class Plan:
         return self
 
     @classmethod
-    def from_device_csr(cls, rowA, colA, nnzA, d_rowptr, d_colidx, d_vals, dtype, cdna4=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, value_map=False, **knobs):
+    def from_device_csr(cls, rowA, colA, nnzA, d_rowptr, d_colidx, d_vals, dtype, cdna4=False, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, value_map=False, transpose=False, **knobs):
         """``tilespmv_plan_create_from_device_csr``: like ``from_csr`` with the CSR arrays already in device memory — ``d_rowptr`` / ``d_colidx`` (int32) and ``d_vals`` are device
-        ADDRESSES (e.g. ``tensor.data_ptr()`` of the crow / col / values tensors of a torch CSR tensor cast to int32); borrowed for the call."""
+        ADDRESSES (e.g. ``tensor.data_ptr()`` of the crow / col / values tensors of a torch CSR tensor cast to int32); borrowed for the call.  ``transpose=True``: the plan of A^T
+        (as in ``from_csr``)."""
         dtype = np.dtype(dtype)
         lib = _lib.load(dtype)
         self = cls.__new__(cls)
         self.lib = lib
         self.rowA, self.colA, self.nnzA = rowA, colA, nnzA
+        self.shape = (colA, rowA) if transpose else (rowA, colA)
         opts = _lib.PlanOptions(coo_mode, dense_mode, kernel, tilerow_begin, tilerow_end, False, **knobs)
         h = C.c_void_p()
-        rc = lib.tilespmv_plan_create_from_device_csr(C.byref(h), rowA, colA, nnzA, C.c_void_p(d_rowptr), C.c_void_p(d_colidx), C.c_void_p(d_vals), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_VALUE_MAP if value_map else 0), C.byref(opts))
+        rc = lib.tilespmv_plan_create_from_device_csr(C.byref(h), rowA, colA, nnzA, C.c_void_p(d_rowptr), C.c_void_p(d_colidx), C.c_void_p(d_vals), CREATE_QUIET | (CREATE_CDNA4 if cdna4 else 0) | (CREATE_VALUE_MAP if value_map else 0) | (CREATE_TRANSPOSE if transpose else 0), C.byref(opts))
         if rc == -4:
             raise NotImplementedError("tilespmv_plan_create_from_device_csr: these options have no device path")
         if rc != 0 or not h:

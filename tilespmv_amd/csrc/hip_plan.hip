@@ -857,6 +857,9 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
 {
     *out = nullptr;
     const Knobs K = resolve_knobs(opts);
+    // TILESPMV_CREATE_TRANSPOSE: the plan of A^T (colA x rowA); the arguments describe A, so the shape is swapped first and every rule below sees the transposed one
+    const bool transpose = (create_flags & TILESPMV_CREATE_TRANSPOSE) != 0;
+    if (transpose) std::swap(rowA, colA);
     const int tilen = (colA + BS - 1) / BS;
     // what has no device path (include/tilespmv.h): the caller builds those plans from a host Tile_matrix
     if (K.dry || K.kernel == TILESPMV_KERNEL_DIRECT || tilen > (1 << UNIT_FLAG_SHIFT) || K.coo_mode == TILESPMV_COO_FALLBACK || K.csr_split == 0)
@@ -864,7 +867,17 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
     const double t0 = now_us();
     DevTile *D = nullptr;
     const bool value_map = (create_flags & TILESPMV_CREATE_VALUE_MAP) != 0;   // built from stand-in values, the caller's written in afterwards (hip_value_map.hip)
-    int rc = devtile_create(&D, rowA, colA, rowptr, colidx, val, create_flags, false, csr_on_device, value_map);
+    int rc = 0;
+    DevCsrT Tr;   // (transposed builds: A^T on the device, hip_transpose.hip; borrowed by the DevTile, so it outlives it)
+    if (transpose) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); fprintf(stderr, "tilespmv: no HIP device visible — the device plan builder has no CPU fallback\n"); return -1; }
+        // value-map builds gather no values: the stand-ins come from the positions, and the caller's values of A (kept on the device for a host CSR) are written in at the end
+        rc = devcsr_transpose(&Tr, colA, rowA, rowptr, colidx, val, csr_on_device, !value_map, value_map, value_map && !csr_on_device);
+        if (rc == 0) rc = devtile_create(&D, rowA, colA, Tr.rp, Tr.ci, Tr.v, create_flags, false, true, value_map, Tr.src);
+        if (rc == 0 && value_map) { (void)hipFree(Tr.src); Tr.src = nullptr; }   // (the stand-ins are written)
+    } else
+        rc = devtile_create(&D, rowA, colA, rowptr, colidx, val, create_flags, false, csr_on_device, value_map);
     if (rc != 0) return rc;
     const double t1 = now_us();
     // the tile LIST on the host (what CHOOSE / CUT / the stride detection read); everything else of the tiled matrix stays where it is
@@ -894,13 +907,17 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
         // the plan's placement is final: the map is allocated now, outside the arena, and never moves.  The caller's values: their device array, or (host CSR) the DevTile's
         // value array, which held the stand-ins, refilled from the host
         const val_t *d_src = val;
-        if (!csr_on_device) {
+        long long limit = D->val_base + D->nnz;
+        if (transpose) {   // the map names positions of A's value array (the stand-ins were vmap_encode(srcT)): the caller's device array, or A's values kept on the device
+            limit = Tr.base + Tr.nnz;
+            if (!csr_on_device) d_src = Tr.valA - Tr.base;
+        } else if (!csr_on_device) {
             d_src = D->val - D->val_base;   // (indexed like the caller's array: the map holds positions from the row pointer's first entry on)
             if (D->nnz > 0 && hipMemcpy(const_cast<val_t *>(D->val), val + D->val_base, (size_t)D->nnz * sizeof(val_t), hipMemcpyHostToDevice) != hipSuccess) {
                 fprintf(stderr, "tilespmv: value map: values to the device failed\n"); (void)hipGetLastError(); rc = -3;
             }
         }
-        if (rc == 0) rc = value_map_attach(*out, D->val_base + D->nnz, d_src);
+        if (rc == 0) rc = value_map_attach(*out, limit, d_src);
         if (rc != 0) { tilespmv_plan_destroy(*out); *out = nullptr; }
     }
     devtile_destroy(D);

@@ -53,10 +53,32 @@ __host__ __device__ inline long long vmap_decode(val_t v) { vmap_bits_t b; __bui
 // csr_on_device: the three CSR arrays are DEVICE pointers already (row pointer based at 0; borrowed, not freed): no upload at all
 // stand_in_values: DevTile::val holds vmap_encode(position in the caller's value array) instead of the caller's values (a device array of its own, whichever side the CSR came from;
 // nothing of the caller's values is read)
+// stand_in_pos (device, with stand_in_values only; nullptr: the nonzero's own position): nonzero j's stand-in is vmap_encode(stand_in_pos[j]) — a transposed build names positions of A
 int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device = false,
-                   bool stand_in_values = false);
+                   bool stand_in_values = false, const int *stand_in_pos = nullptr);
 void devtile_destroy(DevTile *D);
 // every member array into freshly malloc'd host arrays (Tile_destroy frees them)
 int devtile_download(const DevTile *D, Tile_matrix *host);
+
+// hip_transpose.hip: A^T of a CSR on the device (the definition of tilespmv_csr_transpose, include/tilespmv.h).  rp: the row pointer (device; entries from `base` on, base + nnz at
+// rp[rowA]); ci0 / v0: the column indices / values of the block (the caller's position `base` first; v0 may be nullptr).  rpT[colA + 1], ciT / vT / srcT[nnz]; vT and srcT may
+// be nullptr.  Allocates its scratch, synchronises `st`.  hipErrorInvalidValue: a column index outside [0, colA) or a decreasing row pointer
+hipError_t csr_transpose_dev(int rowA, int colA, const int *rp, long long base, long long nnz, const int *ci0, const val_t *v0, int *rpT, int *ciT, val_t *vT, int *srcT,
+                             hipStream_t st);
+// A^T of the caller's CSR (host arrays, uploaded first, or device arrays) in device arrays of its own (TILESPMV_CREATE_TRANSPOSE): a colA x rowA CSR based at 0, ready for
+// devtile_create(csr_on_device = true).  want_values: v gathered; want_src: src = position of every entry in A's arrays (the value map's stand-ins); keep_values_of_a (host CSR):
+// A's values stay on the device in valA (valA[j] = the caller's value at position base + j)
+struct DevCsrT {
+    int rows = 0, cols = 0;
+    long long nnz = 0, base = 0;
+    int *rp = nullptr, *ci = nullptr, *src = nullptr;
+    val_t *v = nullptr, *valA = nullptr;
+    DevCsrT() = default;
+    DevCsrT(const DevCsrT &) = delete;
+    DevCsrT &operator=(const DevCsrT &) = delete;
+    ~DevCsrT();
+};
+// 0, or -3 (HIP error, out of device memory, or not a valid CSR: message on stderr)
+int devcsr_transpose(DevCsrT *T, int rowA, int colA, const MAT_PTR_TYPE *rp, const int *ci, const val_t *v, bool csr_on_device, bool want_values, bool want_src, bool keep_values_of_a);
 
 }  // namespace tilespmv

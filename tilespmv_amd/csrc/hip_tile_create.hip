@@ -289,6 +289,11 @@ __global__ void k_tc_stand_in(long long n, long long base, val_t *__restrict__ v
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = vmap_encode(base + i);
 }
+__global__ void k_tc_stand_in_at(long long n, const int *__restrict__ pos, val_t *__restrict__ v)   // (the stand-ins of a transposed build: positions of A)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = vmap_encode(pos[i]);
+}
 __global__ void k_tc_iota(int n, int *__restrict__ a)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -351,7 +356,8 @@ inline void dfree(DevTile *D, const void *p)   // (an array carved from a pool i
 }
 inline unsigned blocks_for(long long n, int per) { return (unsigned)std::max<long long>(1, (n + per - 1) / per); }
 
-int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device, bool stand_in)
+int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device, bool stand_in,
+                const int *stand_in_pos)
 {
     const bool verbose = getenv("TILESPMV_CREATE_VERBOSE") != nullptr, cdna4 = flags & TILESPMV_CREATE_CDNA4, allow_hyb = flags & TILESPMV_CREATE_HYB;
     pool_end();   // (no pool left over from a build that failed on this thread)
@@ -405,7 +411,8 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
         }
     }
     if (stand_in && nnz > 0) {   // the stand-in values instead of the caller's (hip_tile_create.h): nothing of theirs is read
-        hipLaunchKernelGGL(k_tc_stand_in, dim3(blocks_for(nnz, 256)), dim3(256), 0, 0, nnz, base, d_val);
+        if (stand_in_pos) hipLaunchKernelGGL(k_tc_stand_in_at, dim3(blocks_for(nnz, 256)), dim3(256), 0, 0, nnz, stand_in_pos, d_val);
+        else hipLaunchKernelGGL(k_tc_stand_in, dim3(blocks_for(nnz, 256)), dim3(256), 0, 0, nnz, base, d_val);
         TC_TRY(hipGetLastError());
     }
     D->rowptr = d_rowptr; D->colidx = d_colidx; D->val = d_val;
@@ -621,13 +628,14 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
 
 }  // namespace
 
-int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device, bool stand_in_values)
+int devtile_create(DevTile **out, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, const int *h_colidx, const val_t *h_val, unsigned flags, bool want_deferred, bool csr_on_device, bool stand_in_values,
+                   const int *stand_in_pos)
 {
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); fprintf(stderr, "tilespmv: no HIP device visible — the device Tile_create has no CPU fallback (use Tile_create)\n"); return -1; }
     DevTile *D = new DevTile();
-    const int rc = create_impl(D, rowA, colA, h_rowptr, h_colidx, h_val, flags, want_deferred, csr_on_device, stand_in_values);
+    const int rc = create_impl(D, rowA, colA, h_rowptr, h_colidx, h_val, flags, want_deferred, csr_on_device, stand_in_values, stand_in_pos);
     pool_end();
     if (rc != 0) { devtile_destroy(D); return rc; }
     *out = D;
@@ -719,7 +727,15 @@ extern "C" int Tile_create_device(Tile_matrix *matrix, int rowA, int colA, MAT_P
 {
     (void)nnzA;   // like Tile_create, the row pointer decides how many nonzeros are used
     tilespmv::DevTile *D = nullptr;
-    int rc = tilespmv::devtile_create(&D, rowA, colA, csrRowPtrA, csrColIdxA, csrValA, flags, true);
+    tilespmv::DevCsrT Tr;   // (TILESPMV_CREATE_TRANSPOSE: A^T transposed on the device, hip_transpose.hip; the tiled matrix is built from those device arrays)
+    int rc;
+    if (flags & TILESPMV_CREATE_TRANSPOSE) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); fprintf(stderr, "tilespmv: no HIP device visible — the device Tile_create has no CPU fallback (use Tile_create)\n"); return -1; }
+        rc = tilespmv::devcsr_transpose(&Tr, rowA, colA, csrRowPtrA, csrColIdxA, csrValA, false, true, false, false);
+        if (rc == 0) rc = tilespmv::devtile_create(&D, colA, rowA, Tr.rp, Tr.ci, Tr.v, flags, true, true);
+    } else
+        rc = tilespmv::devtile_create(&D, rowA, colA, csrRowPtrA, csrColIdxA, csrValA, flags, true);
     if (rc != 0) return rc;
     rc = tilespmv::devtile_download(D, matrix);
     tilespmv::devtile_destroy(D);

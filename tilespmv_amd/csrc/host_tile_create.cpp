@@ -356,6 +356,18 @@ void Tile_create_ex(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA, 
                     const int *csrColIdxA, const MAT_VAL_TYPE *csrValA, unsigned flags)
 {
     (void)nnzA;  // like the reference, the row pointer decides how many nonzeros are used
+    if (flags & TILESPMV_CREATE_TRANSPOSE) {   // the Tile_matrix of A^T: the host transposer (host_transpose.cpp), then the same builder
+        const long long nnz = rowA >= 0 && csrRowPtrA ? (long long)csrRowPtrA[rowA] - csrRowPtrA[0] : 0;
+        std::vector<MAT_PTR_TYPE> rpT((size_t)std::max(colA, 0) + 1);
+        std::vector<int> ciT((size_t)std::max<long long>(nnz, 1));
+        std::vector<MAT_VAL_TYPE> vT((size_t)std::max<long long>(nnz, 1));
+        if (tilespmv::csr_transpose_host(rowA, colA, csrRowPtrA, csrColIdxA, csrValA, rpT.data(), ciT.data(), vT.data(), nullptr) != 0) {
+            fprintf(stderr, "tilespmv: Tile_create_ex(TILESPMV_CREATE_TRANSPOSE): not a valid %d x %d CSR\n", rowA, colA);
+            exit(2);
+        }
+        tilespmv::tile_create_impl(matrix, colA, rowA, rpT.data(), ciT.data(), vT.data(), flags & ~TILESPMV_CREATE_TRANSPOSE);
+        return;
+    }
     tilespmv::tile_create_impl(matrix, rowA, colA, csrRowPtrA, csrColIdxA, csrValA, flags);
 }
 

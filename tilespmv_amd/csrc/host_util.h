@@ -175,4 +175,7 @@ void pivot_sort(int *key, val_t *val, int n);
 // Row-block schedule of the reference (src/tilespmv_cpu.h:68-118); arrays are malloc'd.
 int build_rowblock_schedule(const Tile_matrix *T, unsigned int **rowidx, int **colstart, int **colstop);
 
+// A^T of a CSR on the host (host_transpose.cpp; the definition is tilespmv_csr_transpose's, include/tilespmv.h).  0, or -1 for a bad argument
+int csr_transpose_host(int rowA, int colA, const MAT_PTR_TYPE *rp, const int *ci, const val_t *v, MAT_PTR_TYPE *rpT, int *ciT, val_t *vT, int *srcT);
+
 }  // namespace tilespmv

@@ -1,0 +1,190 @@
+"""A sparse operator with both products, ``A x`` and ``A^T x``, from one CSR.
+
+    op = SparseOperator(rows, cols, rp, ci, v)                     # host CSR (numpy); or CUDA tensors / from_device_csr(...) for a device CSR
+    y = op.matvec(x)                                                 # A x      (plan of A)
+    z = op.rmatvec(u)                                                # A^T u    (plan of A^T, built on the device from A's CSR: TILESPMV_CREATE_TRANSPOSE)
+    op = SparseOperator(..., value_map=True); op.update_values(v2)   # new values of the same pattern: both plans refreshed from A's one value array
+    x, info = cgls(op, b)                                            # least squares  min ||A x - b||
+
+The plan of A^T is a plan like any other (tuned kernels, form choice, ordered sums); there is no scatter form of A^T x.
+"""
+import numpy as np
+
+from . import api
+
+
+def _is_tensor(a):
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(a, torch.Tensor)
+
+
+def _stream(stream):
+    if stream is not None:
+        return stream
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+class SparseOperator:
+    """The plans of A (``rows x cols``) and of A^T from one CSR.
+
+    ``rp`` / ``ci`` / ``v``: numpy arrays (host CSR: ``Plan.from_csr``) or CUDA tensors (device CSR: ``Plan.from_device_csr``; the row pointer starts at 0).  ``value_map=True``
+    gives both plans a value map that indexes A's value array, so that ``update_values`` refreshes both from it.  Every other keyword goes to both plan creations
+    (``cdna4``, ``hyb`` (host CSR only), ``coo_mode``, knobs such as ``placement_tries=1``)."""
+
+    def __init__(self, rows, cols, rp, ci, v, dtype=None, value_map=False, **opts):
+        self.shape = (rows, cols)
+        self.value_map = value_map
+        if _is_tensor(v):
+            import torch
+            dtype = np.dtype(dtype or str(v.dtype).replace("torch.", ""))
+            rp32 = rp.to(device=v.device, dtype=torch.int32).contiguous()
+            ci32 = ci.to(device=v.device, dtype=torch.int32).contiguous()
+            vc = v.contiguous()
+            nnz = int(rp32[rows].item())
+            self._init_device(rows, cols, nnz, rp32.data_ptr(), ci32.data_ptr(), vc.data_ptr(), dtype, value_map, opts)
+        else:
+            dtype = np.dtype(dtype or np.asarray(v).dtype)
+            rp = np.ascontiguousarray(rp, dtype=np.int32)
+            nnz = int(rp[rows]) - int(rp[0])
+            self.dtype, self.nnz = dtype, nnz
+            self.A = api.Plan.from_csr(rows, cols, nnz, rp, ci, v, dtype=dtype, value_map=value_map, **opts)
+            try:
+                self.AT = api.Plan.from_csr(rows, cols, nnz, rp, ci, v, dtype=dtype, value_map=value_map, transpose=True, **opts)
+            except Exception:
+                self.A.close()
+                raise
+
+    @classmethod
+    def from_device_csr(cls, rows, cols, nnz, d_rp, d_ci, d_v, dtype, value_map=False, **opts):
+        """Device ADDRESSES of an int32 row pointer (starting at 0), int32 column indices and values, as ``Plan.from_device_csr`` takes them; borrowed for the call."""
+        self = cls.__new__(cls)
+        self.shape = (rows, cols)
+        self.value_map = value_map
+        self._init_device(rows, cols, nnz, d_rp, d_ci, d_v, np.dtype(dtype), value_map, opts)
+        return self
+
+    def _init_device(self, rows, cols, nnz, d_rp, d_ci, d_v, dtype, value_map, opts):
+        self.dtype, self.nnz = dtype, nnz
+        self.A = api.Plan.from_device_csr(rows, cols, nnz, d_rp, d_ci, d_v, dtype, value_map=value_map, **opts)
+        try:
+            self.AT = api.Plan.from_device_csr(rows, cols, nnz, d_rp, d_ci, d_v, dtype, value_map=value_map, transpose=True, **opts)
+        except Exception:
+            self.A.close()
+            raise
+
+    # ---- products
+    def _apply(self, plan, x, y, stream):
+        m, n = plan.shape
+        if not _is_tensor(x):   # device addresses: the caller owns both vectors
+            if y is None:
+                raise ValueError("with a device address for x, y must be a device address too")
+            plan.spmv(x, y, stream or 0)
+            return y
+        import torch
+        if x.dim() != 1 or x.numel() != n or not x.is_contiguous():
+            raise ValueError("x must be a contiguous vector of %d elements" % n)
+        if y is None:
+            y = torch.empty(m + 16, dtype=x.dtype, device=x.device)[:m]   # (room behind the vector, as every y of this project has)
+        elif y.numel() < m or not y.is_contiguous():
+            raise ValueError("y must be a contiguous vector of at least %d elements" % m)
+        plan.spmv(x.data_ptr(), y.data_ptr(), _stream(stream))
+        return y
+
+    def matvec(self, x, y=None, stream=None):
+        """y = A x (x: cols, y: rows).  Torch CUDA vectors (y allocated when None, returned) or device addresses; asynchronous on ``stream`` (default: torch's current)."""
+        return self._apply(self.A, x, y, stream)
+
+    def rmatvec(self, u, v=None, stream=None):
+        """v = A^T u (u: rows, v: cols), as ``matvec``."""
+        return self._apply(self.AT, u, v, stream)
+
+    def _apply_mm(self, plan, X, Y, nvec, stream):
+        m, n = plan.shape
+        if not _is_tensor(X):
+            if Y is None or nvec is None:
+                raise ValueError("with a device address for X, Y and nvec must be given")
+            plan.spmm(X, Y, nvec, stream or 0)
+            return Y
+        import torch
+        if X.dim() != 2 or X.shape[0] != n or not X.is_contiguous():
+            raise ValueError("X must be a contiguous (%d, nvec) matrix" % n)
+        nvec = X.shape[1]
+        if Y is None:
+            Y = torch.empty((m + 16, nvec), dtype=X.dtype, device=X.device)[:m]
+        elif Y.dim() != 2 or Y.shape[0] < m or Y.shape[1] != nvec or not Y.is_contiguous():
+            raise ValueError("Y must be a contiguous (%d, %d) matrix" % (m, nvec))
+        plan.spmm(X.data_ptr(), Y.data_ptr(), nvec, _stream(stream))
+        return Y
+
+    def spmm(self, X, Y=None, nvec=None, stream=None):
+        """Y = A X, X row-major (cols, nvec), nvec in {1, 2, 4, 8}."""
+        return self._apply_mm(self.A, X, Y, nvec, stream)
+
+    def rspmm(self, U, V=None, nvec=None, stream=None):
+        """V = A^T U, U row-major (rows, nvec)."""
+        return self._apply_mm(self.AT, U, V, nvec, stream)
+
+    def update_values(self, d_vals, stream=None):
+        """New values of A, same pattern (``value_map=True``): both plans rewritten from A's one value array (a CUDA tensor, or its device address), asynchronously and in order
+        on one stream — capturable into a graph."""
+        if not self.value_map:
+            raise RuntimeError("SparseOperator.update_values: create the operator with value_map=True")
+        if _is_tensor(d_vals):
+            if d_vals.numel() < self.nnz or not d_vals.is_contiguous():
+                raise ValueError("update_values: a contiguous array of at least %d values" % self.nnz)
+            st = _stream(stream)
+            d_vals = d_vals.data_ptr()
+        else:
+            st = stream or 0
+        self.A.update_values(d_vals, st)
+        self.AT.update_values(d_vals, st)
+
+    def close(self):
+        for p in (getattr(self, "A", None), getattr(self, "AT", None)):
+            if p is not None:
+                p.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def cgls(op, b, x0=None, tol=1e-12, maxiter=None, check_every=1):
+    """Least squares ``min ||A x - b||_2`` by CGLS (conjugate gradients on the normal equations, never forming A^T A): one ``A p`` and one ``A^T r`` per iteration.
+    ``b``: a torch CUDA vector of ``rows`` elements.  Stops when ``||A^T r|| <= tol * ||A^T b||`` (checked every ``check_every`` iterations: each check is one host sync) or after
+    ``maxiter`` iterations (default ``2 * cols``).  Returns ``(x, info)`` with ``info = {"iterations", "normal_residual", "residual", "converged"}``."""
+    import torch
+    rows, cols = op.shape
+    if b.numel() != rows:
+        raise ValueError("b must have %d elements" % rows)
+    maxiter = 2 * cols if maxiter is None else maxiter
+    x = torch.zeros(cols, dtype=b.dtype, device=b.device) if x0 is None else x0.clone()
+    r = b.clone()
+    if x0 is not None:
+        r -= op.matvec(x)
+    s = op.rmatvec(r)
+    norm_atb = float(torch.linalg.vector_norm(op.rmatvec(b)))
+    p = s.clone()
+    gamma = torch.dot(s, s)
+    q = torch.empty(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+    it, converged = 0, float(gamma.sqrt()) <= tol * norm_atb
+    while not converged and it < maxiter:
+        op.matvec(p, q)
+        alpha = gamma / torch.dot(q, q)
+        x.add_(alpha * p)
+        r.sub_(alpha * q)
+        op.rmatvec(r, s)
+        gamma_new = torch.dot(s, s)
+        p.mul_(gamma_new / gamma).add_(s)
+        gamma = gamma_new
+        it += 1
+        if it % check_every == 0 or it == maxiter:
+            converged = float(gamma.sqrt()) <= tol * norm_atb
+    info = {"iterations": it, "normal_residual": float(gamma.sqrt()), "residual": float(torch.linalg.vector_norm(b - op.matvec(x))), "converged": bool(converged)}
+    return x, info
