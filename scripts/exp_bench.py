@@ -22,7 +22,7 @@ def main():
     plans = []
     for v in variants:
         kv = dict(s.split("=") for s in v.split(",") if s)
-        libv = kv.pop("LIB", None)   # LIB=_abl1: a diagnostic build made with `make VARIANT=_abl1 ... libs` (same Tile_matrix struct)
+        libv = kv.pop("LIB", None)   # LIB=_old: lib/libtilespmv_*_old.so, e.g. an earlier commit built by scripts/ab_prev.sh (same Tile_matrix struct)
         for k, val in kv.items(): os.environ[k] = val
         base_lib = tm._lib
         if libv is not None:

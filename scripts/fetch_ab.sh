@@ -1,5 +1,5 @@
 #!/bin/bash
-# FETCH_SIZE / WRITE_SIZE per launch of the unit kernel for the product library and diagnostic variants: scripts/fetch_ab.sh <workload> <dtype> "<variant> <variant> ..."  ("-" = product)
+# FETCH_SIZE / WRITE_SIZE per launch of the unit kernel for the product library and other library variants (e.g. _old, scripts/ab_prev.sh): scripts/fetch_ab.sh <workload> <dtype> "<variant> <variant> ..."  ("-" = product)
 wl=$1; dt=$2; export TMPDIR=/tmp
 for v in $3; do
   [ "$v" = "-" ] && v=""

@@ -3,7 +3,7 @@
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tilespmv_amd import api, generators as G
-if os.environ.get("PROBE_LIB"):   # a diagnostic build (make VARIANT=... libs)
+if os.environ.get("PROBE_LIB"):   # another library by suffix, e.g. _old (scripts/ab_prev.sh build <commit>)
     os.environ["TILESPMV_LIB_VARIANT"] = os.environ["PROBE_LIB"]
 wl = sys.argv[1] if len(sys.argv) > 1 else "nlpkkt160"
 dtype = np.float32 if (len(sys.argv) > 2 and sys.argv[2] == "f32") else np.float64

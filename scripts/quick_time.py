@@ -1,4 +1,4 @@
-"""Default-plan times of a few workloads, fp64 and fp32 (python scripts/quick_time.py wl,wl [f64|f32|both]); TILESPMV_LIB_VARIANT picks a diagnostic library."""
+"""Default-plan times of a few workloads, fp64 and fp32 (python scripts/quick_time.py wl,wl [f64|f32|both]); TILESPMV_LIB_VARIANT picks a library by suffix (e.g. _old, scripts/ab_prev.sh)."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -51,7 +51,7 @@ class PlanOptions(C.Structure):
 
 def lib_path(dtype):
     suf = "f64" if np.dtype(dtype) == np.float64 else "f32"
-    # TILESPMV_LIB_VARIANT: diagnostic builds made with `make VARIANT=... libs` (timing-only ablations; never the product)
+    # TILESPMV_LIB_VARIANT: a library with a suffix, e.g. an earlier commit's built by scripts/ab_prev.sh as lib*_old.so (A/B in one process; never the product)
     return os.path.join(_ROOT, "lib", "libtilespmv_%s%s.so" % (suf, os.environ.get("TILESPMV_LIB_VARIANT", "")))
 
 

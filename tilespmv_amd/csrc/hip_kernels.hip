@@ -27,37 +27,6 @@
 
 #include "hip_plan.h"
 
-// Timing-only diagnostics (ablations whose results are wrong by construction, clock stamps, cache-policy probes) live in hip_kernels_diag.h, which only a diagnostic build
-// includes: `make VARIANT=_name EXTRA_DEFS=-D...` adds -DTILESPMV_DIAG and writes lib*_name.so; the Makefile refuses EXTRA_DEFS without VARIANT, so no stray define can
-// turn the product libraries into something that returns wrong rows.  In a product build every hook below expands to nothing.
-#if !defined(TILESPMV_DIAG) && (defined(TILESPMV_ABL) || defined(XCD_ABL) || defined(TILESPMV_STAMPS) || defined(TILESPMV_POOL_ABL) || defined(TILESPMV_ABL_LDS_PAD) || defined(TILESPMV_GATHER_POLICY))
-#error "diagnostic defines (TILESPMV_ABL, XCD_ABL, TILESPMV_STAMPS, TILESPMV_POOL_ABL, TILESPMV_ABL_LDS_PAD, TILESPMV_GATHER_POLICY) need -DTILESPMV_DIAG: build with make VARIANT=_name EXTRA_DEFS=..."
-#endif
-#ifdef TILESPMV_DIAG
-#include "hip_kernels_diag.h"
-#else
-#define TSPMV_DIAG_GATHER_X(p) (*(p))
-#define TSPMV_DIAG_TRIP_DECL
-#define TSPMV_DIAG_TRIP_RECORD(r, q, e0)
-#define TSPMV_DIAG_TRIP_GATHERS
-#define TSPMV_DIAG_TRIP_ADDS_REPLACED 0
-#define TSPMV_DIAG_TRIP_ADDS
-#define TSPMV_DIAG_UNITS_LDS_PAD
-#define TSPMV_DIAG_UNIT_GATHER_SKIP(k) false
-#define TSPMV_DIAG_UNIT_X(i) (i)
-#define TSPMV_DIAG_COO0_ON true
-#define TSPMV_DIAG_COO0_X(c) (c)
-#define TSPMV_DIAG_POOL_ADD(dest, prod) false
-#define TSPMV_DIAG_POOL_X(load, d) (load)
-#define TSPMV_DIAG_XCD_ZERO 1
-#define TSPMV_DIAG_XCD_TRIP 1
-#define TSPMV_DIAG_XCD_SKIP_ADDS
-#define TSPMV_STAMP_DECL
-#define TSPMV_STAMP(i) do { } while (0)
-#define TSPMV_STAMP_WAIT(i) do { } while (0)
-#define TSPMV_STAMP_STORE
-#endif
-
 namespace tilespmv {
 
 // LDS scatter accumulators are fp64 in BOTH builds: on gfx950 a wavefront's ds_add_f32 takes about 170 cycles whatever the address
@@ -393,7 +362,7 @@ typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
 #define ECOO2_MIN_WAVES 6  // workgroup entry mode: 80 VGPRs
 #endif
 #ifndef TILESPMV_UB
-#define TILESPMV_UB 4   // units per batch of the unit loop (diagnostic builds: 8 with UNITS_MIN_WAVES=6 measured below)
+#define TILESPMV_UB 4   // units per batch of the unit loop (8 with UNITS_MIN_WAVES=6 measured below)
 #endif
 #ifndef UNITS_MIN_WAVES
 #define UNITS_MIN_WAVES 8  // waves per SIMD asked of the register allocator (64 VGPRs)
@@ -453,7 +422,6 @@ __device__ __forceinline__ void wave_entry_trips(const DevStream &S, const val_t
 #endif
 // NTL: the records are read with nontemporal loads (plans whose streams do not fit the Infinity Cache: the once-read stream
 // then does not displace x in the L2s; DevStream::nt_stream).
-__device__ __forceinline__ val_t gather_x(const val_t *p) { return TSPMV_DIAG_GATHER_X(p); }   // (diagnostic builds probe other cache policies here: hip_kernels_diag.h)
 
 template <int CT, int NT, bool NTL>
 __device__ __forceinline__ void wg_entry_trips(const ERec *__restrict__ rec, const unsigned *__restrict__ base, int chunk0, int db, bool ordered,
@@ -465,7 +433,6 @@ __device__ __forceinline__ void wg_entry_trips(const ERec *__restrict__ rec, con
     const unsigned dmask = (1u << db) - 1u;
     const int wave = tid >> 6;
     const int clast = chunk0 + ((ge - 1 - gb) >> 6);
-    TSPMV_DIAG_TRIP_DECL
     ERec rr[CT]; unsigned cb[CT];
     auto load_trip = [&](int e0, ERec (&r)[CT], unsigned (&c)[CT]) {   // unconditional, clamped: exact vmcnt
 #pragma unroll
@@ -477,7 +444,6 @@ __device__ __forceinline__ void wg_entry_trips(const ERec *__restrict__ rec, con
                 for (int z = 0; z < (int)(sizeof(ERec) / 4); z++) rw[z] = __builtin_nontemporal_load(pw + z);
             } else r[q] = rec[min(e0 + NT * q + tid, ge - 1)];
             c[q] = base[__builtin_amdgcn_readfirstlane(min(chunk0 + ((e0 - gb) >> 6) + (NT / 64) * q + wave, clast))];   // a wavefront's 64 records are one chunk
-            TSPMV_DIAG_TRIP_RECORD(r, q, e0)
         }
     };
     if (e_first < ge) load_trip(e_first, rr, cb);
@@ -485,14 +451,12 @@ __device__ __forceinline__ void wg_entry_trips(const ERec *__restrict__ rec, con
         val_t xx[CT];
         if (!WG_TRIP_PIPE && e0 > e_first) load_trip(e0, rr, cb);
 #pragma unroll
-        for (int q = 0; q < CT; q++) xx[q] = gather_x(&x[(size_t)(cb[q] + (rr[q].w >> db))]);
-        TSPMV_DIAG_TRIP_GATHERS
+        for (int q = 0; q < CT; q++) xx[q] = x[(size_t)(cb[q] + (rr[q].w >> db))];
         // the next trip's records go in flight behind this trip's gathers (loads return in issue order: the gathers are waited
         // for with the prefetch still outstanding); the last trip re-requests its own (clamped) records, which costs nothing
         ERec rn[CT]; unsigned cn[CT];
         if (WG_TRIP_PIPE) load_trip(min(e0 + NT * CT, gb + (ge - 1 - gb) / (NT * CT) * (NT * CT)), rn, cn);
-        if constexpr (TSPMV_DIAG_TRIP_ADDS_REPLACED) { TSPMV_DIAG_TRIP_ADDS }
-        else if (ordered) {
+        if (ordered) {
             // the wavefronts add in turn: the order of the additions into one y element is then fixed by the plan (entry
             // order inside a wavefront instruction, instruction order inside a wavefront, wavefront 0..NT/64-1 inside a trip), not
             // by timing, and two launches give the same bits (the reference's atomicAdd, src/tilespmv_cuda.h:784-790, does not)
@@ -595,7 +559,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
     __shared__ uint4 s_d[GROUPS_PER_BLOCK][DCHUNK];
     __shared__ uint2 s_r[POOL && !WIDE ? GROUPS_PER_BLOCK : 1][POOL && !WIDE ? DCHUNK : 1];   // pooled plans: row nibbles of the parked descriptor chunk
     __shared__ uint4 s_c[WIDE ? GROUPS_PER_BLOCK : 1][WIDE ? DCHUNK : 1];                   // wide pooled plans: column-offset bytes of the parked chunk
-    TSPMV_DIAG_UNITS_LDS_PAD
     const int tid = threadIdx.x, r = tid & 15, g = tid >> 4;
     // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD group), each
     // with a private L2; xcd_chunk > 0 gives every XCD runs of xcd_chunk consecutive workgroups inside
@@ -605,8 +568,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         const unsigned C = (unsigned)xcd_chunk, W = 8u * C, win = bid / W, off = bid % W, k = off & 7u;
         if ((win + 1) * W <= gridDim.x) bid = win * W + k * C + (off >> 3);
     }
-    TSPMV_STAMP_DECL
-    TSPMV_STAMP(0);
     const long long task_id = (long long)bid * GROUPS_PER_BLOCK + g;
     const bool have = task_id < S.ntasks;
     constexpr bool WCOO = ECOO == 1;
@@ -706,22 +667,20 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
 #pragma unroll
             for (int k = 0; k < UB; k++) rw[k] = sr[2 * (j0 + k)];
 #pragma unroll
-            for (int k = 0; k < UB; k++) xv[k] = TSPMV_DIAG_POOL_X(x[min((long long)(d[k].x & POOL_BASE_MASK) + (long long)((d[k].y >> (28 - 4 * (r & 7))) & 15u), xlast)], d[k]);
+            for (int k = 0; k < UB; k++) xv[k] = x[min((long long)(d[k].x & POOL_BASE_MASK) + (long long)((d[k].y >> (28 - 4 * (r & 7))) & 15u), xlast)];
             return;
         }
 #pragma unroll
         for (int k = 0; k < UB; k++) {
             const unsigned fl = d[k].x >> 24;
             const unsigned nib = (fl & UNIT_ROWUNIT) ? (unsigned)r : (d[k].y >> (28 - 4 * (r & 7))) & 15u;
-            if (TSPMV_DIAG_UNIT_GATHER_SKIP(k)) xv[k] = xv[k - 1];
-            else if ((d[k].x >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE && r != 15) xv[k] = 0;   // derived unit: only lane 15 loads (unit_x_use gives the others the previous unit's x)
-            else xv[k] = x[TSPMV_DIAG_UNIT_X(min(unit_x_base(d[k].x) + nib, xlast))];
+            if ((d[k].x >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE && r != 15) xv[k] = 0;   // derived unit: only lane 15 loads (unit_x_use gives the others the previous unit's x)
+            else xv[k] = x[min(unit_x_base(d[k].x) + nib, xlast)];
         }
     };
 
     if constexpr (ECOO == 2) {
         const int4 wr = S.wg_coo[bid];
-        TSPMV_STAMP_WAIT(1);   // task and list range have arrived
         // a strip with entries adds its slab at the end, so its slab is zeroed even when the workgroup's list is empty: in a column-panelled plan (x_panels > 1) all of a
         // strip's entries may sit in the other panels' lists
         if (wr.y > wr.x) {  // workgroup-uniform
@@ -735,7 +694,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         // 6 waves — and changes nothing: power-law 8 M 0.1026-0.1034 ms either way, profiles/r03_entry_ablations.txt: bytes in flight are not the limit)
         // pipelined trips on top of that (78 VGPRs at 6 x 256, no spill): 0.1050-0.1062 against 0.1031-0.1046 — slightly worse
         unit_prologue();
-        TSPMV_STAMP_WAIT(2);   // prologue has arrived (the entry loads are inside the trips)
         if (wr.y > wr.x) {
             int ge = wr.y;   // column-panelled launch: this kernel takes the first panel_merge panels of the list, k_entries_acc the rest
             if (GPB == 16 && S.panel_merge > 0) ge = S.panel_off[(size_t)bid * (size_t)(S.x_panels + 1) + (size_t)min(S.x_panels, S.panel_merge)];
@@ -743,7 +701,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             wg_entry_trips<WCOO_HEAVY_CT, 16 * GPB, NTS>(S.grec, S.gbase, wr.z, S.dest_bits, S.coo_ordered != 0, x, &s_y[0][0][0], tid, wr.x, ge);
             __syncthreads();
         }
-        TSPMV_STAMP_WAIT(3);   // entry phase done
     } else if constexpr (WCOO) {
         // ---- small grids (entry mode 1 is chosen when the whole grid is resident at once): the kernel is a chain of
         // round trips, so everything that can be in flight together is: task -> {unit prologue, entry loads} -> {x gathers
@@ -754,7 +711,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         const int4 wr = S.wg_coo[(long long)bid * (GROUPS_PER_BLOCK / 4) + (g >> 2)];  // this wavefront's merged list
         const int tot = wr.y - wr.x;
         lacc_t *swave = &s_y[g & ~3][0][0];  // the wavefront's four slabs of STRIP_MAX_ROWS x 16 values
-        TSPMV_STAMP_WAIT(1);   // task and list range have arrived
         unit_prologue();
         ERec rr[CT]; unsigned cbase[CT]; val_t xx[CT];
         const int db = S.dest_bits;
@@ -772,7 +728,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             wave_lds_fence();
             fetch_batch(0);
         } else if (tot > 0) wave_lds_fence();
-        TSPMV_STAMP_WAIT(2);   // prologue + entry loads (and the first unit batch's gathers) have arrived
         if (tot > 0) {
             const unsigned dmask = (1u << db) - 1u;
 #pragma unroll
@@ -783,7 +738,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             if (tot > 64 * CT) wave_entry_trips<CT>(S, x, swave, lane, wr.x, wr.y, wr.z, CT);
             wave_lds_fence();
         }
-        TSPMV_STAMP_WAIT(3);   // entry phase done
     } else {
     // ---- issue order: first COO chunk, descriptor chunk 0 (+1), first value batch: all in flight together.
     // Strips with many COO entries (> coo_heavy_min, default 32: irregular matrices) run their entry list first,
@@ -812,11 +766,11 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         wave_lds_fence();
     }
     unsigned rb0 = 0; int cc0 = 0; val_t cv0 = 0;
-    const bool coo0 = TSPMV_DIAG_COO0_ON && side && !coo_heavy && (coo_begin + r < coo_end);
+    const bool coo0 = side && !coo_heavy && (coo_begin + r < coo_end);
     if (coo0) { rb0 = stream_load<NT_COO0>(S.crow + coo_begin + r); cc0 = stream_load<NT_COO0>(S.ccol + coo_begin + r); cv0 = stream_load<NT_COO0>(S.cval + coo_begin + r); }
     unit_prologue();
     if (side && !coo_heavy) {  // up to coo_heavy_min entries: 16 with the prologue loads, the rest 4 x 16 per trip
-        if (coo0) atomicAdd(&s_y[g][rb0 >> 4][rb0 & 15u], (lacc_t)(cv0 * x[TSPMV_DIAG_COO0_X(cc0)]));
+        if (coo0) atomicAdd(&s_y[g][rb0 >> 4][rb0 & 15u], (lacc_t)(cv0 * x[cc0]));
         for (int e0 = coo_begin + 16; e0 < coo_end; e0 += 64) {
             unsigned rb[4]; int cc[4]; val_t cv[4], xx[4];
 #pragma unroll
@@ -841,7 +795,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
     auto retire = [&](val_t prod, unsigned flags, unsigned word1) {
         if constexpr (POOL) {   // flags = word 0 >> 24 (tile-row in strip in its top nibble), word1 = this lane's half of the row nibbles
             const unsigned dest = ((flags >> (POOL_KR_SHIFT - 24)) & 7u) * 16u + ((word1 >> (28 - 4 * (r & 7))) & 15u);
-            if (TSPMV_DIAG_POOL_ADD(dest, prod)) return;
             if constexpr (PCOPY) atomicAdd(((r & 1) ? s_y1 : &s_y[0][0][0]) + g * (SROWS * 16) + dest, (lacc_t)prod);
             else atomicAdd(&s_y[g][0][0] + dest, (lacc_t)prod);
             return;
@@ -920,7 +873,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             for (int k = 0; k < UB; k++) v[k] = vn[k];
         }
     }
-    TSPMV_STAMP_WAIT(4);       // unit loop done
     if constexpr (POOL) {   // every add of this wavefront into the slab is behind us
         wave_lds_fence();
         if constexpr (PCOPY) {
@@ -1007,7 +959,6 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             }
         }
     }
-    TSPMV_STAMP_STORE
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1096,11 +1047,10 @@ __global__ __launch_bounds__(256, ECOO2_MIN_WAVES) void k_entries_xcd(DevStream 
     }
     const bool side = t0.w > t0.z;
     const int row0 = t1.x, part = t1.y, nrows = t1.w;
-    if (TSPMV_DIAG_XCD_ZERO) for (int i = tid; i < GROUPS_PER_BLOCK * STRIP_MAX_ROWS * 16; i += 256) s_acc[i] = 0;
+    for (int i = tid; i < GROUPS_PER_BLOCK * STRIP_MAX_ROWS * 16; i += 256) s_acc[i] = 0;
     __syncthreads();
-    if (TSPMV_DIAG_XCD_TRIP) wg_entry_trips<CT, 256, NTS>(S.grec, S.gbase, wr.z, S.dest_bits, false, x, s_acc, tid, wr.x, ge, gs);
+    wg_entry_trips<CT, 256, NTS>(S.grec, S.gbase, wr.z, S.dest_bits, false, x, s_acc, tid, wr.x, ge, gs);
     __syncthreads();
-    TSPMV_DIAG_XCD_SKIP_ADDS
     if (!side) return;
     const lacc_t *mine = s_acc + g * (STRIP_MAX_ROWS * 16);
     if (part >= 0) {
@@ -1314,7 +1264,7 @@ __global__ __launch_bounds__(256, MV_MIN_WAVES) void k_units_mv(DevStream S, int
     constexpr int STRIPS = GROUPS_PER_BLOCK / Q;
     typedef MVec<NV> vec_t;
 #ifndef MV_UBX
-#define MV_UBX 1   // value groups per batch of the multi-vector unit loop (diagnostic builds: 2 = twice the units in flight per wavefront, needs MV_MIN_WAVES <= 5)
+#define MV_UBX 1   // value groups per batch of the multi-vector unit loop (2 = twice the units in flight per wavefront, needs MV_MIN_WAVES <= 5)
 #endif
     constexpr int UB = UNIT_GROUP * MV_UBX; // MV_UBX 16-byte value loads per batch (2 units fp64, 4 units fp32 each)
     // the next descriptor chunk is prefetched into registers (4 VGPRs) except in the fp64 nvec 4 / 8 variants: there the
@@ -2033,8 +1983,7 @@ hipError_t launch_tiles_stream(const DevPlan &P, const DevStream &S, const DevDe
 #define TSPMV_FORM_SMALL(W, B) TSPMV_FORM_(W, B, TSPMV_PLAIN)  /* small grids, entry mode 1: default cache policy */
         // Grids that would give fewer than half the CUs a 256-thread workgroup run 128-thread workgroups of 8 strips instead: twice the workgroups, the same strips
         // (per-strip and per-wavefront entry modes only: the workgroup mode merges the lists of its 16 strips at plan creation)
-        static const int small_grid_workgroups = [] { const char *e = getenv("TILESPMV_SMALL_GRID_WORKGROUPS"); return e && *e ? atoi(e) : SMALL_GRID_WORKGROUPS; }();   // (0 switches the form off)
-        const bool small_grid = entry_mode != 2 && !S.nt_stream && (S.ntasks + 15) / 16 < small_grid_workgroups;
+        const bool small_grid = entry_mode != 2 && !S.nt_stream && (S.ntasks + 15) / 16 < SMALL_GRID_WORKGROUPS;
         if (small_grid) { if (entry_mode == 1) TSPMV_FORM_SMALL(1, 8); else TSPMV_FORM_SMALL(0, 8); }
         else if (entry_mode == 1) TSPMV_FORM_SMALL(1, 16);                                    // (entry mode 1 = small grids: never nontemporal)
         else if (entry_mode == 2 && wg_strips == 32 && !S.pooled) {                          // 512-thread workgroups: classic / dictionary descriptors only

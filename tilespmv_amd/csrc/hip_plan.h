@@ -41,10 +41,7 @@ struct ERec { unsigned v, w; };            // 8 bytes
 struct ERec { unsigned lo, hi, w; };       // 12 bytes, 4-byte aligned
 #endif
 constexpr int ECHUNK = 64;                 // records per column-base chunk
-#ifndef TILESPMV_SMALL_GRID_WORKGROUPS
-#define TILESPMV_SMALL_GRID_WORKGROUPS 128
-#endif
-constexpr int SMALL_GRID_WORKGROUPS = TILESPMV_SMALL_GRID_WORKGROUPS;   // grids with fewer 256-thread workgroups than this (half the CUs) run 128-thread workgroups of 8 strips (hip_kernels.hip launch_tiles_stream):
+constexpr int SMALL_GRID_WORKGROUPS = 128;   // grids with fewer 256-thread workgroups than this (half the CUs) run 128-thread workgroups of 8 strips (hip_kernels.hip launch_tiles_stream):
                                                                     // 33-72 workgroups 6-10 % faster, 157-247 (5-pt 400^2, the scircuit stand-in) within 1.5 % either way — profiles/r05_small_grid_forms.txt
 constexpr int FB_DEST_BITS = 11;           // fallback row blocks: <= 2048 rows
 
@@ -198,9 +195,6 @@ struct DevStream {
     // finishes last (fixed slot order): ifix[i] describes row i, ifix_count[i] counts finished pieces
     const FixRow *ifix;
     unsigned *ifix_count;
-#ifdef TILESPMV_STAMPS
-    unsigned long long *stamps;           // diagnostic build only (scripts/stamps_probe.py): 8 clock stamps per wavefront
-#endif
 };
 
 // Dense tiles on the matrix cores (generation 2): one wavefront per tile-row that owns dense tiles.

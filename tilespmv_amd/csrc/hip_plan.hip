@@ -55,7 +55,6 @@ static Knobs resolve_knobs(const tilespmv_plan_options *opts)
     k.x_stride1 = pick(o.x_stride1, "TILESPMV_X_STRIDE1", 0);
     k.x_stride2 = pick(o.x_stride2, "TILESPMV_X_STRIDE2", 0);
     k.lds_pad = pick(o.lds_pad, "TILESPMV_LDS_PAD", -1);
-    k.brick_rows = env_int("TILESPMV_BRICK_ROWS", 0);
     k.y_store = pick(o.y_store, "TILESPMV_Y_STORE", -1);
     k.mv_native = pick(o.mv_native, "TILESPMV_MV_NATIVE", -1);
     k.mv_xcd_chunk = pick(o.mv_xcd_chunk, "TILESPMV_MV_XCD_CHUNK", -1);
@@ -78,6 +77,10 @@ static Knobs resolve_knobs(const tilespmv_plan_options *opts)
     k.entry_from_caller = pinned(o.entry_mode, "TILESPMV_WAVE_COO");
     k.strip_from_caller = o.strip_cost > 0 || env_int("TILESPMV_STRIP_COST", 0) > 0;
     k.autotune_log = getenv("TILESPMV_AUTOTUNE_LOG");
+    k.verbose = getenv("TILESPMV_PLAN_VERBOSE") != nullptr;
+    k.placement_force = env_int("TILESPMV_PLACEMENT_FORCE", 0) != 0;
+    k.encode_check = env_int("TILESPMV_ENCODE_CHECK", 0) != 0;
+    k.encode_on_host = env_int("TILESPMV_ENCODE_ON_HOST", 0) != 0;
     return k;
 }
 
@@ -108,9 +111,8 @@ static void for_each_plan_pointer(tilespmv_plan *plan, F f)
 // one seen stays.  The search stops early once both ends of the spread have been seen (a placement >= 9 % faster than a slow time two placements agree on) or five
 // placements agree within 1.5 %.  Costs up to `tries` copies of the plan for a moment and a few launches each.  What it cannot do is leave the neighbourhood it started in:
 // consecutive candidates land next to each other and, in runs, in the same state (forty placements in a row: 26 slow, then fast — profiles/r04_placement_retry.txt).
-static void retry_placement(tilespmv_plan *plan, int tries)
+static void retry_placement(tilespmv_plan *plan, int tries, const Knobs &K)
 {
-    const bool verbose = getenv("TILESPMV_PLAN_VERBOSE") != nullptr;
     plan->info[TILESPMV_INFO_PLACEMENT_TRIES] = 1;
     if (tries <= 1 || plan->arena_blocks.empty()) return;
     typedef std::vector<std::pair<void *, size_t>> Blocks;
@@ -129,16 +131,13 @@ static void retry_placement(tilespmv_plan *plan, int tries)
         });
     };
     auto show = [&](int t, double ms, const Blocks &bl) {
-        if (!verbose) return;
+        if (!K.verbose) return;
         fprintf(stderr, "tilespmv: placement %d: %.4f ms  blocks at", t, ms);
         for (auto &b : bl) fprintf(stderr, " %p(+%zu MB)", b.first, b.second >> 20);
         fprintf(stderr, "\n");
     };
     // every candidate placement stays allocated until the choice is made: a freed block would simply be handed out again and the same placement timed twice
-    const bool force_last = env_int("TILESPMV_PLACEMENT_FORCE", 0) != 0;
     std::vector<Blocks> cand{plan->arena_blocks};
-    const int retry_spacer_mb = env_int("TILESPMV_RETRY_SPACER_MB", 0);
-    std::vector<void *> spacers;
     std::vector<double> ms{tilespmv_plan_time(plan, dx, dy, nullptr, 3, 5)};
     show(1, ms[0], cand[0]);
     size_t at = 0, best = 0;   // where the plan's pointers point now; the placement to keep
@@ -146,11 +145,6 @@ static void retry_placement(tilespmv_plan *plan, int tries)
         Blocks fresh;
         bool ok = true;
         for (auto &b : cand[0]) {
-            if (retry_spacer_mb > 0) {   // experiment knob TILESPMV_RETRY_SPACER_MB (off): a held allocation of 1-11 units in front of every block of a candidate — consecutive candidates otherwise keep the same distances between their blocks and, in runs, the same state; it found the fast state within two tries in one session and made no difference in the next (profiles/r04_placement_retry.txt)
-                void *sp = nullptr;
-                const size_t sz = ((size_t)((t * 7 + (int)fresh.size() * 3) % 11 + 1) * (size_t)retry_spacer_mb) << 20;
-                if (hipMalloc(&sp, sz) == hipSuccess) spacers.push_back(sp); else (void)hipGetLastError();
-            }
             void *nb = nullptr;
             {   // a candidate needs room for itself with some to spare: ask first instead of probing by failure (all earlier candidates are still held)
                 size_t mem_free = 0, mem_total = 0;
@@ -168,7 +162,7 @@ static void retry_placement(tilespmv_plan *plan, int tries)
         show(t, ms.back(), fresh);
         plan->info[TILESPMV_INFO_PLACEMENT_TRIES] = t;
         if (ms.back() > 0 && ms.back() < 0.99 * ms[best]) best = at;   // the fastest placement seen stays (1 % = the timing's noise)
-        if (force_last) { best = at; continue; }                      // test knob TILESPMV_PLACEMENT_FORCE=1: always move (every plan kind must survive being moved)
+        if (K.placement_force) { best = at; continue; }               // test knob TILESPMV_PLACEMENT_FORCE=1: always move (every plan kind must survive being moved)
         // stop once both ends of the spread have been seen — it is 10-13 % wide on the matrices that have it; the slow end counts only when two placements agree on it
         // within 2 % (a single slow timing may be a hiccup) — or when five placements in a row agree within 1.5 % (nothing to find around here)
         double slow_confirmed = 0, lo = ms[0], hi = ms[0];
@@ -197,8 +191,7 @@ static void retry_placement(tilespmv_plan *plan, int tries)
     }
     if (best != 0) plan->arena_blocks = cand[best];
     plan->arena_at = nullptr; plan->arena_left = 0;   // the bump allocator pointed into the first placement's last block, which may be gone: placement is final, a later upload starts a fresh block
-    for (void *sp : spacers) (void)hipFree(sp);
-    if (verbose) fprintf(stderr, "tilespmv: placement %zu of %zu kept (%.4f ms; first %.4f)\n", best + 1, cand.size(), ms[best], ms[0]);
+    if (K.verbose) fprintf(stderr, "tilespmv: placement %zu of %zu kept (%.4f ms; first %.4f)\n", best + 1, cand.size(), ms[best], ms[0]);
     (void)hipFree(dx); (void)hipFree(dy);
 }
 
@@ -441,7 +434,7 @@ static int plan_create_tuned(tilespmv_plan **out, const Tile_matrix *T, int rowA
     if (!best) return -4;
     if (Kc.placement_tries < 0 && best->info[TILESPMV_INFO_DEVICE_BYTES] >= (1ll << 30)) {
         const double t0p = now_us();
-        retry_placement(best, 8);
+        retry_placement(best, 8, Kc);
         best->info[TILESPMV_INFO_BUILD_US] += (long long)(now_us() - t0p);
         best->info[TILESPMV_INFO_TIMED_CHOICES_US] += (long long)(now_us() - t0p);
     }
@@ -452,11 +445,10 @@ static int plan_create_tuned(tilespmv_plan **out, const Tile_matrix *T, int rowA
 // Column panels (DevStream::panel_off): which launch form the entry lists get, found by timing — the plain launch (whole lists in the unit kernel), panelled launches with
 // passes of about 4, 8 and 16 MB of x, and column slices pinned to XCDs (k_entries_xcd) in 1, 2 or 4 passes where a slice is about 1-8 MB.  A form other than the plain launch
 // stays only when it is at least 3 % faster than it.  Launch-time choice: every candidate runs on the same lists.
-static void calibrate_panels(tilespmv_plan *plan, int colA)
+static void calibrate_panels(tilespmv_plan *plan, int colA, bool verbose)
 {
     // (runs only when the panels per pass are the plan's to choose — plan->panel_calibrate; the sliced candidates join when plan->slice_calibrate allows them)
     DevStream &S = plan->st;
-    const bool verbose = getenv("TILESPMV_PLAN_VERBOSE") != nullptr;
     val_t *dx = nullptr, *dy = nullptr;
     const size_t nx = (size_t)plan->dev.colA + 16, ny = (size_t)plan->dev.rowA + 16;
     S.panel_merge = 0; S.slice_passes = 0;
@@ -514,11 +506,6 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
 
     auto *plan = new tilespmv_plan();
     plan->dry = K.dry;
-    if (const char *af = getenv("TILESPMV_ARENA_FLAGS")) plan->arena_flags = atoi(af);
-    if (const char *as = getenv("TILESPMV_ARENA_SKEW")) plan->arena_skew = (size_t)std::max(0ll, atoll(as)) / 256 * 256;
-    if (const char *sp = getenv("TILESPMV_ARENA_SPACER_MB")) plan->arena_spacer = (size_t)std::max(0ll, atoll(sp)) << 20;
-    plan->arena_spacer_first_only = env_int("TILESPMV_ARENA_SPACER_FIRST", 0) != 0;
-    if (const char *ab = getenv("TILESPMV_ARENA_MB")) plan->arena_block = (size_t)std::max(0, atoi(ab)) << 20;   // (experiment knob; 0 = one hipMalloc per stream)
     if (!K.dry && hipGetDevice(&plan->device) != hipSuccess) { fprintf(stderr, "tilespmv: hipGetDevice failed\n"); delete plan; return -1; }
 
     // ---- how are COO tiles executed?  (bytes model)
@@ -811,13 +798,13 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
     if (!K.dry) {
         const int tries = K.placement_tries >= 0 ? K.placement_tries : (I[TILESPMV_INFO_DEVICE_BYTES] >= (1ll << 30) ? 8 : 1);
         const double t0p = now_us();
-        retry_placement(plan, tries);
+        retry_placement(plan, tries, K);
         I[TILESPMV_INFO_BUILD_US] += (long long)(now_us() - t0p);
         if (tries > 1 && !plan->arena_blocks.empty()) I[TILESPMV_INFO_TIMED_CHOICES_US] += (long long)(now_us() - t0p);
     }
     if (!K.dry && plan->panel_calibrate) {
         const double t0c = now_us();
-        calibrate_panels(plan, colA);
+        calibrate_panels(plan, colA, K.verbose);
         I[TILESPMV_INFO_BUILD_US] += (long long)(now_us() - t0c);
         I[TILESPMV_INFO_TIMED_CHOICES_US] += (long long)(now_us() - t0c);
     }
@@ -896,7 +883,7 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
     if (e == hipSuccess && H.tilenum > 0) e = hipMemcpy(h_fmt.data(), D->T.Format, (size_t)H.tilenum, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { fprintf(stderr, "tilespmv: tile list to the host: %s\n", hipGetErrorString(e)); (void)hipGetLastError(); devtile_destroy(D); return -3; }
     H.tile_ptr = h_tile_ptr.data(); H.tile_columnidx = h_tile_col.data(); H.Format = h_fmt.data();
-    if (getenv("TILESPMV_PLAN_VERBOSE")) fprintf(stderr, "tilespmv: plan from CSR: device Tile_create %.1f ms (CSR upload included), tile list to the host %.1f ms\n", (t1 - t0) * 1e-3, (now_us() - t1) * 1e-3);
+    if (K.verbose) fprintf(stderr, "tilespmv: plan from CSR: device Tile_create %.1f ms (CSR upload included), tile list to the host %.1f ms\n", (t1 - t0) * 1e-3, (now_us() - t1) * 1e-3);
     Knobs Kd = K;
     if (Kd.kernel == TILESPMV_KERNEL_AUTO) Kd.kernel = TILESPMV_KERNEL_STREAM;
     if (Kd.coo_mode == TILESPMV_COO_AUTO) Kd.coo_mode = TILESPMV_COO_IN_TILE;
@@ -921,7 +908,7 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
         if (rc != 0) { tilespmv_plan_destroy(*out); *out = nullptr; }
     }
     devtile_destroy(D);
-    if (getenv("TILESPMV_PLAN_VERBOSE")) fprintf(stderr, "tilespmv: plan from CSR: plan build %.1f ms, tiled matrix released in %.1f ms\n", (t3 - t2) * 1e-3, (now_us() - t3) * 1e-3);
+    if (K.verbose) fprintf(stderr, "tilespmv: plan from CSR: plan build %.1f ms, tiled matrix released in %.1f ms\n", (t3 - t2) * 1e-3, (now_us() - t3) * 1e-3);
     if (rc == 0 && *out) {
         (*out)->info[TILESPMV_INFO_DEVICE_BUILD] = 1;
         (*out)->info[TILESPMV_INFO_TILE_CREATE_US] = (long long)(t1 - t0);
@@ -1046,17 +1033,6 @@ int tilespmv_plan_spmv_n(tilespmv_plan *plan, const MAT_VAL_TYPE *d_x, MAT_VAL_T
     }
     return 0;
 }
-
-#ifdef TILESPMV_STAMPS
-// diagnostic build only: copies the per-wavefront clock stamps of the last k_units launch (8 per wavefront) to the host
-long long tilespmv_plan_stamps(const tilespmv_plan *plan, unsigned long long *out, long long max_words)
-{
-    const long long n = ((long long)plan->st.ntasks + 15) / 16 * 4 * 8;
-    if (!plan->st.stamps || n > max_words) return -n;
-    if (hipMemcpy(out, plan->st.stamps, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    return n;
-}
-#endif
 
 long long tilespmv_plan_stream_digests(const tilespmv_plan *plan, unsigned long long *out, long long max_streams)
 {

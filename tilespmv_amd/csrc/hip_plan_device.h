@@ -20,7 +20,7 @@ struct DevCounts {
     void release();
 };
 
-struct DevShard { const DevTile *D; int tr0, tr1, t_begin, t_end; bool coo_in_tile, dense_mfma; long long stored0, stored; bool absorb = false, derive = false; };   // absorb: plan_tile_ops.h "absorbed list entries"   // stored: blknnz[t_end] - blknnz[t_begin]
+struct DevShard { const DevTile *D; int tr0, tr1, t_begin, t_end; bool coo_in_tile, dense_mfma; long long stored0, stored; bool absorb = false, derive = false, verbose = false; };   // absorb: plan_tile_ops.h "absorbed list entries"   // stored: blknnz[t_end] - blknnz[t_begin]   // verbose: Knobs::verbose
 
 // rc 0 or -3 (HIP error, reported on stderr)
 int dev_fetch_ints(const int *d_array, const long long *idx, int n, int *out);   // out[k] = d_array[idx[k]]

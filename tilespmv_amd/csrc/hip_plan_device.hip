@@ -512,7 +512,6 @@ int dev_count(const DevShard &S, int csr_form, DevCounts *C, hvec<int> &counts3,
 {
     const DevTile *D = S.D;
     const int nt = S.t_end - S.t_begin, ntr = S.tr1 - S.tr0;
-    const bool verbose = getenv("TILESPMV_PLAN_VERBOSE") != nullptr;
     timeval tv0; gettimeofday(&tv0, NULL);
     auto lap_ms = [&]() { timeval t; gettimeofday(&t, NULL); const double ms = (t.tv_sec - tv0.tv_sec) * 1e3 + (t.tv_usec - tv0.tv_usec) * 1e-3; tv0 = t; return ms; };
     C->release();
@@ -560,7 +559,7 @@ int dev_count(const DevShard &S, int csr_form, DevCounts *C, hvec<int> &counts3,
         PD_TRY(hipGetLastError());
         PD_TRY(hipMemcpy(counts3.data(), d_out.p, counts3.size() * sizeof(int), hipMemcpyDeviceToHost));
     }
-    if (verbose) fprintf(stderr, "tilespmv: device count (form %d): per-tile counts + scans %.1f ms, pooled windows + per-row counts to the host %.1f ms\n", csr_form, ms_tiles, lap_ms());
+    if (S.verbose) fprintf(stderr, "tilespmv: device count (form %d): per-tile counts + scans %.1f ms, pooled windows + per-row counts to the host %.1f ms\n", csr_form, ms_tiles, lap_ms());
     return 0;
 }
 

@@ -39,7 +39,7 @@ inline int env_int(const char *name, int dflt)
     return (e && *e) ? atoi(e) : dflt;
 }
 
-// Every tuning knob of one plan build, resolved ONCE at the API boundary (tilespmv_plan_create): option field if set, else the
+// Every tuning knob of one plan build, resolved ONCE at the API boundary (resolve_knobs, hip_plan.hip): option field if set, else the
 // environment variable (getenv only — the library never writes the environment), else the built-in default.  The builder and
 // the autotuner pass this struct around; nothing below the boundary reads the environment.
 struct Knobs {
@@ -54,7 +54,6 @@ struct Knobs {
     int x_window;        // -1 = default
     int x_stride1, x_stride2;   // tile-rows per grid line / plane for the x windows; 0 = detected from the shard
     int lds_pad;         // bytes of unused LDS added to every unit-kernel workgroup (fewer resident workgroups per CU); -1 = chosen from the shard
-    int brick_rows;      // brick order: tile-rows per strip at most (experiment knob, environment only)
     int y_store;         // -1 by rule, 0 plain y stores, 1 streaming (nontemporal) y stores
     int mv_native;       // -1 = by nvec
     int mv_xcd_chunk;    // -1 = the plan's XCD chunk
@@ -69,6 +68,11 @@ struct Knobs {
     bool xcd_from_caller, entry_from_caller, strip_from_caller;   // the autotuner leaves alone what the caller pinned
     bool dry;            // tilespmv_plan_layout_digest: build the layout on the host only, hash instead of upload
     const char *autotune_log;
+    // switches of tests and investigations (environment only)
+    bool verbose;          // TILESPMV_PLAN_VERBOSE: what the builder chose and how long its stages took, on stderr
+    bool placement_force;  // TILESPMV_PLACEMENT_FORCE=1: every placement try moves the plan (every plan kind must survive being moved)
+    bool encode_check;     // TILESPMV_ENCODE_CHECK=1: ENCODE's value pass runs on the host too, and the device's stream is compared with it
+    bool encode_on_host;   // TILESPMV_ENCODE_ON_HOST=1: ENCODE's value pass runs on the host
 };
 
 }  // namespace tilespmv
@@ -101,7 +105,6 @@ struct tilespmv_plan {
     int device = 0;
     int wg_strips = 16;                 // strips per workgroup of the unit kernel (32 only with the workgroup entry mode)
     int lds_pad_bytes = 0;              // extra (unused) dynamic LDS per workgroup of the unit kernel: caps the workgroups resident on a CU (knob lds_pad)
-    int arena_flags = 0; size_t arena_skew = 0, arena_spacer = 0; bool arena_spacer_first_only = false;
     // (Round 4's opt-in chunked physical backing of large blocks — hipMemAddressReserve / hipMemCreate / hipMemMap, TILESPMV_ARENA_VMM_MB — changed the placement state for the better in two of
     // four sessions and had to keep its virtual ranges reserved for the life of the process because of stale translations on re-reserved ranges (LABBOOK S6.19, scripts/micro/vmm_probe.hip): retired in round 6.)
     // a block of the arena (or a candidate placement of one); the plan owns it until block_free / destroy
@@ -111,7 +114,7 @@ struct tilespmv_plan {
         // slack behind every stream are there for that) and what they find must decode to "nothing" (unit 0, offset 0).  hipMalloc happens to hand out zeroed memory;
         // other allocators do not (found the hard way: stale descriptors behind the last strip sent a value prefetch to a wild address).
         *out = nullptr;
-        hipError_t e = arena_flags ? hipExtMallocWithFlags(out, bytes, (unsigned)arena_flags) : hipMalloc(out, bytes);   // experiment knob TILESPMV_ARENA_FLAGS (4 = physically contiguous)
+        hipError_t e = hipMalloc(out, bytes);
         if (e == hipSuccess) e = hipMemset(*out, 0, bytes);
         if (e != hipSuccess) {
             // a tolerated failure (a candidate placement that does not fit) must not leave HIP's sticky last error behind: the next launch_* returns hipGetLastError() and
@@ -141,7 +144,8 @@ struct tilespmv_plan {
     long long vmap_n[VMAP_STREAMS] = {}, vmap_off[VMAP_STREAMS] = {};
     bool vmap_erec[VMAP_STREAMS] = {};
     size_t arena_used = 0;              // bytes handed out by upload() so far
-    char *arena_at = nullptr; size_t arena_left = 0, arena_block = (size_t)256 << 20, arena_next = (size_t)1 << 20, size_hint = 0;   // bump allocator of upload(); size_hint = the builder's estimate of the plan's bytes
+    static constexpr size_t arena_block = (size_t)256 << 20;
+    char *arena_at = nullptr; size_t arena_left = 0, arena_next = (size_t)1 << 20, size_hint = 0;   // bump allocator of upload(); size_hint = the builder's estimate of the plan's bytes
     bool dry = false;                   // layout-digest build: no HIP call, streams are hashed instead of uploaded
     long long list_records = 0;         // records of the merged entry lists (workgroup entry mode)
     bool slice_calibrate = false;       // ... and whether column slices pinned to XCDs beat them (DevStream::slice_passes)
@@ -172,7 +176,7 @@ struct tilespmv_plan {
         // Streams are carved out of a few large device blocks (bump allocation, 256-byte aligned + 256 bytes of slack so that
         // masked tail lanes never fault) instead of one hipMalloc each: a plan is ~20 streams, and large blocks get large
         // page-table fragments whatever state the allocator is in (fewer hipMalloc calls, too).
-        const size_t need = (std::max<size_t>(n, 1) * sizeof(T) + 256 + 255) / 256 * 256 + arena_skew;   // (arena_skew: experiment knob, bytes left unused behind every stream)
+        const size_t need = (std::max<size_t>(n, 1) * sizeof(T) + 256 + 255) / 256 * 256;
         if (need > arena_left) {   // blocks of arena_block bytes (256 MB) for plans of that size and more; a smaller plan gets one block of about its own size (size_hint)
             // ... and the LAST blocks of a large plan are sized by what the builder still expects to upload (round 5: config 4's plan is 689 MB — its third 256-MB block was
             // followed by a fourth for the last few MB of task records, and allocating + zeroing that block was 90 ms of a 260-ms plan creation)
@@ -180,12 +184,8 @@ struct tilespmv_plan {
             const size_t tail = std::max<size_t>((size_t)32 << 20, left_hint + left_hint / 8 + ((size_t)4 << 20));
             const size_t want = size_hint >= arena_block ? std::min(arena_block, tail) : std::max<size_t>(arena_next, size_hint + size_hint / 4 + ((size_t)1 << 20));
             const size_t blk = std::max<size_t>(need, std::min(want, arena_block));
-            arena_next = std::min<size_t>(arena_next * 4, std::max<size_t>(arena_block, 1));
+            arena_next = std::min<size_t>(arena_next * 4, arena_block);
             void *b = nullptr;
-            if (arena_spacer && (!arena_spacer_first_only || arena_blocks.empty())) {   // experiment knob TILESPMV_ARENA_SPACER_MB: an unused allocation in front of every block (does where a block lands decide its state? DESIGN.md S6.19)
-                void *sp = nullptr;
-                if (hipMalloc(&sp, arena_spacer) == hipSuccess) allocs.push_back(sp); else (void)hipGetLastError();
-            }
             if (block_alloc(&b, blk) != 0) return -1;
             arena_blocks.push_back({b, blk});
             arena_at = (char *)b; arena_left = blk;

@@ -189,7 +189,7 @@ void StreamBuilder::count()
     derive = absorb && K.absorb != 2;        // derived units (plan_tile_ops.h): absorb = 2 keeps every unit gathering
     const int t_begin = T->tile_ptr[tr0], t_end = T->tile_ptr[tr1];
     if (DT) {
-        DS = DevShard{DT, tr0, tr1, t_begin, t_end, coo_in_tile, dense_mfma, 0, 0, absorb, derive};
+        DS = DevShard{DT, tr0, tr1, t_begin, t_end, coo_in_tile, dense_mfma, 0, 0, absorb, derive, K.verbose};
         const long long idx[2] = {t_begin, t_end}; int v[2] = {0, 0};
         if (dev_fetch_ints(DT->T.blknnz, idx, 2, v) != 0) { rc = -3; return; }
         DS.stored0 = v[0]; DS.stored = (long long)v[1] - v[0];
@@ -292,8 +292,8 @@ void StreamBuilder::count()
         const bool take_regular = !take && coo_in_tile && e_classic * 10 >= all_vals && desc_split == 4 && e2 * 2 <= e1 && pooled_reg_b <= split_b && 16 * u2 >= e2 && !would_panel;
         if (take || take_regular) { rc_.swap(alt); csr_form = 2; std::swap(dcnt, dcnt_alt); dcnt.csr_form = 2; }
         dcnt_alt.release();
-        if (getenv("TILESPMV_PLAN_VERBOSE")) fprintf(stderr, "tilespmv: CSR tiles: split form (%d-byte descriptors) %lld units + %lld entries = %.1f MB, pooled form %lld units + %lld entries = %.1f MB -> %s\n",
-                                                     desc_split, u1, e1, split_b / 1e6, u2, e2, pooled_b / 1e6, csr_form == 2 ? (take ? "pooled" : "pooled (regular shard, entries halved)") : "split");
+        if (K.verbose) fprintf(stderr, "tilespmv: CSR tiles: split form (%d-byte descriptors) %lld units + %lld entries = %.1f MB, pooled form %lld units + %lld entries = %.1f MB -> %s\n",
+                               desc_split, u1, e1, split_b / 1e6, u2, e2, pooled_b / 1e6, csr_form == 2 ? (take ? "pooled" : "pooled (regular shard, entries halved)") : "split");
     }
     // ---- wide pooled units (hip_plan.h; csr_form 3): windows of 256 columns take what 16-column windows leave on the entry lists — where the nonzeros are dense enough inside those
     // windows that a unit's 16 gathers still touch few lines of x (window-shuffled FEM / shell meshes: 1.5-3 lines per unit) it wins 5-20 %; where every slot sits on a line of its own
@@ -316,8 +316,8 @@ void StreamBuilder::count()
         //  nonzeros, do not: 0.081 -> 0.074 ms on the 4 M-row one)
         const bool would_panel = (long long)K.coo_cost * e3 * 2 > 16LL * u3 + (long long)K.coo_cost * e3 && 3 * e3 > 16 * u3 && (long long)colA * sv >= (12ll << 20);
         const bool take = lines3 <= POOL_WIDE_MAX_LINES && moved * 25 >= (16 * u3 + e3) && wide_b * 100 <= best_b * 103 && 16 * u3 >= e3 && !would_panel;
-        if (getenv("TILESPMV_PLAN_VERBOSE")) fprintf(stderr, "tilespmv: wide windows: %lld units + %lld entries = %.1f MB (chosen so far: %lld + %lld = %.1f MB), %.2f lines of x per pooled unit, %.1f %% of the nonzeros leave the lists -> %s\n",
-                                                     u3, e3, wide_b / 1e6, ub, eb, best_b / 1e6, lines3, 100.0 * moved / std::max(1LL, 16 * u3 + e3), take ? "wide" : "kept");
+        if (K.verbose) fprintf(stderr, "tilespmv: wide windows: %lld units + %lld entries = %.1f MB (chosen so far: %lld + %lld = %.1f MB), %.2f lines of x per pooled unit, %.1f %% of the nonzeros leave the lists -> %s\n",
+                               u3, e3, wide_b / 1e6, ub, eb, best_b / 1e6, lines3, 100.0 * moved / std::max(1LL, 16 * u3 + e3), take ? "wide" : "kept");
         if (take) { rc_.swap(alt); csr_form = 3; std::swap(dcnt, dcnt_alt); dcnt.csr_form = 3; }
         dcnt_alt.release();
     }
@@ -390,7 +390,7 @@ void StreamBuilder::choose()
     entry_mode = wave_coo_env >= 0 ? std::min(2, wave_coo_env) : (!entry_heavy ? 0 : est_wgs < 768 ? 1 : 2);
     wave_coo = entry_mode != 0;
     plan->entry_mode = entry_mode;
-    if (getenv("TILESPMV_PLAN_VERBOSE")) {
+    if (K.verbose) {
         long long rows_over16 = 0;   // tile-rows with more entries than travel with a strip's prologue
         for (int i = 0; i < ntr; i++) rows_over16 += rc_[i].ncoo > 16;
         fprintf(stderr, "tilespmv: choose: %d tile-rows, %lld units + %lld entries (%.1f per tile-row, %lld tile-rows with more than 16), cost %lld (%.0f per tile-row) -> strips of %d, ~%lld workgroups, entry mode %d\n",
@@ -420,7 +420,7 @@ void StreamBuilder::choose()
     if (brick && xs1 == 0) detect_strides(T, tr0, tr1, csr_split, dense_mfma, &xs1, &xs2);
     if (xs1 < 2 || (K.x_window < 0 && xs2 == 0)) brick = false;   // (2-D grids: measured neutral on the 5-point 4096^2 case)
     // (strips of at most 4 tile-rows in brick plans: nlpkkt160 stand-in fp64 0.418 -> 0.414 ms, fp32 0.252 -> 0.250 in one process; 2 rows: KKT 0.408 but 7-pt 256^3 +5 %)
-    max_strip_rows = pooled ? POOL_STRIP_ROWS : brick ? (K.brick_rows > 0 ? std::min(K.brick_rows, STRIP_MAX_ROWS) : 4) : STRIP_MAX_ROWS;
+    max_strip_rows = pooled ? POOL_STRIP_ROWS : brick ? 4 : STRIP_MAX_ROWS;
     if (brick && !K.xcd_from_caller) plan->xcd_chunk = 8;   // bricks are compact: smaller XCD windows keep an XCD's resident set together
     // ---- column panels of the entry lists (hip_plan.h DevStream::x_panels): scattered, entry-dominated shards whose x is several times an XCD's L2
     {
@@ -700,15 +700,14 @@ void StreamBuilder::order()
                 avgs[(size_t)si] = wgs ? (double)slots / (double)wgs : 1e30;
             }
         });
-        static const int forced_shape = [] { const char *e = getenv("TILESPMV_BRICK_SHAPE"); return e && *e ? atoi(e) : -1; }();   // (experiment knob, environment only: index into the shape list)
         for (int si = 0; si < nshapes; si++)
-            if (forced_shape >= 0 && forced_shape < nshapes ? si == forced_shape : avgs[(size_t)si] < best_avg * 0.98) { best_avg = avgs[(size_t)si]; best_order.swap(orders[(size_t)si]); best_shape = shapes[si]; }
+            if (avgs[(size_t)si] < best_avg * 0.98) { best_avg = avgs[(size_t)si]; best_order.swap(orders[(size_t)si]); best_shape = shapes[si]; }
         {
             std::vector<STask> permuted(nt);
             for (size_t i = 0; i < nt; i++) permuted[i] = tasks[best_order[i]];
             tasks.swap(permuted);
         }
-        if (getenv("TILESPMV_PLAN_VERBOSE"))
+        if (K.verbose)
             fprintf(stderr, "tilespmv: brick order: strides %d / %d tile-rows, brick %d x %d x %d strips, %.1f distinct column blocks per workgroup on the sample\n",
                     xs1, xs2, best_shape.px, best_shape.py, best_shape.pz, best_avg);
     } else brick = false;
@@ -831,8 +830,8 @@ void StreamBuilder::encode()
         std::vector<uint4> packed_col(wide ? (size_t)NUP : 0, make_uint4(0u, 0u, 0u, 0u));
         // The value pass (the plan's largest array, permuted into groups per task) runs on the DEVICE unless this is a layout-digest build or TILESPMV_ENCODE_ON_HOST=1 asks for
         // the host pass — which stays as the checker: TILESPMV_ENCODE_CHECK=1 runs both and compares the device's stream with the host's, byte for byte (tests/test_gpu_parity.py)
-        const bool encode_check = !plan->dry && env_int("TILESPMV_ENCODE_CHECK", 0) != 0;
-        const bool on_device = !plan->dry && NUP > 0 && env_int("TILESPMV_ENCODE_ON_HOST", 0) == 0;
+        const bool encode_check = !plan->dry && K.encode_check;
+        const bool on_device = !plan->dry && NUP > 0 && !K.encode_on_host;
         val_t *paired = (on_device && !encode_check) ? nullptr : zalloc<val_t>((size_t)NUP * 16);
         std::vector<int4> pair_map(on_device ? tasks.size() : 0);
         std::vector<long long> new_begin(tasks.size());
@@ -859,14 +858,6 @@ void StreamBuilder::encode()
                 if (n > 0) { k.unit_begin = (int)nb; k.unit_end = (int)(nb + n); }
             }
         });
-        if (pooled && !wide && getenv("TILESPMV_POOL_PATTERN_STAT")) {   // (study: how many distinct (column nibbles, row nibbles) patterns do the pooled units of this shard use?)
-            std::unordered_map<std::string, long long> cnt;
-            for (long long u = 0; u < NUP; u++) { unsigned w[4] = {packed[(size_t)u].n0, packed[(size_t)u].n1, packed_row[(size_t)u].r0, packed_row[(size_t)u].r1}; cnt[std::string((const char *)w, 16)]++; }
-            std::vector<long long> c; for (auto &kv : cnt) c.push_back(kv.second);
-            std::sort(c.begin(), c.end(), std::greater<long long>());
-            long long top1k = 0, top4k = 0, top64k = 0; for (size_t i = 0; i < c.size(); i++) { if (i < 1024) top1k += c[i]; if (i < 4096) top4k += c[i]; if (i < 65536) top64k += c[i]; }
-            fprintf(stderr, "tilespmv: pooled units: %lld units, %zu distinct 16-byte patterns; the 1,024 / 4,096 / 65,536 most frequent cover %.1f / %.1f / %.1f %% of the units\n", NUP, c.size(), 100.0 * top1k / std::max(1LL, NUP), 100.0 * top4k / std::max(1LL, NUP), 100.0 * top64k / std::max(1LL, NUP));
-        }
         // ---- 4-B descriptors where the units of the shard use few distinct column patterns (stencil-like shards: 4 patterns in the
         // 5- and 7-point grids, 36 in the KKT stand-in): column block | pattern id << cb_bits | flags << 27, the patterns (the
         // two nibble words) in a dictionary the kernels gather from.  Not for x-window plans (their descriptors hold slots).
@@ -1002,7 +993,7 @@ void StreamBuilder::encode()
                 std::vector<val_t> back((size_t)NUP * 16);
                 e = hipMemcpy(back.data(), S.uval, back.size() * sizeof(val_t), hipMemcpyDeviceToHost);
                 if (e == hipSuccess && memcmp(back.data(), paired, back.size() * sizeof(val_t)) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
-                else if (e == hipSuccess && getenv("TILESPMV_PLAN_VERBOSE")) fprintf(stderr, "tilespmv: encode check: %lld units, device value stream == host value stream\n", NUP);
+                else if (e == hipSuccess && K.verbose) fprintf(stderr, "tilespmv: encode check: %lld units, device value stream == host value stream\n", NUP);
             }
             if (d_src) (void)hipFree(d_src);
             if (d_map) (void)hipFree(d_map);
@@ -1167,10 +1158,6 @@ void StreamBuilder::finish(long long &n_tasks, long long &model_bytes)
     // small grids: XCD windows of 8 x 8 workgroups — with the default 8 x 32 a grid of under 256 workgroups has no full window at all and is dealt round-robin, so neighbouring strips
     // never share an XCD's L2 (scircuit stand-in, 246 workgroups: 6.95 -> 6.55 us; webbase stand-in, 750: 13.05 -> 12.75; profiles/r05_small_grid_forms.txt)
     if (!K.xcd_from_caller && ((long long)tasks.size() + wg_strips - 1) / wg_strips < 1024) plan->xcd_chunk = 8;
-#ifdef TILESPMV_STAMPS
-    { void *sp = nullptr; const size_t nst = ((tasks.size() + 15) / 16) * 4 * 8;
-      if (hipMalloc(&sp, nst * 8 + 64) == hipSuccess) { (void)hipMemset(sp, 0, nst * 8 + 64); plan->allocs.push_back(sp); } S.stamps = (unsigned long long *)sp; }
-#endif
     S.ifix = nullptr; S.ifix_count = nullptr;
     if (!ifix.empty()) {
         rc |= plan->upload(ifix.data(), ifix.size(), &S.ifix);
@@ -1201,8 +1188,7 @@ void StreamBuilder::finish(long long &n_tasks, long long &model_bytes)
     {   // entry slab of the multi-vector kernel: shards with >= 3 entries per tile-row (strips then regularly hold more than the 16 entries that travel with the prologue)
         int used = 1;
         for (const STask &k : tasks) used = std::max(used, k.nrows);
-        const int slab_env = env_int("TILESPMV_MV_SLAB", -1);   // (experiment knob: 0 off, 1 on wherever entries exist)
-        plan->mv_slab_rows = (slab_env == 0 || NC == 0) ? 0 : (slab_env > 0 || NC >= 3LL * ntr) ? used : 0;
+        plan->mv_slab_rows = NC > 0 && NC >= 3LL * ntr ? used : 0;
     }
     plan->mv_by_columns = entry_dominated && target >= 800;   // (small strips hold few entries each: scircuit-like 18 / 22 / 32 us native against 22 / 41 / 78 us)
     n_tasks = (long long)tasks.size();
@@ -1234,11 +1220,10 @@ int tilespmv::build_stream(tilespmv_plan *plan, const Knobs &K, const Tile_matri
                            std::vector<FixRow> &fix, int &npartial, long long &n_tasks, long long &model_bytes, const DevTile *DT)
 {
     StreamBuilder B(plan, K, T, rowA, colA, tr0, tr1, coo_in_tile, dense_mfma, hyb_off, fix, npartial, DT);
-    const bool verbose = getenv("TILESPMV_PLAN_VERBOSE") != nullptr;
     double t_prev = now_us(), up_prev = (double)plan->info[TILESPMV_INFO_UPLOAD_US];
     std::string times;
     auto lap = [&](const char *name) {   // host milliseconds of the stage (its uploads counted apart)
-        if (!verbose) return;
+        if (!K.verbose) return;
         const double t = now_us(), up = (double)plan->info[TILESPMV_INFO_UPLOAD_US];
         char buf[96];
         snprintf(buf, sizeof(buf), " %s %.1f (+%.1f upload)", name, (t - t_prev - (up - up_prev)) * 1e-3, (up - up_prev) * 1e-3);
@@ -1255,6 +1240,6 @@ int tilespmv::build_stream(tilespmv_plan *plan, const Knobs &K, const Tile_matri
     if (B.rc == -2 || B.rc == -3) return B.rc;   // (shard too large for 32-bit unit ids)
     B.entries(); lap("entries");
     B.finish(n_tasks, model_bytes); lap("finish");
-    if (verbose) fprintf(stderr, "tilespmv: unit-stream layout, ms per stage:%s\n", times.c_str());
+    if (K.verbose) fprintf(stderr, "tilespmv: unit-stream layout, ms per stage:%s\n", times.c_str());
     return B.rc;
 }
