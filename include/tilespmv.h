@@ -568,6 +568,52 @@ int tilespmv_csr_transpose(int rowA, int colA, const MAT_PTR_TYPE *csrRowPtr, co
                            MAT_PTR_TYPE *rowPtrT /* [colA + 1] */, int *colIdxT, MAT_VAL_TYPE *valT /* may be NULL */, int *srcT /* may be NULL */);
 int tilespmv_csr_transpose_device(int rowA, int colA, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal /* may be NULL */,
                                   MAT_PTR_TYPE *d_rowPtrT, int *d_colIdxT, MAT_VAL_TYPE *d_valT /* may be NULL */, int *d_srcT /* may be NULL */, void *stream);
+
+/* ---- A solver in the library: conjugate gradients around a resident plan (new; no reference counterpart: the reference multiplies once,
+ * src/main.cu:59-110).  A x = b for a symmetric positive definite A, optionally preconditioned by the inverse diagonal (Jacobi).  One iteration = the plan's product Ap = A p
+ * (tilespmv_plan_spmv, whatever launch form the plan has) and THREE streaming kernels: p.Ap;  x += alpha p, r -= alpha Ap with r.r (and r.z, z = dinv o r);  p = z + beta p.
+ * Every scalar (rho = r.z, p.Ap, alpha, beta, |r|^2, |b|^2, the iteration count, the breakdown flag) lives in device memory: a reducing kernel leaves one partial sum per workgroup
+ * and the kernel that consumes the scalar adds the partials itself, every workgroup in the same order.  The number of partials and the order of every addition are fixed by the
+ * number of rows alone, sums and scalars are double in both libraries (alpha, beta rounded to the value type once, where they multiply): on a plan whose y is bit-reproducible
+ * (TILESPMV_INFO_ENTRY_ORDERED = 1, e.g. deterministic = 1) the iterates x_k are too, run after run and plan after plan.
+ * Guards, taken on the device: rho = 0 (b = 0, or an exactly zero residual) -> alpha = beta = 0, further iterations leave x and r as they are — a captured graph of k iterations
+ * may overrun convergence; rho > 0 and not p.Ap > 0 (A is not positive definite on this Krylov space), or rho < 0 (dinv is not) -> the breakdown flag is set, alpha = beta = 0 in
+ * that and every later iteration, x keeps its last good value.
+ * A tilespmv_cg and its plan run on ONE stream at a time (the single-stream rule of tilespmv_plan_spmv, restated: the workspace is per solver, the split-row scratch per plan).
+ * d_b, d_x and d_dinv are DEVICE vectors of `rows` elements, 16-byte aligned (hipErrorInvalidValue otherwise); nothing behind element rows - 1 is read or written.
+ * Cost per iteration beside the product: 11 vector elements per row read or written (13 with Jacobi) in 3 launches; measured against a loop of torch operations (14 per row, about ten
+ * launches) in profiles/cg_fused_ab.txt.  Workspace: 3 vectors of rows + 16 elements and 33 KB.
+ *
+ *   tilespmv_cg_create      binds a workspace to `plan`, which must be square and whole (tilerow_begin = 0, tilerow_end = tilem; a transposed plan qualifies when square) and must
+ *                           outlive it.  d_dinv: NULL = plain CG; else the inverse diagonal, borrowed until destroy — its VALUES may change between solves (a value map:
+ *                           tilespmv_plan_update_values, then tilespmv_csr_diagonal_device into the same array).  Allocates r, p, Ap (rows + 16 elements each: every y of this project
+ *                           has room behind it), the partial-sum arrays and the scalar block in one hipMalloc (synchronises).  Returns 0, hipErrorInvalidValue (NULL / non-square /
+ *                           shard plan / misaligned d_dinv: nothing allocated, and for a NULL argument no HIP call made), or the hipMalloc error.
+ *   tilespmv_cg_begin       r = b - A x (x is the caller's start vector; pass zeros for none), p = z, rho = r.z, |r|^2, |b|^2; iteration count and breakdown flag cleared.
+ *   tilespmv_cg_iterate     `count` iterations back to back.  Like begin: asynchronous on `stream`, no allocation, no synchronisation, no host read — safe to capture into a hipGraph
+ *                           (one linear chain of kernels).  It does not stop at any tolerance: only an exactly zero rho ends the changes to x.
+ *   tilespmv_cg_state_read  synchronises `stream` and reads the scalar block (set out->size = sizeof(tilespmv_cg_state) first).  status: BREAKDOWN, CONVERGED when |r|^2 is exactly 0,
+ *                           else RUNNING — a tolerance is the caller's (or tilespmv_cg_solve's) to apply to rr / bb.  rr is the recurrence's |r|^2, not a recomputed |b - A x|^2.
+ *   tilespmv_cg_solve       begin, then iterate(check_every) + state_read until sqrt(rr / bb) <= rtol (CONVERGED), `maxiter` iterations are done (MAXITER; the last block is cut so that
+ *                           no more run) or a breakdown (BREAKDOWN).  One host synchronisation per check.  bb = 0 -> x = 0, CONVERGED, 0 iterations.
+ * All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_cg tilespmv_cg;
+typedef struct { unsigned size; int iterations; int status; double rr; double bb; } tilespmv_cg_state;
+#define TILESPMV_CG_RUNNING 0
+#define TILESPMV_CG_CONVERGED 1
+#define TILESPMV_CG_MAXITER 2
+#define TILESPMV_CG_BREAKDOWN 3
+int tilespmv_cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv /* may be NULL */);
+void tilespmv_cg_destroy(tilespmv_cg *cg);
+int tilespmv_cg_begin(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream);
+int tilespmv_cg_iterate(tilespmv_cg *cg, MAT_VAL_TYPE *d_x, int count, void *stream);
+int tilespmv_cg_state_read(tilespmv_cg *cg, void *stream, tilespmv_cg_state *out);
+int tilespmv_cg_solve(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream, tilespmv_cg_state *out);
+/* d_out[i] = the sum of the stored entries (i, i) of a device CSR, i < rows (duplicates added in storage order, in double; 0 where none is stored); invert != 0: 1 / that, and 1 where
+ * it is 0 — the d_dinv of tilespmv_cg_create.  rows <= the CSR's column count; the row pointer is used as it stands (positions of the arrays passed).  One thread per row,
+ * asynchronous on `stream`, capturable.  Returns a hipError_t value (hipErrorInvalidValue for a NULL array, hipErrorNoDevice without a device). */
+int tilespmv_csr_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, MAT_VAL_TYPE *d_out, int invert, void *stream);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

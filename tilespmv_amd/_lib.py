@@ -49,6 +49,15 @@ class PlanOptions(C.Structure):
             setattr(self, k, int(v))
 
 
+class CGState(C.Structure):
+    """Mirror of the versioned tilespmv_cg_state (``size`` first)."""
+    _fields_ = [("size", C.c_uint), ("iterations", C.c_int), ("status", C.c_int), ("rr", C.c_double), ("bb", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.size = C.sizeof(CGState)
+
+
 def lib_path(dtype):
     suf = "f64" if np.dtype(dtype) == np.float64 else "f32"
     # TILESPMV_LIB_VARIANT: a library with a suffix, e.g. an earlier commit's built by scripts/ab_prev.sh as lib*_old.so (A/B in one process; never the product)
@@ -158,6 +167,20 @@ def load(dtype=np.float64):
     lib.tilespmv_csr_transpose.restype = C.c_int
     lib.tilespmv_csr_transpose_device.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tilespmv_csr_transpose_device.restype = C.c_int
+    lib.tilespmv_cg_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.tilespmv_cg_create.restype = C.c_int
+    lib.tilespmv_cg_destroy.argtypes = [C.c_void_p]
+    lib.tilespmv_cg_destroy.restype = None
+    lib.tilespmv_cg_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_cg_begin.restype = C.c_int
+    lib.tilespmv_cg_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_cg_iterate.restype = C.c_int
+    lib.tilespmv_cg_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
+    lib.tilespmv_cg_state_read.restype = C.c_int
+    lib.tilespmv_cg_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
+    lib.tilespmv_cg_solve.restype = C.c_int
+    lib.tilespmv_csr_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_csr_diagonal_device.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -180,4 +203,6 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_plan_time_reference_style", "tilespmv_plan_reserve_spmm", "tilespmv_plan_options_layout", "tilespmv_plan_layout_stages",
                     "Tile_create_device", "tilespmv_plan_create_from_csr", "tilespmv_plan_stream_digests", "tilespmv_plan_create_from_device_csr",
                     "tilespmv_reorder_rcm", "tilespmv_csr_permute", "tilespmv_csr_bandwidth", "tilespmv_permute_vector",
-                    "tilespmv_plan_update_values", "tilespmv_csr_transpose", "tilespmv_csr_transpose_device"]
+                    "tilespmv_plan_update_values", "tilespmv_csr_transpose", "tilespmv_csr_transpose_device",
+                    "tilespmv_cg_create", "tilespmv_cg_destroy", "tilespmv_cg_begin", "tilespmv_cg_iterate", "tilespmv_cg_state_read", "tilespmv_cg_solve",
+                    "tilespmv_csr_diagonal_device"]

@@ -427,6 +427,84 @@ class Plan:
             pass
 
 
+CG_RUNNING, CG_CONVERGED, CG_MAXITER, CG_BREAKDOWN = 0, 1, 2, 3
+CG_STATUS_NAMES = ["running", "converged", "maxiter", "breakdown"]
+HIP_ERROR_INVALID_VALUE = 1
+
+
+def csr_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dtype=np.float64):
+    """``tilespmv_csr_diagonal_device``: ``d_out[i]`` = the sum of the stored entries (i, i) of a device CSR (addresses, as ``Plan.from_device_csr`` takes them); ``invert=True``: its
+    inverse, 1 where it is 0 — the ``d_dinv`` of ``CG``.  Asynchronous on ``stream``."""
+    lib = _lib.load(dtype)
+    rc = lib.tilespmv_csr_diagonal_device(rows, C.c_void_p(d_rp), C.c_void_p(d_ci), C.c_void_p(d_v), C.c_void_p(d_out), 1 if invert else 0, C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("tilespmv_csr_diagonal_device failed (hipError %d): bad argument, or no usable device" % rc)
+
+
+class CG:
+    """``tilespmv_cg``: conjugate gradients around a resident plan, every scalar on the device (include/tilespmv.h).
+
+    ``plan``: square and whole; it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal (Jacobi; borrowed), or None for plain CG.  ``b`` / ``x``
+    are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library returns
+    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+
+    def __init__(self, plan, d_dinv=None):
+        self.lib, self.plan = plan.lib, plan
+        h = C.c_void_p()
+        rc = self.lib.tilespmv_cg_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None))
+        self._check(rc, "tilespmv_cg_create")
+        self.h = h
+
+    @staticmethod
+    def _check(rc, what):
+        if rc == HIP_ERROR_INVALID_VALUE:
+            raise ValueError("%s: hipErrorInvalidValue (the plan must be square and whole; vectors 16-byte aligned)" % what)
+        if rc != 0:
+            raise RuntimeError("%s: HIP error %d" % (what, rc))
+
+    @staticmethod
+    def _state(st):
+        rel = (st.rr / st.bb) ** 0.5 if st.bb > 0 else 0.0
+        return {"iterations": st.iterations, "status": st.status, "status_name": CG_STATUS_NAMES[st.status], "rr": st.rr, "bb": st.bb, "relative_residual": rel}
+
+    def begin(self, d_b, d_x, stream=0):
+        """r = b - A x, p = z; asynchronous."""
+        self._check(self.lib.tilespmv_cg_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)), "tilespmv_cg_begin")
+
+    def iterate(self, d_x, count=1, stream=0):
+        """``count`` iterations; asynchronous, capturable into a graph."""
+        self._check(self.lib.tilespmv_cg_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_cg_iterate")
+
+    def state(self, stream=0):
+        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
+        st = _lib.CGState()
+        self._check(self.lib.tilespmv_cg_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_cg_state_read")
+        return self._state(st)
+
+    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
+        """``tilespmv_cg_solve``; returns the final state (as ``state``)."""
+        st = _lib.CGState()
+        self._check(self.lib.tilespmv_cg_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)), "tilespmv_cg_solve")
+        return self._state(st)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tilespmv_cg_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def algorithmic_bytes(nnz, rows, cols, itemsize):
     """B_alg = nnz*(s_v+4) + 4*(m+1) + s_v*(n+m)."""
     return nnz * (itemsize + 4) + 4 * (rows + 1) + itemsize * (cols + rows)

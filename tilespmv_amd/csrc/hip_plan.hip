@@ -782,6 +782,7 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
     D.nfix = (int)fix.size();
     D.rowA = std::min<long long>(rowA, (long long)tr1 * 16); D.colA = colA;
     D.f_row0 = row0; D.f_rows = rows;
+    plan->matrix_rows = rowA;
 
     long long *I = plan->info;
     I[TILESPMV_INFO_NNZ] = span(T->tile_nnz, DT ? DT->T.tile_nnz : nullptr, t_begin, t_end);

@@ -155,6 +155,7 @@ struct tilespmv_plan {
     unsigned long long stage_digest[TILESPMV_STAGE_COUNT] = {0};   // layout-digest builds: one hash per stage of the unit-stream builder (hip_plan_stream.hip)
     std::vector<size_t> uploaded_bytes;          // ... and the bytes of each (tilespmv_plan_stream_digests)
     std::vector<const void **> uploaded_slots;   // every device-pointer MEMBER of this plan that upload() filled: what a re-placement rebases (hip_plan.hip retry_placement)
+    int matrix_rows = 0;                // rows of the WHOLE matrix this plan is a plan (or a shard) of: hip_solver.hip refuses shards and non-square plans by it
     // arena space for n elements that a device kernel will fill (zeroed like every block); same bookkeeping as upload()
     template <class T>
     int reserve(size_t n, const T **out) { return upload<T>(nullptr, n, out); }

@@ -5,6 +5,7 @@
     z = op.rmatvec(u)                                                # A^T u    (plan of A^T, built on the device from A's CSR: TILESPMV_CREATE_TRANSPOSE)
     op = SparseOperator(..., value_map=True); op.update_values(v2)   # new values of the same pattern: both plans refreshed from A's one value array
     x, info = cgls(op, b)                                            # least squares  min ||A x - b||
+    x, info = op.cg(b)                                               # A x = b, A symmetric positive definite: the solver in the library
 
 The plan of A^T is a plan like any other (tuned kernels, form choice, ordered sums); there is no scatter form of A^T x.
 """
@@ -142,6 +143,33 @@ class SparseOperator:
             st = stream or 0
         self.A.update_values(d_vals, st)
         self.AT.update_values(d_vals, st)
+
+    def cg(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None):
+        """A x = b by conjugate gradients in the library (``api.CG`` over the plan of A: symmetric positive definite A) — the product and three fused kernels per
+        iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: the inverse
+        diagonal as a CUDA vector (Jacobi; ``api.csr_diagonal_device(..., invert=True)`` makes it), None = plain CG.  Stops at ``sqrt(rr / bb) <= rtol`` or after ``maxiter``
+        iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}``."""
+        import torch
+        rows, cols = self.shape
+        if rows != cols:
+            raise ValueError("cg needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
+        if b.dim() != 1 or b.numel() != rows or not b.is_contiguous():
+            raise ValueError("b must be a contiguous vector of %d elements" % rows)
+        if dinv is not None and (dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
+            raise ValueError("dinv must be a contiguous vector of %d elements of b's type" % rows)
+        maxiter = 2 * rows if maxiter is None else maxiter
+        x = torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+        if x0 is not None:
+            x.copy_(x0)
+        st = _stream(stream)
+        solver = api.CG(self.A, None if dinv is None else dinv.data_ptr())
+        try:
+            s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
+        finally:
+            solver.close()
+        info = {"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
+                "status": s["status_name"]}
+        return x, info
 
     def close(self):
         for p in (getattr(self, "A", None), getattr(self, "AT", None)):
