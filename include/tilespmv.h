@@ -614,6 +614,44 @@ int tilespmv_cg_solve(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_
  * asynchronous on `stream`, capturable.  Returns a hipError_t value (hipErrorInvalidValue for a NULL array, hipErrorNoDevice without a device). */
 int tilespmv_csr_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, MAT_VAL_TYPE *d_out, int invert, void *stream);
 
+/* ---- Several right-hand sides at once: conjugate gradients on nvec systems A x_j = b_j in lock-step around tilespmv_plan_spmm (new).  The
+ * matrix is streamed ONCE per iteration for all nvec systems.  This is plain CG per column — one rho, p.Ap, alpha, beta, |r|^2, |b|^2, iteration count and breakdown flag per
+ * column — not block CG: no Gram matrices, no rank-deficiency breakdowns.  Per column the meaning is that of tilespmv_cg_*, word for word: the same recurrences, sums and scalars
+ * in double, alpha and beta rounded to the value type once, the same guards taken on the device (rho = 0 -> alpha = beta = 0; rho < 0, or rho > 0 without p.Ap > 0 -> that column's
+ * breakdown flag, the column keeps its last good x).  A column in breakdown or at rho = 0 does not disturb the others.
+ * d_B and d_X are DEVICE arrays, row-major [rows][nvec] (the nvec values of one row are contiguous: the layout of tilespmv_plan_spmm) and 16-byte aligned; nvec in {1, 2, 4, 8};
+ * d_dinv (may be NULL) has `rows` elements and is shared by all columns.  Nothing behind element rows * nvec - 1 of d_B / d_X or rows - 1 of d_dinv is read or written.
+ * One iteration = the multi-vector product and THREE streaming kernels over the flat arrays: 11 * rows * nvec vector elements read or written beside the product (+ 2 * rows with
+ * Jacobi).  One partial sum per workgroup and column; the consuming kernel folds them itself, every workgroup in the same order.  The number of partials and the order of every
+ * addition are fixed by (rows, nvec) alone: on a plan whose tilespmv_plan_spmm is bit-reproducible the iterates are too, and a column's iterates do not depend on what the other
+ * columns hold.  Workspace: r, p, Ap of (rows + 16) * nvec elements each, the partial sums and one scalar block per column, in one hipMalloc.  Measured against nvec successive
+ * tilespmv_cg solves on the same plan in profiles/cg_multi_ab.txt (1.1 x to 2.2 x per system-iteration at nvec 8).
+ *
+ *   tilespmv_cg_multi_create      as tilespmv_cg_create (square, whole plan that outlives the solver; d_dinv borrowed), for nvec right-hand sides.  Also calls
+ *                                 tilespmv_plan_reserve_spmm(plan, nvec), so that plans without a native multi-vector kernel never allocate inside iterate.  Returns 0,
+ *                                 hipErrorInvalidValue (NULL argument or nvec outside {1, 2, 4, 8}: no HIP call made, the plan not touched; non-square / shard plan, misaligned
+ *                                 d_dinv: nothing allocated), or the allocation's error.
+ *   tilespmv_cg_multi_begin       R = B - A X, P = Z, the scalars of every column; iteration counts, breakdown and freeze flags cleared.
+ *   tilespmv_cg_multi_iterate     `count` iterations of all columns back to back.  Like begin: asynchronous on `stream`, no allocation, no synchronisation, no host read, one linear
+ *                                 chain of kernels — safe to capture into a hipGraph, for every kind of plan.  It stops at no tolerance.
+ *   tilespmv_cg_multi_state_read  synchronises `stream` and fills out[0 .. nvec - 1]; set out[0].size first: it is the distance in bytes between the elements of `out`, and the size
+ *                                 of each (tilespmv_cg_state_read's rule).  status per column: BREAKDOWN, CONVERGED when |r|^2 is exactly 0, else RUNNING.
+ *   tilespmv_cg_multi_solve       begin, then iterate(check_every) + state_read.  A column seen at rr <= rtol^2 bb (CONVERGED), in breakdown (BREAKDOWN) or with bb = 0 (x_j = 0,
+ *                                 CONVERGED, 0 iterations) is FROZEN: a flag on the device, set by a one-workgroup kernel, makes alpha = beta = 0 for it and stops its iteration
+ *                                 count; its x and r do not change by a bit from then on, so relative residual <= rtol holds for every CONVERGED column at return although CG's
+ *                                 residual norm is not monotone.  Frozen columns STILL RIDE THROUGH THE PRODUCT: an iteration costs the same until the last column is done.  Ends
+ *                                 when every column is final or the running columns have done `maxiter` iterations (those: MAXITER; the last block is cut so that no more run).
+ *                                 out[j].iterations is the count at which column j was frozen.  One host synchronisation per check.
+ * nvec = 1 is served by tilespmv_cg_* itself: bit-identical x and state.  All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_cg_multi tilespmv_cg_multi;
+int tilespmv_cg_multi_create(tilespmv_cg_multi **cg, tilespmv_plan *plan, int nvec, const MAT_VAL_TYPE *d_dinv /* may be NULL; rows elements, shared by all columns */);
+void tilespmv_cg_multi_destroy(tilespmv_cg_multi *cg);
+int tilespmv_cg_multi_begin(tilespmv_cg_multi *cg, const MAT_VAL_TYPE *d_B, MAT_VAL_TYPE *d_X, void *stream);
+int tilespmv_cg_multi_iterate(tilespmv_cg_multi *cg, MAT_VAL_TYPE *d_X, int count, void *stream);
+int tilespmv_cg_multi_state_read(tilespmv_cg_multi *cg, void *stream, tilespmv_cg_state *out /* [nvec]; out[0].size set, it is the stride */);
+int tilespmv_cg_multi_solve(tilespmv_cg_multi *cg, const MAT_VAL_TYPE *d_B, MAT_VAL_TYPE *d_X, double rtol, int maxiter, int check_every, void *stream,
+                            tilespmv_cg_state *out /* [nvec] */);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

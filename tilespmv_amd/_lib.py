@@ -179,6 +179,18 @@ def load(dtype=np.float64):
     lib.tilespmv_cg_state_read.restype = C.c_int
     lib.tilespmv_cg_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
     lib.tilespmv_cg_solve.restype = C.c_int
+    lib.tilespmv_cg_multi_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_cg_multi_create.restype = C.c_int
+    lib.tilespmv_cg_multi_destroy.argtypes = [C.c_void_p]
+    lib.tilespmv_cg_multi_destroy.restype = None
+    lib.tilespmv_cg_multi_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_cg_multi_begin.restype = C.c_int
+    lib.tilespmv_cg_multi_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_cg_multi_iterate.restype = C.c_int
+    lib.tilespmv_cg_multi_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
+    lib.tilespmv_cg_multi_state_read.restype = C.c_int
+    lib.tilespmv_cg_multi_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
+    lib.tilespmv_cg_multi_solve.restype = C.c_int
     lib.tilespmv_csr_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_csr_diagonal_device.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
@@ -205,4 +217,6 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_reorder_rcm", "tilespmv_csr_permute", "tilespmv_csr_bandwidth", "tilespmv_permute_vector",
                     "tilespmv_plan_update_values", "tilespmv_csr_transpose", "tilespmv_csr_transpose_device",
                     "tilespmv_cg_create", "tilespmv_cg_destroy", "tilespmv_cg_begin", "tilespmv_cg_iterate", "tilespmv_cg_state_read", "tilespmv_cg_solve",
-                    "tilespmv_csr_diagonal_device"]
+                    "tilespmv_csr_diagonal_device",
+                    "tilespmv_cg_multi_create", "tilespmv_cg_multi_destroy", "tilespmv_cg_multi_begin", "tilespmv_cg_multi_iterate", "tilespmv_cg_multi_state_read",
+                    "tilespmv_cg_multi_solve"]

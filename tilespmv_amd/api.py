@@ -505,6 +505,71 @@ class CG:
             pass
 
 
+class CGMulti:
+    """``tilespmv_cg_multi``: conjugate gradients on ``nvec`` systems in lock-step around the multi-vector product, one set of device scalars per column (include/tilespmv.h,
+    DESIGN.md §3.8).
+
+    ``plan``: square and whole; it must stay open while the solver is.  ``nvec``: 1, 2, 4 or 8.  ``d_dinv``: device ADDRESS of the inverse diagonal (``rows`` elements, shared by
+    the columns; borrowed), or None.  ``B`` / ``X`` are device addresses of row-major ``(rows, nvec)`` arrays, 16-byte aligned.  ``state`` and ``solve`` return a list of ``nvec``
+    dicts in the shape of ``CG.state``.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (another nvec, a shard, a non-square plan, a misaligned array)."""
+
+    def __init__(self, plan, nvec, d_dinv=None):
+        self.lib, self.plan, self.nvec = plan.lib, plan, int(nvec)
+        h = C.c_void_p()
+        rc = self.lib.tilespmv_cg_multi_create(C.byref(h), plan.h, self.nvec, C.c_void_p(d_dinv or None))
+        self._check(rc, "tilespmv_cg_multi_create")
+        self.h = h
+
+    @staticmethod
+    def _check(rc, what):
+        if rc == HIP_ERROR_INVALID_VALUE:
+            raise ValueError("%s: hipErrorInvalidValue (nvec in {1, 2, 4, 8}; the plan must be square and whole; arrays 16-byte aligned)" % what)
+        if rc != 0:
+            raise RuntimeError("%s: HIP error %d" % (what, rc))
+
+    def _states(self):
+        arr = (_lib.CGState * self.nvec)()
+        arr[0].size = C.sizeof(_lib.CGState)
+        return arr
+
+    def begin(self, d_B, d_X, stream=0):
+        """R = B - A X, P = Z; asynchronous."""
+        self._check(self.lib.tilespmv_cg_multi_begin(self.h, C.c_void_p(d_B), C.c_void_p(d_X), C.c_void_p(stream)), "tilespmv_cg_multi_begin")
+
+    def iterate(self, d_X, count=1, stream=0):
+        """``count`` iterations of every column; asynchronous, capturable into a graph."""
+        self._check(self.lib.tilespmv_cg_multi_iterate(self.h, C.c_void_p(d_X), count, C.c_void_p(stream)), "tilespmv_cg_multi_iterate")
+
+    def state(self, stream=0):
+        """Synchronises ``stream``; one dict per column."""
+        arr = self._states()
+        self._check(self.lib.tilespmv_cg_multi_state_read(self.h, C.c_void_p(stream), arr), "tilespmv_cg_multi_state_read")
+        return [CG._state(st) for st in arr]
+
+    def solve(self, d_B, d_X, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
+        """``tilespmv_cg_multi_solve``; returns the final state of every column."""
+        arr = self._states()
+        self._check(self.lib.tilespmv_cg_multi_solve(self.h, C.c_void_p(d_B), C.c_void_p(d_X), rtol, maxiter, check_every, C.c_void_p(stream), arr), "tilespmv_cg_multi_solve")
+        return [CG._state(st) for st in arr]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tilespmv_cg_multi_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def algorithmic_bytes(nnz, rows, cols, itemsize):
     """B_alg = nnz*(s_v+4) + 4*(m+1) + s_v*(n+m)."""
     return nnz * (itemsize + 4) + 4 * (rows + 1) + itemsize * (cols + rows)

@@ -1,0 +1,568 @@
+// hip_solver_mv.hip — conjugate gradients on nvec systems in lock-step around the multi-vector product (tilespmv_cg_multi_*).
+//
+// The recurrences, sums, guards and ownership rules are those of hip_solver.hip, once per COLUMN: B, X, r, p, Ap are row-major [rows][NVEC] (the layout of tilespmv_plan_spmm),
+// so the matrix is streamed once per iteration for all NVEC systems.  One iteration is that product and three streaming kernels, templated on NVEC in {2, 4, 8}:
+//   k_cgm_dot        reads p, Ap                     partial sums of p.Ap, one per workgroup and column
+//   k_cgm_update     reads p, Ap, x, r (, dinv)      alpha_c = rho_c / (p.Ap)_c;  x += alpha p;  r -= alpha Ap;  partial sums of r.r and (Jacobi) r.z per column
+//   k_cgm_direction  reads r, p (, dinv)             beta_c = rho_new_c / rho_c;  p = z + beta p
+// 11 rows NVEC vector elements per iteration (+ 2 rows of dinv with Jacobi: dinv is shared by the columns and read once per lane vector).
+//
+// The vectors are walked as flat streams of n = rows * NVEC elements in 16-byte lane vectors, exactly as hip_solver.hip walks its vectors; flat element e belongs to column
+// e % NVEC.  A workgroup's trip stride (CG_U * CGB lane vectors), CGB and 64 are multiples of the lane vectors per row (LPR = NVEC / CG_VPL when NVEC >= CG_VPL), so a thread meets
+// the same columns in every trip: (threadIdx.x % LPR) * CG_VPL + q for element q of its lane vectors.  In fp32 with NVEC = 2 a lane vector holds two rows and element q is column
+// q % 2.  Either way a thread keeps KC = min(CG_VPL, NVEC) accumulators and as many alpha / beta, all indexed at compile time.
+// Sums per column: the wave tree runs over the shuffle offsets 32 .. LPR (lanes LPR apart hold the same columns), the four wave sums are added in wave order through LDS, one
+// partial per workgroup and column is written ([workgroup][NVEC]).  The consuming kernel folds the np * NVEC partials itself: thread t adds flat partials t, t + CGB, ... (all of
+// column t % NVEC), the wave tree stops at offset NVEC, the four wave sums are added in wave order.  Every workgroup does the same additions in the same order; the number of
+// partials (cgm_parts) and every addition order are functions of (rows, NVEC) alone.  No atomics, no finishing launch, no occupancy query.
+//
+// The scalar block is one CgmScal per column; the fields of hip_solver.hip's CgScal keep their one writing kernel each (k_cgm_dot: rho; k_cgm_update: breakdown; k_cgm_direction:
+// rr, iterations; k_cgm_begin_fold: all), and
+//   frozen      k_cgm_freeze (one workgroup, launched by tilespmv_cg_multi_solve between two blocks of iterations; set), k_cgm_begin_fold (cleared)     read by k_cgm_dot, k_cgm_direction
+// Under the flag k_cgm_dot hands out rho = 0 for the column, which is the rho = 0 guard: alpha = beta = 0, x and r keep their bits, and k_cgm_direction leaves its iteration count.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "hip_plan_internal.h"
+
+namespace tilespmv {
+namespace {
+
+// (the constants of hip_solver.hip, restated: that file stays as it is)
+constexpr int CGB = 256;                              // threads per workgroup
+constexpr int CG_VPL = 16 / (int)sizeof(val_t);       // elements per 16-byte lane load (2 in fp64, 4 in fp32)
+constexpr int CG_U = 2;                               // lane vectors per lane and trip
+constexpr int CG_MAX_PARTS = 1024;                    // partial sums per column = workgroups of the streaming kernels
+constexpr int MAX_NVEC = TILESPMV_MAX_NVEC;
+typedef val_t cvec_t __attribute__((ext_vector_type(CG_VPL)));
+
+struct CgmScal {
+    double rho, rr, bb;
+    int iterations, breakdown, frozen, pad;
+};
+
+template <int NVEC> struct Cols {
+    static constexpr int LPR = NVEC >= CG_VPL ? NVEC / CG_VPL : 1;   // lane vectors per row (1 when a lane vector holds whole rows)
+    static constexpr int KC = NVEC >= CG_VPL ? CG_VPL : NVEC;        // columns a thread meets
+    static constexpr int RPL = NVEC >= CG_VPL ? 1 : CG_VPL / NVEC;   // rows per lane vector
+    // the first of this thread's KC consecutive columns
+    static __device__ __forceinline__ int first() { return NVEC >= CG_VPL ? ((int)threadIdx.x % LPR) * CG_VPL : 0; }
+};
+
+// workgroups (= partial sums per column) for rows x nvec: a function of the two alone
+inline int cgm_parts(long long rows, int nvec)
+{
+    const long long trips = (rows * nvec / CG_VPL + (long long)CG_U * CGB - 1) / ((long long)CG_U * CGB);
+    return (int)std::max<long long>(1, std::min<long long>(CG_MAX_PARTS, trips));
+}
+
+// The workgroup's sums of the per-thread accumulators, by column: left in s[wave * NVEC + column], four values per column (col_total adds them).
+template <int NVEC> __device__ __forceinline__ void block_cols(const double (&acc)[Cols<NVEC>::KC], double *s)
+{
+    constexpr int LPR = Cols<NVEC>::LPR, KC = Cols<NVEC>::KC;
+    double w[KC];
+#pragma unroll
+    for (int k = 0; k < KC; k++) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = 32; o >= LPR; o >>= 1) v += __shfl_down(v, o, 64);
+        w[k] = v;
+    }
+    __syncthreads();   // (s may still be read from an earlier reduction)
+    const int lane = threadIdx.x & 63;
+    if (lane < LPR) {
+#pragma unroll
+        for (int k = 0; k < KC; k++) s[(threadIdx.x >> 6) * NVEC + lane * KC + k] = w[k];
+    }
+    __syncthreads();
+}
+// The sums of np partials per column ([np][nvec]), the same additions in every workgroup: left in s as by block_cols.
+__device__ __forceinline__ void fold_cols(const double *__restrict__ part, int np, int nvec, double *s)
+{
+    double a = 0.0;
+    for (int i = threadIdx.x; i < np * nvec; i += CGB) a += part[i];
+    for (int o = 32; o >= nvec; o >>= 1) a += __shfl_down(a, o, 64);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    if (lane < nvec) s[(threadIdx.x >> 6) * nvec + lane] = a;
+    __syncthreads();
+}
+__device__ __forceinline__ double col_total(const double *s, int nvec, int c)
+{
+    return ((s[c] + s[nvec + c]) + s[2 * nvec + c]) + s[3 * nvec + c];
+}
+// one partial per workgroup and column
+template <int NVEC> __device__ __forceinline__ void write_partials(const double *s, double *__restrict__ part)
+{
+    if (threadIdx.x < NVEC) part[(long long)blockIdx.x * NVEC + threadIdx.x] = col_total(s, NVEC, threadIdx.x);
+}
+
+// dinv of the rows of lane vector v, element for element: one scalar load when the lane vector lies within a row, an 8-byte pair in fp32 with NVEC = 2
+template <int NVEC> __device__ __forceinline__ cvec_t load_dinv(const val_t *__restrict__ dinv, long long v)
+{
+    cvec_t d;
+    if constexpr (Cols<NVEC>::RPL == 1) {
+        d = dinv[v / Cols<NVEC>::LPR];
+    } else {
+        typedef val_t pair_t __attribute__((ext_vector_type(Cols<NVEC>::RPL)));
+        const pair_t t = reinterpret_cast<const pair_t *>(dinv)[v];
+#pragma unroll
+        for (int q = 0; q < CG_VPL; q++) d[q] = t[q / NVEC];
+    }
+    return d;
+}
+
+// Element ranges as in hip_solver.hip: full lane vectors [0, nv) in trips of CG_U * CGB; the n % CG_VPL elements behind them (fp32, NVEC = 2, odd rows: one row) belong to
+// thread 0 of workgroup 0, whose columns start at 0 (scalar accesses: nothing past element n - 1 of a caller's array is touched).
+#define CGM_FOR_TRIPS(base) for (long long base = (long long)blockIdx.x * (CG_U * CGB) + threadIdx.x; base < nv; base += (long long)gridDim.x * (CG_U * CGB))
+
+template <int NVEC>
+__global__ __launch_bounds__(CGB) void k_cgm_dot(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, double *__restrict__ ppap, const double *__restrict__ prz,
+                                                 int np, CgmScal *__restrict__ S)
+{
+    constexpr int KC = Cols<NVEC>::KC;
+    __shared__ double s[(CGB / 64) * NVEC];
+    const long long nv = n / CG_VPL;
+    double acc[KC];
+#pragma unroll
+    for (int k = 0; k < KC; k++) acc[k] = 0.0;
+    CGM_FOR_TRIPS(base) {
+        cvec_t a[CG_U], b[CG_U];
+#pragma unroll
+        for (int u = 0; u < CG_U; u++) {
+            const long long v = base + u * CGB;
+            if (v < nv) { a[u] = reinterpret_cast<const cvec_t *>(p)[v]; b[u] = reinterpret_cast<const cvec_t *>(Ap)[v]; }
+            else { a[u] = (val_t)0; b[u] = (val_t)0; }
+        }
+#pragma unroll
+        for (int u = 0; u < CG_U; u++)
+#pragma unroll
+            for (int q = 0; q < CG_VPL; q++) acc[q % KC] += (double)a[u][q] * (double)b[u][q];
+    }
+    if constexpr (NVEC < CG_VPL) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < KC; k++) {
+                const long long i = nv * CG_VPL + k;
+                if (i < n) acc[k] += (double)p[i] * (double)Ap[i];
+            }
+        }
+    }
+    block_cols<NVEC>(acc, s);
+    write_partials<NVEC>(s, ppap);
+    if (blockIdx.x == 0) {   // rho of this iteration, for the two kernels that follow
+        fold_cols(prz, np, NVEC, s);
+        if (threadIdx.x < NVEC) S[threadIdx.x].rho = (S[threadIdx.x].breakdown || S[threadIdx.x].frozen) ? 0.0 : col_total(s, NVEC, threadIdx.x);
+    }
+}
+
+template <int NVEC>
+__global__ __launch_bounds__(CGB) void k_cgm_update(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, val_t *__restrict__ x, val_t *__restrict__ r,
+                                                    const val_t *__restrict__ dinv, const double *__restrict__ ppap, double *__restrict__ prr, double *__restrict__ prz, int np,
+                                                    CgmScal *__restrict__ S)
+{
+    constexpr int KC = Cols<NVEC>::KC, LPR = Cols<NVEC>::LPR;
+    __shared__ double s[(CGB / 64) * NVEC];
+    const int c0 = Cols<NVEC>::first();
+    fold_cols(ppap, np, NVEC, s);
+    val_t alpha[KC];
+#pragma unroll
+    for (int k = 0; k < KC; k++) {
+        const double pap = col_total(s, NVEC, c0 + k), rho = S[c0 + k].rho;
+        const bool broke = rho < 0.0 || (rho > 0.0 && !(pap > 0.0));
+        alpha[k] = (val_t)((rho > 0.0 && pap > 0.0) ? rho / pap : 0.0);
+        if (broke && blockIdx.x == 0 && threadIdx.x < LPR) S[c0 + k].breakdown = 1;   // (threads 0 .. LPR - 1 hold each column once)
+    }
+    cvec_t av;
+#pragma unroll
+    for (int q = 0; q < CG_VPL; q++) av[q] = alpha[q % KC];
+    const long long nv = n / CG_VPL;
+    double arr[KC], arz[KC];
+#pragma unroll
+    for (int k = 0; k < KC; k++) { arr[k] = 0.0; arz[k] = 0.0; }
+    CGM_FOR_TRIPS(base) {
+        cvec_t vp[CG_U], va[CG_U], vx[CG_U], vr[CG_U], vd[CG_U];
+#pragma unroll
+        for (int u = 0; u < CG_U; u++) {
+            const long long v = base + u * CGB;
+            if (v < nv) {
+                vp[u] = reinterpret_cast<const cvec_t *>(p)[v]; va[u] = reinterpret_cast<const cvec_t *>(Ap)[v];
+                vx[u] = reinterpret_cast<const cvec_t *>(x)[v]; vr[u] = reinterpret_cast<const cvec_t *>(r)[v];
+                if (dinv) vd[u] = load_dinv<NVEC>(dinv, v);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CG_U; u++) {
+            const long long v = base + u * CGB;
+            if (v < nv) {
+                const cvec_t nx = vx[u] + av * vp[u], nr = vr[u] - av * va[u];
+                reinterpret_cast<cvec_t *>(x)[v] = nx;
+                reinterpret_cast<cvec_t *>(r)[v] = nr;
+#pragma unroll
+                for (int q = 0; q < CG_VPL; q++) {
+                    arr[q % KC] += (double)nr[q] * (double)nr[q];
+                    if (dinv) arz[q % KC] += (double)nr[q] * (double)(val_t)(vd[u][q] * nr[q]);
+                }
+            }
+        }
+    }
+    if constexpr (NVEC < CG_VPL) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < KC; k++) {
+                const long long i = nv * CG_VPL + k;
+                if (i < n) {
+                    const val_t nr = r[i] - alpha[k] * Ap[i];
+                    x[i] = x[i] + alpha[k] * p[i];
+                    r[i] = nr;
+                    arr[k] += (double)nr * (double)nr;
+                    if (dinv) arz[k] += (double)nr * (double)(val_t)(dinv[i / NVEC] * nr);
+                }
+            }
+        }
+    }
+    block_cols<NVEC>(arr, s);
+    write_partials<NVEC>(s, prr);
+    if (dinv) {   // (plain CG: r.z is r.r, and prz is prr)
+        block_cols<NVEC>(arz, s);
+        write_partials<NVEC>(s, prz);
+    }
+}
+
+template <int NVEC>
+__global__ __launch_bounds__(CGB) void k_cgm_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ dinv,
+                                                       const double *__restrict__ prr, const double *__restrict__ prz, int np, CgmScal *__restrict__ S)
+{
+    constexpr int KC = Cols<NVEC>::KC;
+    __shared__ double s[(CGB / 64) * NVEC];
+    const int c0 = Cols<NVEC>::first();
+    fold_cols(prz, np, NVEC, s);
+    val_t beta[KC];
+#pragma unroll
+    for (int k = 0; k < KC; k++) {
+        const double rho_new = col_total(s, NVEC, c0 + k), rho = S[c0 + k].rho;
+        beta[k] = (val_t)((rho > 0.0 && !S[c0 + k].breakdown) ? rho_new / rho : 0.0);
+    }
+    if (blockIdx.x == 0) {   // what the host reads
+        if (dinv) fold_cols(prr, np, NVEC, s);
+        if (threadIdx.x < NVEC) {
+            S[threadIdx.x].rr = col_total(s, NVEC, threadIdx.x);
+            if (!S[threadIdx.x].frozen) S[threadIdx.x].iterations = S[threadIdx.x].iterations + 1;
+        }
+    }
+    cvec_t bv;
+#pragma unroll
+    for (int q = 0; q < CG_VPL; q++) bv[q] = beta[q % KC];
+    const long long nv = n / CG_VPL;
+    CGM_FOR_TRIPS(base) {
+        cvec_t vr[CG_U], vp[CG_U], vd[CG_U];
+#pragma unroll
+        for (int u = 0; u < CG_U; u++) {
+            const long long v = base + u * CGB;
+            if (v < nv) {
+                vr[u] = reinterpret_cast<const cvec_t *>(r)[v]; vp[u] = reinterpret_cast<const cvec_t *>(p)[v];
+                if (dinv) vd[u] = load_dinv<NVEC>(dinv, v);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CG_U; u++) {
+            const long long v = base + u * CGB;
+            if (v < nv) {
+                const cvec_t z = dinv ? vd[u] * vr[u] : vr[u];
+                reinterpret_cast<cvec_t *>(p)[v] = z + bv * vp[u];
+            }
+        }
+    }
+    if constexpr (NVEC < CG_VPL) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < KC; k++) {
+                const long long i = nv * CG_VPL + k;
+                if (i < n) p[i] = (dinv ? (val_t)(dinv[i / NVEC] * r[i]) : r[i]) + beta[k] * p[i];
+            }
+        }
+    }
+}
+
+// the start of a solve: r = B - A X (AX holds the product), p = z, partial sums of r.r, r.z and b.b per column
+template <int NVEC>
+__global__ __launch_bounds__(CGB) void k_cgm_begin(long long n, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, val_t *__restrict__ p,
+                                                   const val_t *__restrict__ dinv, double *__restrict__ prr, double *__restrict__ prz, double *__restrict__ pbb)
+{
+    constexpr int KC = Cols<NVEC>::KC;
+    __shared__ double s[(CGB / 64) * NVEC];
+    const long long nv = n / CG_VPL;
+    double arr[KC], arz[KC], abb[KC];
+#pragma unroll
+    for (int k = 0; k < KC; k++) { arr[k] = 0.0; arz[k] = 0.0; abb[k] = 0.0; }
+    CGM_FOR_TRIPS(base) {
+#pragma unroll
+        for (int u = 0; u < CG_U; u++) {
+            const long long v = base + u * CGB;
+            if (v < nv) {
+                const cvec_t vb = reinterpret_cast<const cvec_t *>(b)[v], nr = vb - reinterpret_cast<const cvec_t *>(Ax)[v];
+                const cvec_t z = dinv ? load_dinv<NVEC>(dinv, v) * nr : nr;
+                reinterpret_cast<cvec_t *>(r)[v] = nr;
+                reinterpret_cast<cvec_t *>(p)[v] = z;
+#pragma unroll
+                for (int q = 0; q < CG_VPL; q++) {
+                    arr[q % KC] += (double)nr[q] * (double)nr[q];
+                    arz[q % KC] += (double)nr[q] * (double)z[q];
+                    abb[q % KC] += (double)vb[q] * (double)vb[q];
+                }
+            }
+        }
+    }
+    if constexpr (NVEC < CG_VPL) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < KC; k++) {
+                const long long i = nv * CG_VPL + k;
+                if (i < n) {
+                    const val_t nr = b[i] - Ax[i], z = dinv ? (val_t)(dinv[i / NVEC] * nr) : nr;
+                    r[i] = nr; p[i] = z;
+                    arr[k] += (double)nr * (double)nr; arz[k] += (double)nr * (double)z; abb[k] += (double)b[i] * (double)b[i];
+                }
+            }
+        }
+    }
+    block_cols<NVEC>(arr, s);
+    write_partials<NVEC>(s, prr);
+    block_cols<NVEC>(abb, s);
+    write_partials<NVEC>(s, pbb);
+    if (dinv) {
+        block_cols<NVEC>(arz, s);
+        write_partials<NVEC>(s, prz);
+    }
+}
+// ... and its scalars (one workgroup; prz is prr in plain CG)
+__global__ __launch_bounds__(CGB) void k_cgm_begin_fold(const double *__restrict__ prr, const double *__restrict__ prz, const double *__restrict__ pbb, int np, int nvec,
+                                                        CgmScal *__restrict__ S)
+{
+    __shared__ double s[(CGB / 64) * MAX_NVEC];
+    const int c = threadIdx.x < nvec ? threadIdx.x : 0;
+    fold_cols(prr, np, nvec, s);
+    const double rr = col_total(s, nvec, c);
+    fold_cols(prz, np, nvec, s);
+    const double rz = col_total(s, nvec, c);
+    fold_cols(pbb, np, nvec, s);
+    const double bb = col_total(s, nvec, c);
+    if (threadIdx.x < nvec) {
+        CgmScal v;
+        v.rho = rz; v.rr = rr; v.bb = bb; v.iterations = 0; v.breakdown = 0; v.frozen = 0; v.pad = 0;
+        S[threadIdx.x] = v;
+    }
+}
+
+// tilespmv_cg_multi_solve, between two blocks of iterations: the columns of `mask` are final
+__global__ __launch_bounds__(64) void k_cgm_freeze(CgmScal *__restrict__ S, int nvec, unsigned mask)
+{
+    if (threadIdx.x < nvec && ((mask >> threadIdx.x) & 1u)) S[threadIdx.x].frozen = 1;
+}
+// ... and the columns of `mask` (b = 0) are 0
+__global__ __launch_bounds__(CGB) void k_cgm_zero_columns(long long rows, int nvec, unsigned mask, val_t *__restrict__ x)
+{
+    const long long i = (long long)blockIdx.x * CGB + threadIdx.x;
+    if (i >= rows) return;
+    for (int c = 0; c < nvec; c++)
+        if ((mask >> c) & 1u) x[i * nvec + c] = (val_t)0;
+}
+
+inline bool misaligned(const void *p) { return ((uintptr_t)p & 15u) != 0; }
+
+}  // namespace
+}  // namespace tilespmv
+
+using namespace tilespmv;
+
+struct tilespmv_cg_multi {
+    tilespmv_plan *plan = nullptr;
+    tilespmv_cg *single = nullptr;   // nvec = 1: tilespmv_cg_* itself
+    long long rows = 0, n = 0;       // n = rows * nvec
+    int nvec = 0, np = 0;
+    const val_t *dinv = nullptr;     // borrowed
+    void *block = nullptr;           // the one allocation: r, p, Ap, the partial-sum arrays, the scalar blocks
+    val_t *r = nullptr, *p = nullptr, *Ap = nullptr;
+    double *ppap = nullptr, *prr = nullptr, *prz = nullptr, *pbb = nullptr;
+    CgmScal *S = nullptr;
+};
+
+namespace {
+
+template <int NVEC> void launch_begin(const tilespmv_cg_multi *c, const val_t *B, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_cgm_begin<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, B, c->Ap, c->r, c->p, c->dinv, c->prr, c->prz, c->pbb);
+}
+template <int NVEC> void launch_iteration(const tilespmv_cg_multi *c, val_t *X, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_cgm_dot<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, c->p, c->Ap, c->ppap, c->prz, c->np, c->S);
+    hipLaunchKernelGGL(k_cgm_update<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, c->p, c->Ap, X, c->r, c->dinv, c->ppap, c->prr, c->prz, c->np, c->S);
+    hipLaunchKernelGGL(k_cgm_direction<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, c->r, c->p, c->dinv, c->prr, c->prz, c->np, c->S);
+}
+
+// the scalar blocks of all columns, after a synchronisation of the stream
+int read_columns(const tilespmv_cg_multi *c, hipStream_t st, tilespmv_cg_state *cols /* [nvec], whole structs */)
+{
+    CgmScal h[MAX_NVEC];
+    hipError_t e = hipMemcpyAsync(h, c->S, sizeof(CgmScal) * c->nvec, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    for (int j = 0; j < c->nvec; j++) {
+        cols[j].size = sizeof(tilespmv_cg_state);
+        cols[j].iterations = h[j].iterations;
+        cols[j].status = h[j].breakdown ? TILESPMV_CG_BREAKDOWN : h[j].rr == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
+        cols[j].rr = h[j].rr; cols[j].bb = h[j].bb;
+    }
+    return 0;
+}
+// element j of a caller's array whose elements are `stride` bytes apart (a caller built against a shorter struct gets the fields it knows)
+void put_state(tilespmv_cg_state *out, unsigned stride, int j, tilespmv_cg_state s)
+{
+    s.size = stride;
+    memcpy((char *)out + (size_t)j * stride, &s, std::min<size_t>(stride, sizeof(s)));
+}
+
+}  // namespace
+
+extern "C" int tilespmv_cg_multi_create(tilespmv_cg_multi **cg, tilespmv_plan *plan, int nvec, const MAT_VAL_TYPE *d_dinv)
+{
+    if (cg) *cg = nullptr;
+    if (!cg || !plan) return (int)hipErrorInvalidValue;
+    if (nvec != 1 && nvec != 2 && nvec != 4 && nvec != 8) return (int)hipErrorInvalidValue;   // (before the plan is touched)
+    const long long rows = plan->matrix_rows;
+    if (rows <= 0 || plan->dev.colA != rows || plan->dev.f_row0 != 0 || plan->dev.f_rows != rows) return (int)hipErrorInvalidValue;   // square, whole matrix
+    if (misaligned(d_dinv)) return (int)hipErrorInvalidValue;
+    if (nvec == 1) {
+        tilespmv_cg *one = nullptr;
+        const int rc = tilespmv_cg_create(&one, plan, d_dinv);
+        if (rc) return rc;
+        auto *c = new tilespmv_cg_multi();
+        c->plan = plan; c->single = one; c->rows = c->n = rows; c->nvec = 1;
+        *cg = c;
+        return 0;
+    }
+    int rc = tilespmv_plan_reserve_spmm(plan, nvec);   // plans that multiply one right-hand side at a time: their scratch now, so that iterate never allocates
+    if (rc) return rc;
+    const size_t vec = ((size_t)(rows + 16) * nvec * sizeof(val_t) + 255) / 256 * 256, parts = (size_t)CG_MAX_PARTS * nvec * sizeof(double);
+    const size_t bytes = 3 * vec + 4 * parts + ((size_t)nvec * sizeof(CgmScal) + 255) / 256 * 256;
+    void *blk = nullptr;
+    hipError_t e = hipMalloc(&blk, bytes);
+    if (e == hipSuccess) e = hipMemset(blk, 0, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (blk) (void)hipFree(blk);
+        return (int)e;
+    }
+    auto *c = new tilespmv_cg_multi();
+    c->plan = plan; c->rows = rows; c->nvec = nvec; c->n = rows * nvec; c->np = cgm_parts(rows, nvec); c->dinv = d_dinv; c->block = blk;
+    char *at = (char *)blk;
+    c->r = (val_t *)at; at += vec;
+    c->p = (val_t *)at; at += vec;
+    c->Ap = (val_t *)at; at += vec;
+    c->ppap = (double *)at; at += parts;
+    c->prr = (double *)at; at += parts;
+    c->prz = d_dinv ? (double *)at : c->prr; at += parts;
+    c->pbb = (double *)at; at += parts;
+    c->S = (CgmScal *)at;
+    *cg = c;
+    return 0;
+}
+
+extern "C" void tilespmv_cg_multi_destroy(tilespmv_cg_multi *cg)
+{
+    if (!cg) return;
+    if (cg->single) tilespmv_cg_destroy(cg->single);
+    if (cg->block) (void)hipFree(cg->block);
+    delete cg;
+}
+
+extern "C" int tilespmv_cg_multi_begin(tilespmv_cg_multi *cg, const MAT_VAL_TYPE *d_B, MAT_VAL_TYPE *d_X, void *stream)
+{
+    if (!cg || !d_B || !d_X || misaligned(d_B) || misaligned(d_X)) return (int)hipErrorInvalidValue;
+    if (cg->single) return tilespmv_cg_begin(cg->single, d_B, d_X, stream);
+    const hipStream_t st = (hipStream_t)stream;
+    const int rc = tilespmv_plan_spmm(cg->plan, d_X, cg->Ap, cg->nvec, stream);
+    if (rc) return rc;
+    switch (cg->nvec) {
+    case 2: launch_begin<2>(cg, d_B, st); break;
+    case 4: launch_begin<4>(cg, d_B, st); break;
+    default: launch_begin<8>(cg, d_B, st); break;
+    }
+    hipLaunchKernelGGL(k_cgm_begin_fold, dim3(1), dim3(CGB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->nvec, cg->S);
+    return (int)hipGetLastError();
+}
+
+extern "C" int tilespmv_cg_multi_iterate(tilespmv_cg_multi *cg, MAT_VAL_TYPE *d_X, int count, void *stream)
+{
+    if (!cg || !d_X || misaligned(d_X) || count < 0) return (int)hipErrorInvalidValue;
+    if (cg->single) return tilespmv_cg_iterate(cg->single, d_X, count, stream);
+    const hipStream_t st = (hipStream_t)stream;
+    for (int i = 0; i < count; i++) {
+        const int rc = tilespmv_plan_spmm(cg->plan, cg->p, cg->Ap, cg->nvec, stream);
+        if (rc) return rc;
+        switch (cg->nvec) {
+        case 2: launch_iteration<2>(cg, d_X, st); break;
+        case 4: launch_iteration<4>(cg, d_X, st); break;
+        default: launch_iteration<8>(cg, d_X, st); break;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+extern "C" int tilespmv_cg_multi_state_read(tilespmv_cg_multi *cg, void *stream, tilespmv_cg_state *out)
+{
+    if (!cg || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
+    if (cg->single) return tilespmv_cg_state_read(cg->single, stream, out);
+    tilespmv_cg_state cols[MAX_NVEC];
+    const int rc = read_columns(cg, (hipStream_t)stream, cols);
+    if (rc) return rc;
+    const unsigned stride = out->size;
+    for (int j = 0; j < cg->nvec; j++) put_state(out, stride, j, cols[j]);
+    return 0;
+}
+
+extern "C" int tilespmv_cg_multi_solve(tilespmv_cg_multi *cg, const MAT_VAL_TYPE *d_B, MAT_VAL_TYPE *d_X, double rtol, int maxiter, int check_every, void *stream,
+                                       tilespmv_cg_state *out)
+{
+    if (!cg || !out || out->size < sizeof(tilespmv_cg_state) || maxiter < 0) return (int)hipErrorInvalidValue;
+    if (cg->single) return tilespmv_cg_solve(cg->single, d_B, d_X, rtol, maxiter, check_every, stream, out);
+    if (check_every < 1) check_every = 1;
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned stride = out->size, all = (1u << cg->nvec) - 1u;
+    int rc = tilespmv_cg_multi_begin(cg, d_B, d_X, stream);
+    if (rc) return rc;
+    unsigned final_mask = 0;   // columns whose out[] entry stands: frozen on the device, they ride through the product and change no more
+    int done = 0;              // iterations issued = the count of every column that still runs
+    for (;;) {
+        tilespmv_cg_state cols[MAX_NVEC];
+        rc = read_columns(cg, st, cols);
+        if (rc) return rc;
+        unsigned fresh = 0, zero = 0;
+        for (int j = 0; j < cg->nvec; j++) {
+            const unsigned bit = 1u << j;
+            if (final_mask & bit) continue;
+            tilespmv_cg_state s = cols[j];
+            if (s.status == TILESPMV_CG_BREAKDOWN) fresh |= bit;
+            else if (s.bb == 0.0) { s.rr = 0.0; s.status = TILESPMV_CG_CONVERGED; fresh |= bit; zero |= bit; }   // b = 0: the solution is 0
+            else if (s.rr <= rtol * rtol * s.bb) { s.status = TILESPMV_CG_CONVERGED; fresh |= bit; }
+            else s.status = done >= maxiter ? TILESPMV_CG_MAXITER : TILESPMV_CG_RUNNING;
+            put_state(out, stride, j, s);
+        }
+        final_mask |= fresh;
+        const bool last = final_mask == all || done >= maxiter;
+        if (fresh && !last) hipLaunchKernelGGL(k_cgm_freeze, dim3(1), dim3(64), 0, st, cg->S, cg->nvec, fresh);
+        if (zero) hipLaunchKernelGGL(k_cgm_zero_columns, dim3((unsigned)((cg->rows + CGB - 1) / CGB)), dim3(CGB), 0, st, cg->rows, cg->nvec, zero, d_X);
+        if ((fresh && !last) || zero) {
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return (int)e;
+        }
+        if (last) return zero ? (int)hipStreamSynchronize(st) : 0;
+        const int k = std::min(check_every, maxiter - done);
+        rc = tilespmv_cg_multi_iterate(cg, d_X, k, stream);
+        if (rc) return rc;
+        done += k;
+    }
+}

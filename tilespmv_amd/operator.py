@@ -6,6 +6,7 @@
     op = SparseOperator(..., value_map=True); op.update_values(v2)   # new values of the same pattern: both plans refreshed from A's one value array
     x, info = cgls(op, b)                                            # least squares  min ||A x - b||
     x, info = op.cg(b)                                               # A x = b, A symmetric positive definite: the solver in the library
+    X, infos = op.cg(B)                                              # B of shape (rows, k): k systems in lock-step around the multi-vector product
 
 The plan of A^T is a plan like any other (tuned kernels, form choice, ordered sums); there is no scatter form of A^T x.
 """
@@ -148,11 +149,14 @@ class SparseOperator:
         """A x = b by conjugate gradients in the library (``api.CG`` over the plan of A: symmetric positive definite A) — the product and three fused kernels per
         iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: the inverse
         diagonal as a CUDA vector (Jacobi; ``api.csr_diagonal_device(..., invert=True)`` makes it), None = plain CG.  Stops at ``sqrt(rr / bb) <= rtol`` or after ``maxiter``
-        iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}``."""
+        iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}``.
+        A contiguous 2-D ``b`` of shape (rows, k) solves k systems at once (``_cg_multi``): ``(X, [info] * k)``."""
         import torch
         rows, cols = self.shape
         if rows != cols:
             raise ValueError("cg needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
+        if b.dim() == 2:
+            return self._cg_multi(b, x0, rtol, maxiter, check_every, dinv, stream)
         if b.dim() != 1 or b.numel() != rows or not b.is_contiguous():
             raise ValueError("b must be a contiguous vector of %d elements" % rows)
         if dinv is not None and (dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
@@ -170,6 +174,56 @@ class SparseOperator:
         info = {"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
                 "status": s["status_name"]}
         return x, info
+
+    @staticmethod
+    def cg_groups(k):
+        """How ``cg`` splits ``k`` right-hand sides: ``[(first column, columns, nvec), ...]`` — groups of at most 8 columns, each solved by ``api.CGMulti`` with nvec = the next
+        of 2, 4, 8 (a lone last column: nvec = 1, the single solver)."""
+        out = []
+        for g in range(0, k, 8):
+            w = min(8, k - g)
+            out.append((g, w, 1 if w == 1 else 2 if w == 2 else 4 if w <= 4 else 8))
+        return out
+
+    def _cg_multi(self, b, x0, rtol, maxiter, check_every, dinv, stream):
+        """``cg`` for a contiguous ``b`` of shape (rows, k), k >= 1: the columns are solved in lock-step around the multi-vector product (``api.CGMulti``) in the
+        groups of ``cg_groups(k)``; a group narrower than its nvec is padded with zero columns, which the library returns as x = 0 after 0 iterations without touching the others.
+        Returns ``(X, infos)``: ``X`` of shape (rows, k) and a list of k info dicts as the 1-D form returns."""
+        import torch
+        rows = self.shape[0]
+        k = b.shape[1]
+        if b.shape[0] != rows or k < 1 or not b.is_contiguous():
+            raise ValueError("b must be a contiguous (%d, k) matrix, k >= 1" % rows)
+        if x0 is not None and (tuple(x0.shape) != (rows, k)):
+            raise ValueError("x0 must have b's shape")
+        if dinv is not None and (dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
+            raise ValueError("dinv must be a contiguous vector of %d elements of b's type" % rows)
+        maxiter = 2 * rows if maxiter is None else maxiter
+        st = _stream(stream)
+        X = torch.zeros((rows + 16, k), dtype=b.dtype, device=b.device)[:rows]
+        if x0 is not None:
+            X.copy_(x0)
+        infos = []
+        for g, w, nvec in self.cg_groups(k):
+            whole = w == k and nvec == k and b.data_ptr() % 16 == 0   # the group is b itself: no copies
+            if whole:
+                Bg, Xg = b, X
+            else:
+                Bg = torch.zeros((rows + 16, nvec), dtype=b.dtype, device=b.device)[:rows]
+                Xg = torch.zeros((rows + 16, nvec), dtype=b.dtype, device=b.device)[:rows]
+                Bg[:, :w].copy_(b[:, g:g + w])
+                Xg[:, :w].copy_(X[:, g:g + w])
+            solver = api.CGMulti(self.A, nvec, None if dinv is None else dinv.data_ptr())
+            try:
+                states = solver.solve(Bg.data_ptr(), Xg.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
+            finally:
+                solver.close()
+            if not whole:
+                X[:, g:g + w].copy_(Xg[:, :w])
+            for s in states[:w]:
+                infos.append({"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"],
+                              "converged": s["status"] == api.CG_CONVERGED, "status": s["status_name"]})
+        return X, infos
 
     def close(self):
         for p in (getattr(self, "A", None), getattr(self, "AT", None)):
