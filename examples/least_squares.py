@@ -1,6 +1,9 @@
 """Least squares  min ||A x - b||  with CGLS on one GPU: the plans of A and of A^T from one CSR (SparseOperator; A^T built on the device from A's CSR).
 
-    python examples/least_squares.py --rows 2000000 --cols 500000 --per-row 8
+    python examples/least_squares.py --rows 2000000 --cols 500000 --per-row 8 [--solver library|torch] [--damp 0.1]
+
+--solver library (the default): SparseOperator.cgls, the solver in the library (tilespmv_cgls_*: two products and four fused kernels per iteration, every scalar on the device);
+--solver torch: the module-level cgls, the same recurrences as a loop of torch operations (no damping).
 
 A is a tall random sparse matrix with a scaled identity stacked into its first rows (well conditioned); b = A x_true + noise.  Prints one JSON line: iterations, residuals, the
 error against x_true, and the time per iteration (one A p and one A^T r).
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--tol", type=float, default=1e-10)
     ap.add_argument("--maxiter", type=int, default=500)
+    ap.add_argument("--solver", default="library", choices=["library", "torch"])
+    ap.add_argument("--damp", type=float, default=0.0, help="Tikhonov damping (library solver only)")
     a = ap.parse_args()
     import torch
     from tilespmv_amd import generators as G
@@ -44,10 +49,15 @@ def main():
     b += 1e-3 * torch.randn(rows, dtype=b.dtype, device=b.device)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    x, info = cgls(op, b, tol=a.tol, maxiter=a.maxiter, check_every=4)
+    if a.solver == "library":
+        x, info = op.cgls(b, rtol=a.tol, maxiter=a.maxiter, check_every=4, damp=a.damp)
+    else:
+        if a.damp != 0.0:
+            raise SystemExit("--damp needs --solver library")
+        x, info = cgls(op, b, tol=a.tol, maxiter=a.maxiter, check_every=4)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    info.update({"rows": rows, "cols": cols, "nnz": nnz, "dtype": a.dtype, "seconds": round(dt, 4),
+    info.update({"solver": a.solver, "rows": rows, "cols": cols, "nnz": nnz, "dtype": a.dtype, "seconds": round(dt, 4),
                  "ms_per_iteration": round(dt * 1e3 / max(info["iterations"], 1), 4),
                  "relative_error_vs_x_true": float(torch.linalg.vector_norm(x - xt) / torch.linalg.vector_norm(xt))})
     op.close()

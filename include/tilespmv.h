@@ -652,6 +652,56 @@ int tilespmv_cg_multi_state_read(tilespmv_cg_multi *cg, void *stream, tilespmv_c
 int tilespmv_cg_multi_solve(tilespmv_cg_multi *cg, const MAT_VAL_TYPE *d_B, MAT_VAL_TYPE *d_X, double rtol, int maxiter, int check_every, void *stream,
                             tilespmv_cg_state *out /* [nvec] */);
 
+/* ---- Least squares in the library: CGLS around the resident plans of A and A^T (new).  min |A x - b|^2 + damp^2 |x|^2 for a rows x cols
+ * matrix A of any shape and rank: conjugate gradients on (A^T A + damp^2 I) x = A^T b, never forming A^T A, optionally preconditioned by a positive diagonal z = cinv o s (with
+ * cinv_j = 1 / |a_j|^2 this is Jacobi on the normal equations: column scaling).  From x0 = 0 and damp = 0 an underdetermined system converges to the minimum-norm solution.
+ * r, q have `rows` elements, p, s have `cols`, all in the value type; gamma = s.z, delta = q.q + damp^2 p.p, nn = s.s and rr = r.r are accumulated in double.
+ *   begin     r = b - A x;  s = A^T r - damp^2 x;  p = z;  gamma, nn, rr, bb = b.b;  nn0 = |A^T b|^2 (one more A^T product);  iteration count and breakdown flag cleared
+ *   iterate   q = A p;  alpha = gamma / delta;  x += alpha p;  r -= alpha q;  s = A^T r - damp^2 x;  z = cinv o s;  gamma' = s.z;  beta = gamma' / gamma;  p = z + beta p
+ * alpha, beta and damp^2 are formed in double and rounded to the value type once, where they multiply (the rule of tilespmv_cg_*).
+ * One iteration = the two plan products and FOUR streaming kernels (q.q (+ p.p);  the update of x and r with r.r;  the normal pass over s;  the direction).  Every scalar lives in
+ * device memory with one writing kernel per field; a reducing kernel leaves one partial per workgroup and the consuming kernel folds them itself, every workgroup in the same order: no
+ * atomics, no finishing launch, no host read.  The number of partials depends on `rows` for row-length sums and on `cols` for column-length sums and on nothing else: where both plans
+ * give a bit-reproducible y (TILESPMV_INFO_ENTRY_ORDERED = 1, e.g. deterministic = 1) the iterates x_k are bit-reproducible too.
+ * Vector elements read or written per iteration beside the two products, by count: 4 rows + 7 cols with damp = 0 and d_cinv = NULL (then nothing extra is touched: no x read in the
+ * normal pass, no store of s, z never stored); damping adds 3 cols, d_cinv adds 2 cols.  The torch loop it replaces moves 7 rows + 12 cols in about a dozen launches; measured in
+ * profiles/cgls_fused_ab.txt.
+ * Guards, taken on the device, with the meaning of the CG guards: gamma = 0 -> alpha = beta = 0, x and r no longer change — a captured graph of k iterations may overrun
+ * convergence; gamma < 0 (a cinv that is not positive), or gamma > 0 without delta > 0 -> the breakdown flag is set, alpha = beta = 0 from then on, x keeps its last good value.
+ * d_b (rows), d_x (cols) and d_cinv (cols) are DEVICE vectors, 16-byte aligned (hipErrorInvalidValue otherwise); nothing behind their last element is read or written.
+ *
+ *   tilespmv_cgls_create      plan_A: whole (tilerow_begin = 0, tilerow_end = tilem), rows x cols; plan_AT: whole, cols x rows — a TILESPMV_CREATE_TRANSPOSE plan or any plan of the
+ *                             transposed CSR.  Both are borrowed and must outlive the solver.  d_cinv: NULL, or cols elements, borrowed; its VALUES may change between solves.  One
+ *                             hipMalloc holds r, q (rows + 16 elements each), p, s (cols + 16 each), the partial-sum arrays and the scalar block.  Returns 0, hipErrorInvalidValue
+ *                             (a NULL argument: no HIP call made; shapes that do not match, a shard plan, a misaligned d_cinv: nothing allocated), or the allocation's error.
+ *   tilespmv_cgls_begin       as above, from the caller's x (pass zeros for none).  `damp` holds for the tilespmv_cgls_iterate calls that follow (it is kept on the device).
+ *   tilespmv_cgls_iterate     `count` iterations back to back.  Like begin: asynchronous on `stream`, no allocation, no synchronisation, no host read, one linear chain of kernels —
+ *                             safe to capture into a hipGraph.  It stops at no tolerance.  Both plans and the solver run on ONE stream at a time.
+ *   tilespmv_cgls_state_read  synchronises `stream` and fills the state (set out->size = sizeof(tilespmv_cgls_state) first; a shorter struct gets the fields it knows).  status (the
+ *                             TILESPMV_CG_* values): BREAKDOWN, CONVERGED when nn is exactly 0, else RUNNING.  nn = the squared norm of the UNPRECONDITIONED normal residual
+ *                             A^T r - damp^2 x; rr = the recurrence's |r|^2, not a recomputed |b - A x|^2.
+ *   tilespmv_cgls_solve       begin, then iterate(check_every) + state_read until nn <= rtol^2 nn0 (CONVERGED: |A^T r| <= rtol |A^T b|), `maxiter` iterations are done (MAXITER; the
+ *                             last block is cut so that no more run) or a breakdown (BREAKDOWN).  nn0 = 0 (b = 0, or b orthogonal to the range of A) -> x = 0, CONVERGED, 0
+ *                             iterations.  check_every < 1 -> 1.  One host synchronisation per check.
+ * All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_cgls tilespmv_cgls;
+typedef struct { unsigned size; int iterations; int status; double nn; double nn0; double rr; double bb; } tilespmv_cgls_state;
+int tilespmv_cgls_create(tilespmv_cgls **ls, tilespmv_plan *plan_A, tilespmv_plan *plan_AT, const MAT_VAL_TYPE *d_cinv /* may be NULL; cols elements */);
+void tilespmv_cgls_destroy(tilespmv_cgls *ls);
+int tilespmv_cgls_begin(tilespmv_cgls *ls, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double damp, void *stream);
+int tilespmv_cgls_iterate(tilespmv_cgls *ls, MAT_VAL_TYPE *d_x, int count, void *stream);
+int tilespmv_cgls_state_read(tilespmv_cgls *ls, void *stream, tilespmv_cgls_state *out);
+int tilespmv_cgls_solve(tilespmv_cgls *ls, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double damp, double rtol, int maxiter, int check_every, void *stream,
+                        tilespmv_cgls_state *out);
+/* d_out[i] = the sum over k in [d_rowPtr[i], d_rowPtr[i + 1]) of v(k)^2, v(k) = d_val[d_src ? d_src[k] : k], i < rows: sums in double, in storage order, one thread per row.
+ * invert != 0: 1 / that, and 1 where it is 0 (an empty column of a wide matrix makes no Inf) — the d_cinv of tilespmv_cgls_create.
+ * Intended use, column scaling that follows the matrix values: transpose the PATTERN once with tilespmv_csr_transpose_device and keep rpT and srcT; after every
+ * tilespmv_plan_update_values call this with d_rowPtr = rpT, d_src = srcT and d_val = A's own value array: row j of A^T read through srcT is column j of A, so d_out[j] = 1 / |a_j|^2
+ * without a second sort, and in an order fixed by the pattern.  Asynchronous on `stream`, capturable.  Returns a hipError_t value (hipErrorInvalidValue for a NULL array other than
+ * d_src, hipErrorNoDevice without a device). */
+int tilespmv_csr_row_sqnorms_device(int rows, const MAT_PTR_TYPE *d_rowPtr, const int *d_src /* may be NULL */, const MAT_VAL_TYPE *d_val, MAT_VAL_TYPE *d_out, int invert,
+                                    void *stream);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

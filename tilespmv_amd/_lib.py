@@ -58,6 +58,15 @@ class CGState(C.Structure):
         self.size = C.sizeof(CGState)
 
 
+class CGLSState(C.Structure):
+    """Mirror of the versioned tilespmv_cgls_state (``size`` first)."""
+    _fields_ = [("size", C.c_uint), ("iterations", C.c_int), ("status", C.c_int), ("nn", C.c_double), ("nn0", C.c_double), ("rr", C.c_double), ("bb", C.c_double)]
+
+    def __init__(self):
+        super().__init__()
+        self.size = C.sizeof(CGLSState)
+
+
 def lib_path(dtype):
     suf = "f64" if np.dtype(dtype) == np.float64 else "f32"
     # TILESPMV_LIB_VARIANT: a library with a suffix, e.g. an earlier commit's built by scripts/ab_prev.sh as lib*_old.so (A/B in one process; never the product)
@@ -193,6 +202,20 @@ def load(dtype=np.float64):
     lib.tilespmv_cg_multi_solve.restype = C.c_int
     lib.tilespmv_csr_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_csr_diagonal_device.restype = C.c_int
+    lib.tilespmv_cgls_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_cgls_create.restype = C.c_int
+    lib.tilespmv_cgls_destroy.argtypes = [C.c_void_p]
+    lib.tilespmv_cgls_destroy.restype = None
+    lib.tilespmv_cgls_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    lib.tilespmv_cgls_begin.restype = C.c_int
+    lib.tilespmv_cgls_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_cgls_iterate.restype = C.c_int
+    lib.tilespmv_cgls_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGLSState)]
+    lib.tilespmv_cgls_state_read.restype = C.c_int
+    lib.tilespmv_cgls_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGLSState)]
+    lib.tilespmv_cgls_solve.restype = C.c_int
+    lib.tilespmv_csr_row_sqnorms_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_csr_row_sqnorms_device.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -219,4 +242,6 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_cg_create", "tilespmv_cg_destroy", "tilespmv_cg_begin", "tilespmv_cg_iterate", "tilespmv_cg_state_read", "tilespmv_cg_solve",
                     "tilespmv_csr_diagonal_device",
                     "tilespmv_cg_multi_create", "tilespmv_cg_multi_destroy", "tilespmv_cg_multi_begin", "tilespmv_cg_multi_iterate", "tilespmv_cg_multi_state_read",
-                    "tilespmv_cg_multi_solve"]
+                    "tilespmv_cg_multi_solve",
+                    "tilespmv_cgls_create", "tilespmv_cgls_destroy", "tilespmv_cgls_begin", "tilespmv_cgls_iterate", "tilespmv_cgls_state_read", "tilespmv_cgls_solve",
+                    "tilespmv_csr_row_sqnorms_device"]

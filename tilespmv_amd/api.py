@@ -570,6 +570,86 @@ class CGMulti:
             pass
 
 
+def csr_row_sqnorms_device(rows, d_rp, d_src, d_v, d_out, invert=False, stream=0, dtype=np.float64):
+    """``tilespmv_csr_row_sqnorms_device``: ``d_out[i]`` = the sum of the squares of the values of row ``i`` of a device CSR (addresses), read through ``d_src`` when it is not None
+    (``v[src[k]]``: with the ``rpT`` / ``srcT`` of ``csr_transpose_device`` and A's own value array, the squared column norms of A); ``invert=True``: its inverse, 1 where it is
+    0 — the ``d_cinv`` of ``CGLS``.  Asynchronous on ``stream``."""
+    lib = _lib.load(dtype)
+    rc = lib.tilespmv_csr_row_sqnorms_device(rows, C.c_void_p(d_rp), C.c_void_p(d_src or None), C.c_void_p(d_v), C.c_void_p(d_out), 1 if invert else 0, C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("tilespmv_csr_row_sqnorms_device failed (hipError %d): bad argument, or no usable device" % rc)
+
+
+class CGLS:
+    """``tilespmv_cgls``: least squares ``min |A x - b|^2 + damp^2 |x|^2`` by CGLS around the resident plans of A and A^T, every scalar on the device (include/tilespmv.h,
+    DESIGN.md §3.9).  It mirrors ``CG``.
+
+    ``plan_A`` (rows x cols) and ``plan_AT`` (cols x rows; ``transpose=True``, or any plan of the transposed CSR): whole plans; they must stay open while the solver is.
+    ``d_cinv``: device ADDRESS of a positive diagonal of ``cols`` elements (column scaling: ``csr_row_sqnorms_device(..., invert=True)``; borrowed), or None.  ``b`` (rows) / ``x``
+    (cols) are device addresses, 16-byte aligned.  The solver and its plans run on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue
+    (swapped or mismatched plans, a shard, a misaligned vector)."""
+
+    def __init__(self, plan_A, plan_AT, d_cinv=None):
+        if plan_A.lib is not plan_AT.lib:
+            raise ValueError("CGLS: both plans must have the same value type")
+        self.lib, self.plan_A, self.plan_AT = plan_A.lib, plan_A, plan_AT
+        h = C.c_void_p()
+        rc = self.lib.tilespmv_cgls_create(C.byref(h), plan_A.h, plan_AT.h, C.c_void_p(d_cinv or None))
+        self._check(rc, "tilespmv_cgls_create")
+        self.h = h
+
+    @staticmethod
+    def _check(rc, what):
+        if rc == HIP_ERROR_INVALID_VALUE:
+            raise ValueError("%s: hipErrorInvalidValue (whole plans of a rows x cols matrix and of its transpose; vectors 16-byte aligned)" % what)
+        if rc != 0:
+            raise RuntimeError("%s: HIP error %d" % (what, rc))
+
+    @staticmethod
+    def _state(st):
+        rel = (st.nn / st.nn0) ** 0.5 if st.nn0 > 0 else 0.0
+        return {"iterations": st.iterations, "status": st.status, "status_name": CG_STATUS_NAMES[st.status], "nn": st.nn, "nn0": st.nn0, "rr": st.rr, "bb": st.bb,
+                "relative_normal_residual": rel}
+
+    def begin(self, d_b, d_x, damp=0.0, stream=0):
+        """r = b - A x, s = A^T r - damp^2 x, p = z; asynchronous.  ``damp`` holds for the ``iterate`` calls that follow."""
+        self._check(self.lib.tilespmv_cgls_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), damp, C.c_void_p(stream)), "tilespmv_cgls_begin")
+
+    def iterate(self, d_x, count=1, stream=0):
+        """``count`` iterations; asynchronous, capturable into a graph."""
+        self._check(self.lib.tilespmv_cgls_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_cgls_iterate")
+
+    def state(self, stream=0):
+        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "nn", "nn0", "rr", "bb", "relative_normal_residual"}``."""
+        st = _lib.CGLSState()
+        self._check(self.lib.tilespmv_cgls_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_cgls_state_read")
+        return self._state(st)
+
+    def solve(self, d_b, d_x, damp=0.0, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
+        """``tilespmv_cgls_solve``; returns the final state (as ``state``)."""
+        st = _lib.CGLSState()
+        self._check(self.lib.tilespmv_cgls_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), damp, rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
+                    "tilespmv_cgls_solve")
+        return self._state(st)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tilespmv_cgls_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def algorithmic_bytes(nnz, rows, cols, itemsize):
     """B_alg = nnz*(s_v+4) + 4*(m+1) + s_v*(n+m)."""
     return nnz * (itemsize + 4) + 4 * (rows + 1) + itemsize * (cols + rows)

@@ -4,7 +4,8 @@
     y = op.matvec(x)                                                 # A x      (plan of A)
     z = op.rmatvec(u)                                                # A^T u    (plan of A^T, built on the device from A's CSR: TILESPMV_CREATE_TRANSPOSE)
     op = SparseOperator(..., value_map=True); op.update_values(v2)   # new values of the same pattern: both plans refreshed from A's one value array
-    x, info = cgls(op, b)                                            # least squares  min ||A x - b||
+    x, info = op.cgls(b)                                             # least squares  min ||A x - b|| (+ damp, column scaling): the solver in the library
+    x, info = cgls(op, b)                                            # ... the same as a loop of torch operations (the A/B baseline of scripts/cgls_time.py)
     x, info = op.cg(b)                                               # A x = b, A symmetric positive definite: the solver in the library
     X, infos = op.cg(B)                                              # B of shape (rows, k): k systems in lock-step around the multi-vector product
 
@@ -224,6 +225,34 @@ class SparseOperator:
                 infos.append({"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"],
                               "converged": s["status"] == api.CG_CONVERGED, "status": s["status_name"]})
         return X, infos
+
+    def cgls(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, cinv=None, damp=0.0, stream=None):
+        """Least squares ``min |A x - b|^2 + damp^2 |x|^2`` by CGLS in the library (``api.CGLS`` over both plans) — the two products and four fused kernels per
+        iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a contiguous torch CUDA vector of ``rows`` elements; ``cinv``: a
+        positive diagonal of ``cols`` elements as a CUDA vector (column scaling; ``api.csr_row_sqnorms_device(..., invert=True)`` makes it), None = unpreconditioned.  Stops at
+        ``|A^T r - damp^2 x| <= rtol |A^T b|`` or after ``maxiter`` iterations (default ``2 * cols``).  Returns ``(x, info)`` with ``info = {"iterations", "normal_residual",
+        "relative_normal_residual", "residual", "converged", "status"}`` (``residual``: the recurrence's ``|r|``)."""
+        import torch
+        rows, cols = self.shape
+        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
+            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
+        if cinv is not None and (not _is_tensor(cinv) or cinv.numel() != cols or not cinv.is_contiguous() or cinv.dtype != b.dtype):
+            raise ValueError("cinv must be a contiguous vector of %d elements of b's type" % cols)
+        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != cols or x0.dtype != b.dtype):
+            raise ValueError("x0 must be a vector of %d elements of b's type" % cols)
+        maxiter = 2 * cols if maxiter is None else maxiter
+        x = torch.zeros(cols + 16, dtype=b.dtype, device=b.device)[:cols]
+        if x0 is not None:
+            x.copy_(x0)
+        st = _stream(stream)
+        solver = api.CGLS(self.A, self.AT, None if cinv is None else cinv.data_ptr())
+        try:
+            s = solver.solve(b.data_ptr(), x.data_ptr(), damp=damp, rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
+        finally:
+            solver.close()
+        info = {"iterations": s["iterations"], "normal_residual": s["nn"] ** 0.5, "relative_normal_residual": s["relative_normal_residual"], "residual": s["rr"] ** 0.5,
+                "converged": s["status"] == api.CG_CONVERGED, "status": s["status_name"]}
+        return x, info
 
     def close(self):
         for p in (getattr(self, "A", None), getattr(self, "AT", None)):
