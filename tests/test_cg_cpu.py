@@ -3,7 +3,6 @@ compiler made spill-free kernels of hip_solver.hip and few of them, and the nump
 the inputs of those tests — checked here so that a GPU visit is not spent finding out."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import cg_mirror as M
+from kernel_asm import device_asm, private_segments
 from tilespmv_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,25 +61,16 @@ print("DONE")
     assert r.returncode == 0 and "DONE" in r.stdout and r.stdout.count("RC") == 2, r.stdout
 
 
-def _device_asm(dt, out):
-    """hip_solver.hip as device assembly, the source and flags of tilespmv_amd/csrc/Makefile (the method of tests/test_kernel_resources.py)."""
-    defs = ["-DMAT_VAL_TYPE=double"] if dt == "f64" else ["-DMAT_VAL_TYPE=float", "-DTILESPMV_F32"]
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "--offload-arch=gfx950", "-munsafe-fp-atomics", "-w"] + defs +
-                   ["-S", "--cuda-device-only", os.path.join(ROOT, "tilespmv_amd/csrc/hip_solver.hip"), "-o", out], check=True)
-    return open(out).read()
-
-
 def test_no_solver_kernel_spills_and_there_are_few_of_them(tmp_path):
     with ThreadPoolExecutor(2) as ex:
-        asm = dict(zip(("f64", "f32"), ex.map(lambda dt: _device_asm(dt, str(tmp_path / (dt + ".s"))), ("f64", "f32"))))
+        asm = dict(zip(("f64", "f32"), ex.map(lambda dt: device_asm("hip_solver.hip", dt, str(tmp_path / (dt + ".s"))), ("f64", "f32"))))
     for dt, s in asm.items():
-        kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S)
-        names = [k for k, _ in kernels]
-        print(dt, len(kernels), "kernels:", names)
-        assert 4 <= len(kernels) <= MAX_SOLVER_KERNELS, (dt, names)
+        spills = private_segments(s)
+        names = list(spills)
+        print(dt, len(spills), "kernels:", names)
+        assert 4 <= len(spills) <= MAX_SOLVER_KERNELS, (dt, names)
         for want in ("k_cg_dot", "k_cg_update", "k_cg_direction", "k_csr_diagonal"):
             assert sum(want in k for k in names) == 1, (dt, want, names)
-        spills = {name: int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) for name, body in kernels}
         assert not {k: v for k, v in spills.items() if v}, (dt, spills)
         assert "global_load_dwordx4" in s and "global_store_dwordx4" in s      # the vectors travel as 16-byte lane accesses
 

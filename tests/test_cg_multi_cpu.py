@@ -10,8 +10,6 @@ right-hand sides that tests/test_gpu_cg_multi.py solves (tests/cg_multi_cases.py
 """
 import ctypes as C
 import os
-import re
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -19,6 +17,7 @@ import pytest
 
 import cg_mirror as M
 import cg_multi_cases as MC
+from kernel_asm import device_asm, private_segments
 from tilespmv_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,28 +52,19 @@ def test_the_symbols_are_exported_and_bad_arguments_are_refused_without_a_device
     assert lib.tilespmv_cg_multi_solve(None, None, None, 1e-8, 10, 8, None, st) == HIP_ERROR_INVALID_VALUE
 
 
-def _device_asm(dt, out):
-    """hip_solver_mv.hip as device assembly, the source and flags of tilespmv_amd/csrc/Makefile (the method of tests/test_cg_cpu.py)."""
-    defs = ["-DMAT_VAL_TYPE=double"] if dt == "f64" else ["-DMAT_VAL_TYPE=float", "-DTILESPMV_F32"]
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "--offload-arch=gfx950", "-munsafe-fp-atomics", "-w"] + defs +
-                   ["-S", "--cuda-device-only", os.path.join(ROOT, "tilespmv_amd/csrc/hip_solver_mv.hip"), "-o", out], check=True)
-    return open(out).read()
-
-
 def test_no_kernel_touches_scratch_and_there_are_few_of_them(tmp_path):
     assert "hip_solver_mv.hip" in open(os.path.join(ROOT, "tilespmv_amd/csrc/Makefile")).read()
     with ThreadPoolExecutor(2) as ex:
-        asm = dict(zip(("f64", "f32"), ex.map(lambda dt: _device_asm(dt, str(tmp_path / (dt + ".s"))), ("f64", "f32"))))
+        asm = dict(zip(("f64", "f32"), ex.map(lambda dt: device_asm("hip_solver_mv.hip", dt, str(tmp_path / (dt + ".s"))), ("f64", "f32"))))
     for dt, s in asm.items():
-        kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S)
-        names = [k for k, _ in kernels]
-        print(dt, len(kernels), "kernels:", names)
-        assert 12 <= len(kernels) <= MAX_KERNELS, (dt, names)
+        scratch = private_segments(s)
+        names = list(scratch)
+        print(dt, len(scratch), "kernels:", names)
+        assert 12 <= len(scratch) <= MAX_KERNELS, (dt, names)
         for want in ("k_cgm_dot", "k_cgm_update", "k_cgm_direction", "k_cgm_begin"):
             assert sum(want + "ILi" in k for k in names) == 3, (dt, want, names)                  # one per NVEC in {2, 4, 8}
         for want in ("k_cgm_begin_fold", "k_cgm_freeze"):
             assert sum(want in k for k in names) == 1, (dt, want, names)
-        scratch = {name: int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) for name, body in kernels}
         assert not {k: v for k, v in scratch.items() if v}, (dt, scratch)
         assert "global_load_dwordx4" in s and "global_store_dwordx4" in s      # the arrays travel as 16-byte lane accesses
 

@@ -432,6 +432,35 @@ CG_STATUS_NAMES = ["running", "converged", "maxiter", "breakdown"]
 HIP_ERROR_INVALID_VALUE = 1
 
 
+class _Solver:
+    """What the solver wrappers share: the handle ``h`` of library ``lib``, the translation of return codes, and the end of the handle's life.  A subclass names its destroy
+    entry point (``_destroy``) and says what hipErrorInvalidValue means for it (``_hint``)."""
+
+    @classmethod
+    def _check(cls, rc, what):
+        if rc == HIP_ERROR_INVALID_VALUE:
+            raise ValueError("%s: hipErrorInvalidValue (%s)" % (what, cls._hint))
+        if rc != 0:
+            raise RuntimeError("%s: HIP error %d" % (what, rc))
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._destroy)(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def csr_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dtype=np.float64):
     """``tilespmv_csr_diagonal_device``: ``d_out[i]`` = the sum of the stored entries (i, i) of a device CSR (addresses, as ``Plan.from_device_csr`` takes them); ``invert=True``: its
     inverse, 1 where it is 0 — the ``d_dinv`` of ``CG``.  Asynchronous on ``stream``."""
@@ -441,12 +470,15 @@ def csr_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dt
         raise RuntimeError("tilespmv_csr_diagonal_device failed (hipError %d): bad argument, or no usable device" % rc)
 
 
-class CG:
+class CG(_Solver):
     """``tilespmv_cg``: conjugate gradients around a resident plan, every scalar on the device (include/tilespmv.h).
 
     ``plan``: square and whole; it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal (Jacobi; borrowed), or None for plain CG.  ``b`` / ``x``
     are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library returns
     hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+
+    _destroy = "tilespmv_cg_destroy"
+    _hint = "the plan must be square and whole; vectors 16-byte aligned"
 
     def __init__(self, plan, d_dinv=None):
         self.lib, self.plan = plan.lib, plan
@@ -454,13 +486,6 @@ class CG:
         rc = self.lib.tilespmv_cg_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None))
         self._check(rc, "tilespmv_cg_create")
         self.h = h
-
-    @staticmethod
-    def _check(rc, what):
-        if rc == HIP_ERROR_INVALID_VALUE:
-            raise ValueError("%s: hipErrorInvalidValue (the plan must be square and whole; vectors 16-byte aligned)" % what)
-        if rc != 0:
-            raise RuntimeError("%s: HIP error %d" % (what, rc))
 
     @staticmethod
     def _state(st):
@@ -487,25 +512,8 @@ class CG:
         self._check(self.lib.tilespmv_cg_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)), "tilespmv_cg_solve")
         return self._state(st)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.tilespmv_cg_destroy(self.h)
-            self.h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CGMulti:
+class CGMulti(_Solver):
     """``tilespmv_cg_multi``: conjugate gradients on ``nvec`` systems in lock-step around the multi-vector product, one set of device scalars per column (include/tilespmv.h,
     DESIGN.md §3.8).
 
@@ -513,19 +521,15 @@ class CGMulti:
     the columns; borrowed), or None.  ``B`` / ``X`` are device addresses of row-major ``(rows, nvec)`` arrays, 16-byte aligned.  ``state`` and ``solve`` return a list of ``nvec``
     dicts in the shape of ``CG.state``.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (another nvec, a shard, a non-square plan, a misaligned array)."""
 
+    _destroy = "tilespmv_cg_multi_destroy"
+    _hint = "nvec in {1, 2, 4, 8}; the plan must be square and whole; arrays 16-byte aligned"
+
     def __init__(self, plan, nvec, d_dinv=None):
         self.lib, self.plan, self.nvec = plan.lib, plan, int(nvec)
         h = C.c_void_p()
         rc = self.lib.tilespmv_cg_multi_create(C.byref(h), plan.h, self.nvec, C.c_void_p(d_dinv or None))
         self._check(rc, "tilespmv_cg_multi_create")
         self.h = h
-
-    @staticmethod
-    def _check(rc, what):
-        if rc == HIP_ERROR_INVALID_VALUE:
-            raise ValueError("%s: hipErrorInvalidValue (nvec in {1, 2, 4, 8}; the plan must be square and whole; arrays 16-byte aligned)" % what)
-        if rc != 0:
-            raise RuntimeError("%s: HIP error %d" % (what, rc))
 
     def _states(self):
         arr = (_lib.CGState * self.nvec)()
@@ -552,23 +556,6 @@ class CGMulti:
         self._check(self.lib.tilespmv_cg_multi_solve(self.h, C.c_void_p(d_B), C.c_void_p(d_X), rtol, maxiter, check_every, C.c_void_p(stream), arr), "tilespmv_cg_multi_solve")
         return [CG._state(st) for st in arr]
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.tilespmv_cg_multi_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def csr_row_sqnorms_device(rows, d_rp, d_src, d_v, d_out, invert=False, stream=0, dtype=np.float64):
     """``tilespmv_csr_row_sqnorms_device``: ``d_out[i]`` = the sum of the squares of the values of row ``i`` of a device CSR (addresses), read through ``d_src`` when it is not None
@@ -580,7 +567,7 @@ def csr_row_sqnorms_device(rows, d_rp, d_src, d_v, d_out, invert=False, stream=0
         raise RuntimeError("tilespmv_csr_row_sqnorms_device failed (hipError %d): bad argument, or no usable device" % rc)
 
 
-class CGLS:
+class CGLS(_Solver):
     """``tilespmv_cgls``: least squares ``min |A x - b|^2 + damp^2 |x|^2`` by CGLS around the resident plans of A and A^T, every scalar on the device (include/tilespmv.h,
     DESIGN.md §3.9).  It mirrors ``CG``.
 
@@ -588,6 +575,9 @@ class CGLS:
     ``d_cinv``: device ADDRESS of a positive diagonal of ``cols`` elements (column scaling: ``csr_row_sqnorms_device(..., invert=True)``; borrowed), or None.  ``b`` (rows) / ``x``
     (cols) are device addresses, 16-byte aligned.  The solver and its plans run on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue
     (swapped or mismatched plans, a shard, a misaligned vector)."""
+
+    _destroy = "tilespmv_cgls_destroy"
+    _hint = "whole plans of a rows x cols matrix and of its transpose; vectors 16-byte aligned"
 
     def __init__(self, plan_A, plan_AT, d_cinv=None):
         if plan_A.lib is not plan_AT.lib:
@@ -597,13 +587,6 @@ class CGLS:
         rc = self.lib.tilespmv_cgls_create(C.byref(h), plan_A.h, plan_AT.h, C.c_void_p(d_cinv or None))
         self._check(rc, "tilespmv_cgls_create")
         self.h = h
-
-    @staticmethod
-    def _check(rc, what):
-        if rc == HIP_ERROR_INVALID_VALUE:
-            raise ValueError("%s: hipErrorInvalidValue (whole plans of a rows x cols matrix and of its transpose; vectors 16-byte aligned)" % what)
-        if rc != 0:
-            raise RuntimeError("%s: HIP error %d" % (what, rc))
 
     @staticmethod
     def _state(st):
@@ -631,23 +614,6 @@ class CGLS:
         self._check(self.lib.tilespmv_cgls_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), damp, rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
                     "tilespmv_cgls_solve")
         return self._state(st)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.tilespmv_cgls_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def algorithmic_bytes(nnz, rows, cols, itemsize):

@@ -4,10 +4,8 @@
 //   k_cg_dot        reads p, Ap                     partial sums of p.Ap, one per workgroup
 //   k_cg_update     reads p, Ap, x, r (, dinv)      alpha = rho / p.Ap;  x += alpha p;  r -= alpha Ap;  partial sums of r.r and (Jacobi) r.z, z = dinv o r
 //   k_cg_direction  reads r, p (, dinv)             beta = rho_new / rho;  p = z + beta p  (z recomputed from r and dinv, never stored)
-// 11 n vector elements per iteration (13 n with Jacobi).  No scalar ever visits the host: a reducing kernel writes one partial per workgroup and the CONSUMING kernel folds
-// the partials itself — every workgroup the same additions in the same order, so all of them hold the same bits of alpha / beta; no finishing launch, no atomics.  The number
-// of partials (cg_parts) and which elements a thread adds depend on n alone, the wave and workgroup reductions are fixed trees: the order of every sum is fixed by the problem size.
-// Partial sums and scalars are double in both builds; alpha and beta are rounded to the value type once, where they multiply.
+// 11 n vector elements per iteration (13 n with Jacobi).  The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail
+// are those of hip_solver_common.h; the number of partials is solver_parts(n).  alpha and beta are rounded to the value type once, where they multiply.
 //
 // The scalar block (CgScal) has ONE writing kernel per field and no kernel reads a field it (or a concurrent workgroup of it) writes:
 //   rho         k_cg_dot, workgroup 0 (fold of the r.z partials the previous update left; 0 after a breakdown)      read by k_cg_update, k_cg_direction
@@ -18,80 +16,37 @@
 // positive definite) -> breakdown is set, alpha = beta = 0 in this and every later iteration, x keeps its last good value.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "hip_plan_internal.h"
+#include "hip_solver_common.h"
 
 namespace tilespmv {
 namespace {
-
-constexpr int CGB = 256;                              // threads per workgroup
-constexpr int CG_VPL = 16 / (int)sizeof(val_t);       // elements per 16-byte lane load (2 in fp64, 4 in fp32)
-constexpr int CG_U = 2;                               // vectors per lane and trip: a workgroup's trip covers CG_U * CGB consecutive vectors
-constexpr int CG_MAX_PARTS = 1024;                    // partial sums = workgroups of the streaming kernels: 4 per CU on 256 CUs
-typedef val_t cvec_t __attribute__((ext_vector_type(CG_VPL)));
 
 struct CgScal {
     double rho, rr, bb;
     int iterations, breakdown;
 };
 
-// workgroups (= partial sums) for n elements: a function of n alone
-inline int cg_parts(long long n)
-{
-    const long long trips = (n / CG_VPL + (long long)CG_U * CGB - 1) / ((long long)CG_U * CGB);
-    return (int)std::max<long long>(1, std::min<long long>(CG_MAX_PARTS, trips));
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-// the workgroup's sum, returned to every thread: wave trees, then the four wave sums in wave order
-__device__ __forceinline__ double block_sum(double v, double *s)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = ((s[0] + s[1]) + s[2]) + s[3];
-    __syncthreads();
-    return t;
-}
-// the sum of np partials, the same additions in every workgroup
-__device__ __forceinline__ double fold(const double *__restrict__ part, int np, double *s)
-{
-    double a = 0.0;
-    for (int i = threadIdx.x; i < np; i += CGB) a += part[i];
-    return block_sum(a, s);
-}
-
-// Element ranges: full 16-byte vectors [0, nv) are walked in trips of CG_U * CGB by workgroup blockIdx.x, blockIdx.x + gridDim.x, ...; the n % CG_VPL elements behind them belong
-// to thread 0 of workgroup 0 (scalar accesses: nothing past element n - 1 of a caller's vector is touched).
-#define CG_FOR_TRIPS(base) for (long long base = (long long)blockIdx.x * (CG_U * CGB) + threadIdx.x; base < nv; base += (long long)gridDim.x * (CG_U * CGB))
-
-__global__ __launch_bounds__(CGB) void k_cg_dot(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, double *__restrict__ ppap, const double *__restrict__ prz,
+__global__ __launch_bounds__(SVB) void k_cg_dot(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, double *__restrict__ ppap, const double *__restrict__ prz,
                                                 int np, CgScal *__restrict__ S)
 {
-    __shared__ double s[CGB / 64];
-    const long long nv = n / CG_VPL;
+    __shared__ double s[SVB / 64];
+    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    CG_FOR_TRIPS(base) {
-        cvec_t a[CG_U], b[CG_U];
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t a[SV_U], b[SV_U];
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
-            if (v < nv) { a[u] = reinterpret_cast<const cvec_t *>(p)[v]; b[u] = reinterpret_cast<const cvec_t *>(Ap)[v]; }
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) { a[u] = lanes(p)[v]; b[u] = lanes(Ap)[v]; }
             else { a[u] = (val_t)0; b[u] = (val_t)0; }
         }
 #pragma unroll
-        for (int u = 0; u < CG_U; u++)
+        for (int u = 0; u < SV_U; u++)
 #pragma unroll
-            for (int q = 0; q < CG_VPL; q++) acc += (double)a[u][q] * (double)b[u][q];
+            for (int q = 0; q < SV_VPL; q++) acc += (double)a[u][q] * (double)b[u][q];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * CG_VPL; i < n; i++) acc += (double)p[i] * (double)Ap[i];
+        for (long long i = nv * SV_VPL; i < n; i++) acc += (double)p[i] * (double)Ap[i];
     const double t = block_sum(acc, s);
     if (threadIdx.x == 0) ppap[blockIdx.x] = t;
     if (blockIdx.x == 0) {   // rho of this iteration, for the two kernels that follow
@@ -100,37 +55,37 @@ __global__ __launch_bounds__(CGB) void k_cg_dot(long long n, const val_t *__rest
     }
 }
 
-__global__ __launch_bounds__(CGB) void k_cg_update(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, val_t *__restrict__ x, val_t *__restrict__ r,
+__global__ __launch_bounds__(SVB) void k_cg_update(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, val_t *__restrict__ x, val_t *__restrict__ r,
                                                    const val_t *__restrict__ dinv, const double *__restrict__ ppap, double *__restrict__ prr, double *__restrict__ prz, int np,
                                                    CgScal *__restrict__ S)
 {
-    __shared__ double s[CGB / 64];
+    __shared__ double s[SVB / 64];
     const double pap = fold(ppap, np, s), rho = S->rho;
     const bool broke = rho < 0.0 || (rho > 0.0 && !(pap > 0.0));
     const val_t alpha = (val_t)((rho > 0.0 && pap > 0.0) ? rho / pap : 0.0);
     if (broke && blockIdx.x == 0 && threadIdx.x == 0) S->breakdown = 1;
-    const long long nv = n / CG_VPL;
+    const long long nv = n / SV_VPL;
     double arr = 0.0, arz = 0.0;
-    CG_FOR_TRIPS(base) {
-        cvec_t vp[CG_U], va[CG_U], vx[CG_U], vr[CG_U], vd[CG_U];
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t vp[SV_U], va[SV_U], vx[SV_U], vr[SV_U], vd[SV_U];
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                vp[u] = reinterpret_cast<const cvec_t *>(p)[v]; va[u] = reinterpret_cast<const cvec_t *>(Ap)[v];
-                vx[u] = reinterpret_cast<const cvec_t *>(x)[v]; vr[u] = reinterpret_cast<const cvec_t *>(r)[v];
-                if (dinv) vd[u] = reinterpret_cast<const cvec_t *>(dinv)[v];
+                vp[u] = lanes(p)[v]; va[u] = lanes(Ap)[v];
+                vx[u] = lanes(x)[v]; vr[u] = lanes(r)[v];
+                if (dinv) vd[u] = lanes(dinv)[v];
             }
         }
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const cvec_t nx = vx[u] + alpha * vp[u], nr = vr[u] - alpha * va[u];
-                reinterpret_cast<cvec_t *>(x)[v] = nx;
-                reinterpret_cast<cvec_t *>(r)[v] = nr;
+                const svec_t nx = vx[u] + alpha * vp[u], nr = vr[u] - alpha * va[u];
+                lanes(x)[v] = nx;
+                lanes(r)[v] = nr;
 #pragma unroll
-                for (int q = 0; q < CG_VPL; q++) {
+                for (int q = 0; q < SV_VPL; q++) {
                     arr += (double)nr[q] * (double)nr[q];
                     if (dinv) arz += (double)nr[q] * (double)(val_t)(vd[u][q] * nr[q]);
                 }
@@ -138,7 +93,7 @@ __global__ __launch_bounds__(CGB) void k_cg_update(long long n, const val_t *__r
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * CG_VPL; i < n; i++) {
+        for (long long i = nv * SV_VPL; i < n; i++) {
             const val_t nr = r[i] - alpha * Ap[i];
             x[i] = x[i] + alpha * p[i];
             r[i] = nr;
@@ -153,58 +108,58 @@ __global__ __launch_bounds__(CGB) void k_cg_update(long long n, const val_t *__r
     }
 }
 
-__global__ __launch_bounds__(CGB) void k_cg_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ dinv,
+__global__ __launch_bounds__(SVB) void k_cg_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ dinv,
                                                       const double *__restrict__ prr, const double *__restrict__ prz, int np, CgScal *__restrict__ S)
 {
-    __shared__ double s[CGB / 64];
+    __shared__ double s[SVB / 64];
     const double rho_new = fold(prz, np, s), rho = S->rho;
     const val_t beta = (val_t)((rho > 0.0 && !S->breakdown) ? rho_new / rho : 0.0);
     if (blockIdx.x == 0) {   // what the host reads
         const double rr = dinv ? fold(prr, np, s) : rho_new;
         if (threadIdx.x == 0) { S->rr = rr; S->iterations = S->iterations + 1; }
     }
-    const long long nv = n / CG_VPL;
-    CG_FOR_TRIPS(base) {
-        cvec_t vr[CG_U], vp[CG_U], vd[CG_U];
+    const long long nv = n / SV_VPL;
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t vr[SV_U], vp[SV_U], vd[SV_U];
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                vr[u] = reinterpret_cast<const cvec_t *>(r)[v]; vp[u] = reinterpret_cast<const cvec_t *>(p)[v];
-                if (dinv) vd[u] = reinterpret_cast<const cvec_t *>(dinv)[v];
+                vr[u] = lanes(r)[v]; vp[u] = lanes(p)[v];
+                if (dinv) vd[u] = lanes(dinv)[v];
             }
         }
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const cvec_t z = dinv ? vd[u] * vr[u] : vr[u];
-                reinterpret_cast<cvec_t *>(p)[v] = z + beta * vp[u];
+                const svec_t z = dinv ? vd[u] * vr[u] : vr[u];
+                lanes(p)[v] = z + beta * vp[u];
             }
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * CG_VPL; i < n; i++) p[i] = (dinv ? (val_t)(dinv[i] * r[i]) : r[i]) + beta * p[i];
+        for (long long i = nv * SV_VPL; i < n; i++) p[i] = (dinv ? (val_t)(dinv[i] * r[i]) : r[i]) + beta * p[i];
 }
 
 // the start of a solve: r = b - A x (Ax holds the product), p = z, partial sums of r.r, r.z and b.b
-__global__ __launch_bounds__(CGB) void k_cg_begin(long long n, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, val_t *__restrict__ p,
+__global__ __launch_bounds__(SVB) void k_cg_begin(long long n, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, val_t *__restrict__ p,
                                                   const val_t *__restrict__ dinv, double *__restrict__ prr, double *__restrict__ prz, double *__restrict__ pbb)
 {
-    __shared__ double s[CGB / 64];
-    const long long nv = n / CG_VPL;
+    __shared__ double s[SVB / 64];
+    const long long nv = n / SV_VPL;
     double arr = 0.0, arz = 0.0, abb = 0.0;
-    CG_FOR_TRIPS(base) {
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const cvec_t vb = reinterpret_cast<const cvec_t *>(b)[v], nr = vb - reinterpret_cast<const cvec_t *>(Ax)[v];
-                const cvec_t z = dinv ? reinterpret_cast<const cvec_t *>(dinv)[v] * nr : nr;
-                reinterpret_cast<cvec_t *>(r)[v] = nr;
-                reinterpret_cast<cvec_t *>(p)[v] = z;
+                const svec_t vb = lanes(b)[v], nr = vb - lanes(Ax)[v];
+                const svec_t z = dinv ? lanes(dinv)[v] * nr : nr;
+                lanes(r)[v] = nr;
+                lanes(p)[v] = z;
 #pragma unroll
-                for (int q = 0; q < CG_VPL; q++) {
+                for (int q = 0; q < SV_VPL; q++) {
                     arr += (double)nr[q] * (double)nr[q];
                     arz += (double)nr[q] * (double)z[q];
                     abb += (double)vb[q] * (double)vb[q];
@@ -213,7 +168,7 @@ __global__ __launch_bounds__(CGB) void k_cg_begin(long long n, const val_t *__re
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * CG_VPL; i < n; i++) {
+        for (long long i = nv * SV_VPL; i < n; i++) {
             const val_t nr = b[i] - Ax[i], z = dinv ? (val_t)(dinv[i] * nr) : nr;
             r[i] = nr; p[i] = z;
             arr += (double)nr * (double)nr; arz += (double)nr * (double)z; abb += (double)b[i] * (double)b[i];
@@ -225,26 +180,24 @@ __global__ __launch_bounds__(CGB) void k_cg_begin(long long n, const val_t *__re
     }
 }
 // ... and its scalars (one workgroup)
-__global__ __launch_bounds__(CGB) void k_cg_begin_fold(const double *__restrict__ prr, const double *__restrict__ prz, const double *__restrict__ pbb, int np, CgScal *__restrict__ S)
+__global__ __launch_bounds__(SVB) void k_cg_begin_fold(const double *__restrict__ prr, const double *__restrict__ prz, const double *__restrict__ pbb, int np, CgScal *__restrict__ S)
 {
-    __shared__ double s[CGB / 64];
+    __shared__ double s[SVB / 64];
     const double rr = fold(prr, np, s), rz = fold(prz, np, s), bb = fold(pbb, np, s);
     if (threadIdx.x == 0) { S->rho = rz; S->rr = rr; S->bb = bb; S->iterations = 0; S->breakdown = 0; }
 }
 
 // one row per thread: the stored entries (i, i), added in storage order
-__global__ __launch_bounds__(CGB) void k_csr_diagonal(int rows, const int *__restrict__ rp, const int *__restrict__ ci, const val_t *__restrict__ v, val_t *__restrict__ out, int invert)
+__global__ __launch_bounds__(SVB) void k_csr_diagonal(int rows, const int *__restrict__ rp, const int *__restrict__ ci, const val_t *__restrict__ v, val_t *__restrict__ out, int invert)
 {
-    const long long i = (long long)blockIdx.x * CGB + threadIdx.x;
+    const long long i = (long long)blockIdx.x * SVB + threadIdx.x;
     if (i >= rows) return;
     double a = 0.0;
     for (long long k = rp[i]; k < rp[i + 1]; k++)
         if (ci[k] == (int)i) a += (double)v[k];
     const val_t d = (val_t)a;
-    out[i] = !invert ? d : d == (val_t)0 ? (val_t)1 : (val_t)1 / d;
+    out[i] = !invert ? d : SV_INVERSE_OR_ONE(d);
 }
-
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15u) != 0; }
 
 }  // namespace
 }  // namespace tilespmv
@@ -267,29 +220,23 @@ extern "C" int tilespmv_cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const M
     if (cg) *cg = nullptr;
     if (!cg || !plan) return (int)hipErrorInvalidValue;
     const long long n = plan->matrix_rows;
-    if (n <= 0 || plan->dev.colA != n || plan->dev.f_row0 != 0 || plan->dev.f_rows != n) return (int)hipErrorInvalidValue;   // square, whole matrix
+    if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
     if (misaligned(d_dinv)) return (int)hipErrorInvalidValue;
-    const size_t vec = ((size_t)(n + 16) * sizeof(val_t) + 255) / 256 * 256, parts = (size_t)CG_MAX_PARTS * sizeof(double);
-    const size_t bytes = 3 * vec + 4 * parts + 256;
-    void *blk = nullptr;
-    hipError_t e = hipMalloc(&blk, bytes);
-    if (e == hipSuccess) e = hipMemset(blk, 0, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (blk) (void)hipFree(blk);
-        return (int)e;
-    }
+    const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    DeviceBlock blk;
+    const hipError_t e = blk.alloc(3 * vec + 4 * parts + 256);
+    if (e != hipSuccess) return (int)e;
     auto *c = new tilespmv_cg();
-    c->plan = plan; c->n = n; c->np = cg_parts(n); c->dinv = d_dinv; c->block = blk;
-    char *at = (char *)blk;
-    c->r = (val_t *)at; at += vec;
-    c->p = (val_t *)at; at += vec;
-    c->Ap = (val_t *)at; at += vec;
-    c->ppap = (double *)at; at += parts;
-    c->prr = (double *)at; at += parts;
-    c->prz = d_dinv ? (double *)at : c->prr; at += parts;
-    c->pbb = (double *)at; at += parts;
-    c->S = (CgScal *)at;
+    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->block = blk.base;
+    c->r = blk.take<val_t>(vec);
+    c->p = blk.take<val_t>(vec);
+    c->Ap = blk.take<val_t>(vec);
+    c->ppap = blk.take<double>(parts);
+    c->prr = blk.take<double>(parts);
+    double *const rz = blk.take<double>(parts);
+    c->prz = d_dinv ? rz : c->prr;
+    c->pbb = blk.take<double>(parts);
+    c->S = blk.take<CgScal>(256);
     *cg = c;
     return 0;
 }
@@ -307,8 +254,8 @@ extern "C" int tilespmv_cg_begin(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_V
     const hipStream_t st = (hipStream_t)stream;
     const int rc = tilespmv_plan_spmv(cg->plan, d_x, cg->Ap, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_cg_begin, dim3(cg->np), dim3(CGB), 0, st, cg->n, d_b, cg->Ap, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->pbb);
-    hipLaunchKernelGGL(k_cg_begin_fold, dim3(1), dim3(CGB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->S);
+    hipLaunchKernelGGL(k_cg_begin, dim3(cg->np), dim3(SVB), 0, st, cg->n, d_b, cg->Ap, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->pbb);
+    hipLaunchKernelGGL(k_cg_begin_fold, dim3(1), dim3(SVB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->S);
     return (int)hipGetLastError();
 }
 
@@ -319,9 +266,9 @@ extern "C" int tilespmv_cg_iterate(tilespmv_cg *cg, MAT_VAL_TYPE *d_x, int count
     for (int i = 0; i < count; i++) {
         const int rc = tilespmv_plan_spmv(cg->plan, cg->p, cg->Ap, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_cg_dot, dim3(cg->np), dim3(CGB), 0, st, cg->n, cg->p, cg->Ap, cg->ppap, cg->prz, cg->np, cg->S);
-        hipLaunchKernelGGL(k_cg_update, dim3(cg->np), dim3(CGB), 0, st, cg->n, cg->p, cg->Ap, d_x, cg->r, cg->dinv, cg->ppap, cg->prr, cg->prz, cg->np, cg->S);
-        hipLaunchKernelGGL(k_cg_direction, dim3(cg->np), dim3(CGB), 0, st, cg->n, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->np, cg->S);
+        hipLaunchKernelGGL(k_cg_dot, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->p, cg->Ap, cg->ppap, cg->prz, cg->np, cg->S);
+        hipLaunchKernelGGL(k_cg_update, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->p, cg->Ap, d_x, cg->r, cg->dinv, cg->ppap, cg->prr, cg->prz, cg->np, cg->S);
+        hipLaunchKernelGGL(k_cg_direction, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->np, cg->S);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -331,17 +278,14 @@ extern "C" int tilespmv_cg_iterate(tilespmv_cg *cg, MAT_VAL_TYPE *d_x, int count
 extern "C" int tilespmv_cg_state_read(tilespmv_cg *cg, void *stream, tilespmv_cg_state *out)
 {
     if (!cg || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
-    const hipStream_t st = (hipStream_t)stream;
     CgScal h;
-    hipError_t e = hipMemcpyAsync(&h, cg->S, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    const hipError_t e = read_scalars(&h, cg->S, sizeof(h), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
     tilespmv_cg_state s;
-    s.size = out->size;
     s.iterations = h.iterations;
     s.status = h.breakdown ? TILESPMV_CG_BREAKDOWN : h.rr == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
     s.rr = h.rr; s.bb = h.bb;
-    memcpy(out, &s, std::min<size_t>(out->size, sizeof(s)));   // (a caller built against a shorter struct gets the fields it knows)
+    put_versioned(out, out->size, 0, s);
     return 0;
 }
 
@@ -375,6 +319,6 @@ extern "C" int tilespmv_csr_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrR
     if (rows < 0 || (rows > 0 && (!d_csrRowPtr || !d_csrColIdx || !d_csrVal || !d_out))) return (int)hipErrorInvalidValue;
     if (tilespmv_device_count() <= 0) return (int)hipErrorNoDevice;
     if (rows > 0)
-        hipLaunchKernelGGL(k_csr_diagonal, dim3((unsigned)((rows + CGB - 1) / CGB)), dim3(CGB), 0, (hipStream_t)stream, rows, d_csrRowPtr, d_csrColIdx, d_csrVal, d_out, invert);
+        hipLaunchKernelGGL(k_csr_diagonal, dim3((unsigned)((rows + SVB - 1) / SVB)), dim3(SVB), 0, (hipStream_t)stream, rows, d_csrRowPtr, d_csrColIdx, d_csrVal, d_out, invert);
     return (int)hipGetLastError();
 }

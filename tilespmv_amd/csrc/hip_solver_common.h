@@ -1,0 +1,114 @@
+// hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip): the launch shape, the number of
+// partial sums, the reduction tree, the walk over a vector, and the host-side handling of the one allocation and of the versioned state structs.
+//
+// No scalar ever visits the host: a reducing kernel writes one partial per workgroup and the CONSUMING kernel folds the partials itself — every workgroup the same additions in the
+// same order, so all of them hold the same bits of the scalar; no finishing launch, no atomics.  The number of partials (solver_parts) and which elements a thread adds depend on the
+// vector's length alone, the wave and workgroup reductions are fixed trees: the order of every sum is fixed by the problem size.  Partial sums and scalars are double in both builds.
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+
+#include "hip_plan_internal.h"
+
+namespace tilespmv {
+namespace {
+
+constexpr int SVB = 256;                              // threads per workgroup
+constexpr int SV_VPL = 16 / (int)sizeof(val_t);       // elements per 16-byte lane load (2 in fp64, 4 in fp32)
+constexpr int SV_U = 2;                               // lane vectors per lane and trip: a workgroup's trip covers SV_U * SVB consecutive lane vectors
+constexpr int SV_MAX_PARTS = 1024;                    // partial sums = workgroups of the streaming kernels: 4 per CU on 256 CUs
+typedef val_t svec_t __attribute__((ext_vector_type(SV_VPL)));
+
+// workgroups (= partial sums) for a stream of `elements` values: a function of that length alone
+inline int solver_parts(long long elements)
+{
+    const long long trips = (elements / SV_VPL + (long long)SV_U * SVB - 1) / ((long long)SV_U * SVB);
+    return (int)std::max<long long>(1, std::min<long long>(SV_MAX_PARTS, trips));
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+// the workgroup's sum, returned to every thread: wave trees, then the four wave sums in wave order
+__device__ __forceinline__ double block_sum(double v, double *s)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double t = ((s[0] + s[1]) + s[2]) + s[3];
+    __syncthreads();
+    return t;
+}
+// the sum of np partials, the same additions in every workgroup
+__device__ __forceinline__ double fold(const double *__restrict__ part, int np, double *s)
+{
+    double a = 0.0;
+    for (int i = threadIdx.x; i < np; i += SVB) a += part[i];
+    return block_sum(a, s);
+}
+
+// a vector as its 16-byte lane vectors
+__device__ __forceinline__ svec_t *lanes(val_t *p) { return reinterpret_cast<svec_t *>(p); }
+__device__ __forceinline__ const svec_t *lanes(const val_t *p) { return reinterpret_cast<const svec_t *>(p); }
+
+// Element ranges of a vector of n elements served by nwg workgroups: the full lane vectors [0, nv), nv = n / SV_VPL, are walked in trips of SV_U * SVB by workgroup blockIdx.x,
+// blockIdx.x + nwg, ...; the n % SV_VPL elements behind them belong to thread 0 of workgroup 0 (scalar accesses: nothing past element n - 1 of a caller's vector is touched).
+// nwg is gridDim.x, or less: then the kernel keeps the workgroups from nwg on out of the walk itself (no guard here: it would cost the kernels that need none).
+#define SV_FOR_TRIPS(base, nv, nwg) for (long long base = (long long)blockIdx.x * (SV_U * SVB) + threadIdx.x; base < (nv); base += (long long)(nwg) * (SV_U * SVB))
+
+// the tail of the k_csr_* kernels under `invert`: 1 / d, 1 where d is 0 (a macro: as an inlined function it reaches the kernels as a select, and their code changes)
+#define SV_INVERSE_OR_ONE(d) ((d) == (val_t)0 ? (val_t)1 : (val_t)1 / (d))
+
+inline bool misaligned(const void *p) { return ((uintptr_t)p & 15u) != 0; }
+// the plan of a whole rows x cols matrix (no shard)
+inline bool whole_plan(const tilespmv_plan *plan, long long rows, long long cols)
+{
+    return plan->matrix_rows == rows && plan->dev.colA == cols && plan->dev.f_row0 == 0 && plan->dev.f_rows == rows;
+}
+// bytes of a work vector of rows x nvec elements inside a solver's allocation: 16 rows of slack, rounded to 256
+inline size_t vec_bytes(long long rows, int nvec = 1) { return ((size_t)(rows + 16) * nvec * sizeof(val_t) + 255) / 256 * 256; }
+
+// A solver's one allocation: zeroed, then handed out in consecutive pieces (the caller adds up their sizes; multiples of 256 keep every piece aligned).  A failed alloc leaves nothing.
+struct DeviceBlock {
+    char *base = nullptr, *at = nullptr;
+    hipError_t alloc(size_t bytes)
+    {
+        hipError_t e = hipMalloc((void **)&base, bytes);
+        if (e == hipSuccess) e = hipMemset(base, 0, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (base) (void)hipFree(base);
+            base = nullptr;
+        }
+        at = base;
+        return e;
+    }
+    template <class T> T *take(size_t bytes)
+    {
+        T *p = (T *)at;
+        at += bytes;
+        return p;
+    }
+};
+
+// a scalar block on the host, after a synchronisation of the stream
+inline hipError_t read_scalars(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+// element j of a caller's array of state structs whose elements are `stride` bytes apart (a caller built against a shorter struct gets the fields it knows)
+template <class State> void put_versioned(State *out, unsigned stride, int j, State s)
+{
+    s.size = stride;
+    memcpy((char *)out + (size_t)j * stride, &s, std::min<size_t>(stride, sizeof(s)));
+}
+
+}  // namespace
+}  // namespace tilespmv

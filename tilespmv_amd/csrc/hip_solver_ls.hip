@@ -11,10 +11,10 @@
 // damping adds 3 cols (p in the dot; x read and s stored in the normal pass), cinv adds 2 cols (read in the normal and the direction pass).
 // The loop of torch operations it replaces (operator.cgls) moves 7 rows + 12 cols in about a dozen launches.
 //
-// No scalar ever visits the host: a reducing kernel writes one partial per workgroup and the CONSUMING kernel folds the partials itself, every workgroup the same additions in the
-// same order — no finishing launch, no atomics.  Row-length sums (q.q, r.r, b.b) have ls_parts(rows) partials, column-length sums (p.p, s.s, s.z) ls_parts(cols), and which
-// elements a thread adds depends on that length alone; the wave and workgroup reductions are fixed trees.  Sums and scalars are double in both builds; alpha, beta and damp^2 are
-// rounded to the value type once, where they multiply.
+// The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail are those of hip_solver_common.h.  Row-length sums
+// (q.q, r.r, b.b) have npr = solver_parts(rows) partials, column-length sums (p.p, s.s, s.z) npc = solver_parts(cols).  A kernel that walks both lengths is launched over
+// max(npr, npc) workgroups, so every walk here is guarded: the workgroups from the vector's own count on skip it.  alpha, beta and damp^2 are rounded to the value type once,
+// where they multiply.
 //
 // The scalar block (LsScal) has ONE writing kernel per field and no kernel reads a field it (or a concurrent workgroup of it) writes:
 //   gamma            k_ls_dot, workgroup 0 (fold of the s.z partials the previous normal pass left; 0 after a breakdown)    read by k_ls_update, k_ls_direction
@@ -26,91 +26,43 @@
 // delta > 0 -> breakdown is set, alpha = beta = 0 in this and every later iteration, x keeps its last good value.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "hip_plan_internal.h"
+#include "hip_solver_common.h"
 
 namespace tilespmv {
 namespace {
-
-constexpr int LSB = 256;                              // threads per workgroup
-constexpr int LS_VPL = 16 / (int)sizeof(val_t);       // elements per 16-byte lane load (2 in fp64, 4 in fp32)
-constexpr int LS_U = 2;                               // vectors per lane and trip: a workgroup's trip covers LS_U * LSB consecutive vectors
-constexpr int LS_MAX_PARTS = 1024;                    // partial sums = workgroups of the streaming kernels: 4 per CU on 256 CUs
-typedef val_t lvec_t __attribute__((ext_vector_type(LS_VPL)));
 
 struct LsScal {
     double gamma, nn, nn0, rr, bb, damp2;
     int iterations, breakdown;
 };
 
-// workgroups (= partial sums) for a vector of n elements: a function of n alone
-inline int ls_parts(long long n)
-{
-    const long long trips = (n / LS_VPL + (long long)LS_U * LSB - 1) / ((long long)LS_U * LSB);
-    return (int)std::max<long long>(1, std::min<long long>(LS_MAX_PARTS, trips));
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-// the workgroup's sum, returned to every thread: wave trees, then the four wave sums in wave order
-__device__ __forceinline__ double block_sum(double v, double *s)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = ((s[0] + s[1]) + s[2]) + s[3];
-    __syncthreads();
-    return t;
-}
-// the sum of np partials, the same additions in every workgroup
-__device__ __forceinline__ double fold(const double *__restrict__ part, int np, double *s)
-{
-    double a = 0.0;
-    for (int i = threadIdx.x; i < np; i += LSB) a += part[i];
-    return block_sum(a, s);
-}
-
-// Element ranges of a vector of n elements served by nwg workgroups (nwg = ls_parts(n); a launch over both lengths has max(npr, npc) workgroups and the ones beyond nwg skip the
-// vector): full 16-byte vectors [0, nv) are walked in trips of LS_U * LSB by workgroup blockIdx.x, blockIdx.x + nwg, ...; the n % LS_VPL elements behind them belong to thread 0
-// of workgroup 0 (scalar accesses: nothing past element n - 1 of a caller's vector is touched).
-#define LS_FOR_TRIPS(base, nv, nwg) \
-    if ((int)blockIdx.x < (nwg))    \
-        for (long long base = (long long)blockIdx.x * (LS_U * LSB) + threadIdx.x; base < (nv); base += (long long)(nwg) * (LS_U * LSB))
-#define LS_V(ptr) reinterpret_cast<lvec_t *>(ptr)
-#define LS_CV(ptr) reinterpret_cast<const lvec_t *>(ptr)
-
 // partial sums of v.v over n elements
 __device__ __forceinline__ double sq_partial(long long n, const val_t *__restrict__ v, int nwg)
 {
-    const long long nv = n / LS_VPL;
+    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    LS_FOR_TRIPS(base, nv, nwg) {
-        lvec_t a[LS_U];
+    if ((int)blockIdx.x < nwg) SV_FOR_TRIPS(base, nv, nwg) {
+        svec_t a[SV_U];
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long i = base + u * LSB;
-            if (i < nv) a[u] = LS_CV(v)[i];
+        for (int u = 0; u < SV_U; u++) {
+            const long long i = base + u * SVB;
+            if (i < nv) a[u] = lanes(v)[i];
             else a[u] = (val_t)0;
         }
 #pragma unroll
-        for (int u = 0; u < LS_U; u++)
+        for (int u = 0; u < SV_U; u++)
 #pragma unroll
-            for (int k = 0; k < LS_VPL; k++) acc += (double)a[u][k] * (double)a[u][k];
+            for (int k = 0; k < SV_VPL; k++) acc += (double)a[u][k] * (double)a[u][k];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * LS_VPL; i < n; i++) acc += (double)v[i] * (double)v[i];
+        for (long long i = nv * SV_VPL; i < n; i++) acc += (double)v[i] * (double)v[i];
     return acc;
 }
 
-__global__ __launch_bounds__(LSB) void k_ls_dot(long long rows, long long cols, const val_t *__restrict__ q, const val_t *__restrict__ p, double *__restrict__ pqq,
+__global__ __launch_bounds__(SVB) void k_ls_dot(long long rows, long long cols, const val_t *__restrict__ q, const val_t *__restrict__ p, double *__restrict__ pqq,
                                                 double *__restrict__ ppp, const double *__restrict__ psz, int npr, int npc, LsScal *__restrict__ S)
 {
-    __shared__ double s[LSB / 64];
+    __shared__ double s[SVB / 64];
     const bool damped = S->damp2 != 0.0;
     const double tq = block_sum(sq_partial(rows, q, npr), s);
     if (threadIdx.x == 0 && (int)blockIdx.x < npr) pqq[blockIdx.x] = tq;
@@ -124,53 +76,53 @@ __global__ __launch_bounds__(LSB) void k_ls_dot(long long rows, long long cols, 
     }
 }
 
-__global__ __launch_bounds__(LSB) void k_ls_update(long long rows, long long cols, const val_t *__restrict__ p, const val_t *__restrict__ q, val_t *__restrict__ x,
+__global__ __launch_bounds__(SVB) void k_ls_update(long long rows, long long cols, const val_t *__restrict__ p, const val_t *__restrict__ q, val_t *__restrict__ x,
                                                    val_t *__restrict__ r, const double *__restrict__ pqq, const double *__restrict__ ppp, double *__restrict__ prr, int npr, int npc,
                                                    LsScal *__restrict__ S)
 {
-    __shared__ double s[LSB / 64];
+    __shared__ double s[SVB / 64];
     const double d2 = S->damp2, gamma = S->gamma;
     double delta = fold(pqq, npr, s);
     if (d2 != 0.0) delta += d2 * fold(ppp, npc, s);
     const bool broke = gamma < 0.0 || (gamma > 0.0 && !(delta > 0.0));
     const val_t alpha = (val_t)((gamma > 0.0 && delta > 0.0) ? gamma / delta : 0.0);
     if (broke && blockIdx.x == 0 && threadIdx.x == 0) S->breakdown = 1;
-    const long long nvc = cols / LS_VPL, nvr = rows / LS_VPL;
-    LS_FOR_TRIPS(base, nvc, npc) {
-        lvec_t vp[LS_U], vx[LS_U];
+    const long long nvc = cols / SV_VPL, nvr = rows / SV_VPL;
+    if ((int)blockIdx.x < npc) SV_FOR_TRIPS(base, nvc, npc) {
+        svec_t vp[SV_U], vx[SV_U];
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
-            if (v < nvc) { vp[u] = LS_CV(p)[v]; vx[u] = LS_CV(x)[v]; }
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nvc) { vp[u] = lanes(p)[v]; vx[u] = lanes(x)[v]; }
         }
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
-            if (v < nvc) LS_V(x)[v] = vx[u] + alpha * vp[u];
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nvc) lanes(x)[v] = vx[u] + alpha * vp[u];
         }
     }
     double arr = 0.0;
-    LS_FOR_TRIPS(base, nvr, npr) {
-        lvec_t vq[LS_U], vr[LS_U];
+    if ((int)blockIdx.x < npr) SV_FOR_TRIPS(base, nvr, npr) {
+        svec_t vq[SV_U], vr[SV_U];
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
-            if (v < nvr) { vq[u] = LS_CV(q)[v]; vr[u] = LS_CV(r)[v]; }
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nvr) { vq[u] = lanes(q)[v]; vr[u] = lanes(r)[v]; }
         }
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nvr) {
-                const lvec_t nr = vr[u] - alpha * vq[u];
-                LS_V(r)[v] = nr;
+                const svec_t nr = vr[u] - alpha * vq[u];
+                lanes(r)[v] = nr;
 #pragma unroll
-                for (int k = 0; k < LS_VPL; k++) arr += (double)nr[k] * (double)nr[k];
+                for (int k = 0; k < SV_VPL; k++) arr += (double)nr[k] * (double)nr[k];
             }
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (long long i = nvc * LS_VPL; i < cols; i++) x[i] = x[i] + alpha * p[i];
-        for (long long i = nvr * LS_VPL; i < rows; i++) {
+        for (long long i = nvc * SV_VPL; i < cols; i++) x[i] = x[i] + alpha * p[i];
+        for (long long i = nvr * SV_VPL; i < rows; i++) {
             const val_t nr = r[i] - alpha * q[i];
             r[i] = nr;
             arr += (double)nr * (double)nr;
@@ -182,36 +134,36 @@ __global__ __launch_bounds__(LSB) void k_ls_update(long long rows, long long col
 
 // The normal residual s = A^T r (the product left it) - damp^2 x, its squared norm and s.z.  plain != 0: s as it stands, no damping, no cinv (|A^T b|^2 at the start of a solve).
 // p_out != NULL (the start of a solve): p = z as well.
-__global__ __launch_bounds__(LSB) void k_ls_normal(long long cols, val_t *__restrict__ sv, const val_t *__restrict__ x, const val_t *__restrict__ cinv_, double *__restrict__ pss,
+__global__ __launch_bounds__(SVB) void k_ls_normal(long long cols, val_t *__restrict__ sv, const val_t *__restrict__ x, const val_t *__restrict__ cinv_, double *__restrict__ pss,
                                                    double *__restrict__ psz, val_t *__restrict__ p_out, int plain, int npc, const LsScal *__restrict__ S)
 {
-    __shared__ double s[LSB / 64];
+    __shared__ double s[SVB / 64];
     const val_t d2 = plain ? (val_t)0 : (val_t)S->damp2;
     const val_t *__restrict__ cinv = plain ? nullptr : cinv_;
     const bool damped = d2 != (val_t)0;
-    const long long nv = cols / LS_VPL;
+    const long long nv = cols / SV_VPL;
     double ass = 0.0, asz = 0.0;
-    LS_FOR_TRIPS(base, nv, npc) {
-        lvec_t vs[LS_U], vx[LS_U], vc[LS_U];
+    if ((int)blockIdx.x < npc) SV_FOR_TRIPS(base, nv, npc) {
+        svec_t vs[SV_U], vx[SV_U], vc[SV_U];
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                vs[u] = LS_CV(sv)[v];
-                if (damped) vx[u] = LS_CV(x)[v];
-                if (cinv) vc[u] = LS_CV(cinv)[v];
+                vs[u] = lanes(sv)[v];
+                if (damped) vx[u] = lanes(x)[v];
+                if (cinv) vc[u] = lanes(cinv)[v];
             }
         }
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                lvec_t ns = vs[u];
-                if (damped) { ns = vs[u] - d2 * vx[u]; LS_V(sv)[v] = ns; }
-                const lvec_t z = cinv ? vc[u] * ns : ns;
-                if (p_out) LS_V(p_out)[v] = z;
+                svec_t ns = vs[u];
+                if (damped) { ns = vs[u] - d2 * vx[u]; lanes(sv)[v] = ns; }
+                const svec_t z = cinv ? vc[u] * ns : ns;
+                if (p_out) lanes(p_out)[v] = z;
 #pragma unroll
-                for (int k = 0; k < LS_VPL; k++) {
+                for (int k = 0; k < SV_VPL; k++) {
                     ass += (double)ns[k] * (double)ns[k];
                     if (cinv) asz += (double)ns[k] * (double)z[k];
                 }
@@ -219,7 +171,7 @@ __global__ __launch_bounds__(LSB) void k_ls_normal(long long cols, val_t *__rest
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * LS_VPL; i < cols; i++) {
+        for (long long i = nv * SV_VPL; i < cols; i++) {
             val_t ns = sv[i];
             if (damped) { ns = ns - d2 * x[i]; sv[i] = ns; }
             const val_t z = cinv ? (val_t)(cinv[i] * ns) : ns;
@@ -235,57 +187,57 @@ __global__ __launch_bounds__(LSB) void k_ls_normal(long long cols, val_t *__rest
     }
 }
 
-__global__ __launch_bounds__(LSB) void k_ls_direction(long long cols, const val_t *__restrict__ sv, val_t *__restrict__ p, const val_t *__restrict__ cinv,
+__global__ __launch_bounds__(SVB) void k_ls_direction(long long cols, const val_t *__restrict__ sv, val_t *__restrict__ p, const val_t *__restrict__ cinv,
                                                       const double *__restrict__ pss, const double *__restrict__ psz, const double *__restrict__ prr, int npr, int npc,
                                                       LsScal *__restrict__ S)
 {
-    __shared__ double s[LSB / 64];
+    __shared__ double s[SVB / 64];
     const double g_new = fold(psz, npc, s), gamma = S->gamma;
     const val_t beta = (val_t)((gamma > 0.0 && !S->breakdown) ? g_new / gamma : 0.0);
     if (blockIdx.x == 0) {   // what the host reads
         const double nn = cinv ? fold(pss, npc, s) : g_new, rr = fold(prr, npr, s);
         if (threadIdx.x == 0) { S->nn = nn; S->rr = rr; S->iterations = S->iterations + 1; }
     }
-    const long long nv = cols / LS_VPL;
-    LS_FOR_TRIPS(base, nv, npc) {
-        lvec_t vs[LS_U], vp[LS_U], vc[LS_U];
+    const long long nv = cols / SV_VPL;
+    if ((int)blockIdx.x < npc) SV_FOR_TRIPS(base, nv, npc) {
+        svec_t vs[SV_U], vp[SV_U], vc[SV_U];
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                vs[u] = LS_CV(sv)[v]; vp[u] = LS_CV(p)[v];
-                if (cinv) vc[u] = LS_CV(cinv)[v];
+                vs[u] = lanes(sv)[v]; vp[u] = lanes(p)[v];
+                if (cinv) vc[u] = lanes(cinv)[v];
             }
         }
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const lvec_t z = cinv ? vc[u] * vs[u] : vs[u];
-                LS_V(p)[v] = z + beta * vp[u];
+                const svec_t z = cinv ? vc[u] * vs[u] : vs[u];
+                lanes(p)[v] = z + beta * vp[u];
             }
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * LS_VPL; i < cols; i++) p[i] = (cinv ? (val_t)(cinv[i] * sv[i]) : sv[i]) + beta * p[i];
+        for (long long i = nv * SV_VPL; i < cols; i++) p[i] = (cinv ? (val_t)(cinv[i] * sv[i]) : sv[i]) + beta * p[i];
 }
 
 // the start of a solve: r = b - A x (Ax holds the product), partial sums of r.r and b.b; the damping of this solve goes into the scalar block
-__global__ __launch_bounds__(LSB) void k_ls_begin_r(long long rows, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, double *__restrict__ prr,
+__global__ __launch_bounds__(SVB) void k_ls_begin_r(long long rows, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, double *__restrict__ prr,
                                                     double *__restrict__ pbb, double damp2, int npr, LsScal *__restrict__ S)
 {
-    __shared__ double s[LSB / 64];
-    const long long nv = rows / LS_VPL;
+    __shared__ double s[SVB / 64];
+    const long long nv = rows / SV_VPL;
     double arr = 0.0, abb = 0.0;
-    LS_FOR_TRIPS(base, nv, npr) {
+    if ((int)blockIdx.x < npr) SV_FOR_TRIPS(base, nv, npr) {
 #pragma unroll
-        for (int u = 0; u < LS_U; u++) {
-            const long long v = base + u * LSB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const lvec_t vb = LS_CV(b)[v], nr = vb - LS_CV(Ax)[v];
-                LS_V(r)[v] = nr;
+                const svec_t vb = lanes(b)[v], nr = vb - lanes(Ax)[v];
+                lanes(r)[v] = nr;
 #pragma unroll
-                for (int k = 0; k < LS_VPL; k++) {
+                for (int k = 0; k < SV_VPL; k++) {
                     arr += (double)nr[k] * (double)nr[k];
                     abb += (double)vb[k] * (double)vb[k];
                 }
@@ -293,7 +245,7 @@ __global__ __launch_bounds__(LSB) void k_ls_begin_r(long long rows, const val_t 
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (long long i = nv * LS_VPL; i < rows; i++) {
+        for (long long i = nv * SV_VPL; i < rows; i++) {
             const val_t nr = b[i] - Ax[i];
             r[i] = nr;
             arr += (double)nr * (double)nr; abb += (double)b[i] * (double)b[i];
@@ -304,19 +256,19 @@ __global__ __launch_bounds__(LSB) void k_ls_begin_r(long long rows, const val_t 
     if (threadIdx.x == 0) { prr[blockIdx.x] = trr; pbb[blockIdx.x] = tbb; }
 }
 // ... and its scalars (one workgroup)
-__global__ __launch_bounds__(LSB) void k_ls_begin_fold(const double *__restrict__ pss, const double *__restrict__ psz, const double *__restrict__ pn0, const double *__restrict__ prr,
+__global__ __launch_bounds__(SVB) void k_ls_begin_fold(const double *__restrict__ pss, const double *__restrict__ psz, const double *__restrict__ pn0, const double *__restrict__ prr,
                                                        const double *__restrict__ pbb, int npr, int npc, LsScal *__restrict__ S)
 {
-    __shared__ double s[LSB / 64];
+    __shared__ double s[SVB / 64];
     const double ss = fold(pss, npc, s), sz = fold(psz, npc, s), n0 = fold(pn0, npc, s), rr = fold(prr, npr, s), bb = fold(pbb, npr, s);
     if (threadIdx.x == 0) { S->gamma = sz; S->nn = ss; S->nn0 = n0; S->rr = rr; S->bb = bb; S->iterations = 0; S->breakdown = 0; }
 }
 
 // one row per thread: the squares of the row's stored values, added in storage order (through src: the rows of A^T as positions of A's value array = A's column norms)
-__global__ __launch_bounds__(LSB) void k_csr_row_sqnorms(int rows, const int *__restrict__ rp, const int *__restrict__ src, const val_t *__restrict__ v, val_t *__restrict__ out,
+__global__ __launch_bounds__(SVB) void k_csr_row_sqnorms(int rows, const int *__restrict__ rp, const int *__restrict__ src, const val_t *__restrict__ v, val_t *__restrict__ out,
                                                          int invert)
 {
-    const long long i = (long long)blockIdx.x * LSB + threadIdx.x;
+    const long long i = (long long)blockIdx.x * SVB + threadIdx.x;
     if (i >= rows) return;
     double a = 0.0;
     for (long long k = rp[i]; k < rp[i + 1]; k++) {
@@ -324,13 +276,7 @@ __global__ __launch_bounds__(LSB) void k_csr_row_sqnorms(int rows, const int *__
         a += e * e;
     }
     const val_t d = (val_t)a;
-    out[i] = !invert ? d : d == (val_t)0 ? (val_t)1 : (val_t)1 / d;
-}
-
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15u) != 0; }
-inline bool whole(const tilespmv_plan *plan, long long rows, long long cols)
-{
-    return plan->matrix_rows == rows && plan->dev.colA == cols && plan->dev.f_row0 == 0 && plan->dev.f_rows == rows;
+    out[i] = !invert ? d : SV_INVERSE_OR_ONE(d);
 }
 
 }  // namespace
@@ -354,35 +300,28 @@ extern "C" int tilespmv_cgls_create(tilespmv_cgls **ls, tilespmv_plan *plan_A, t
     if (ls) *ls = nullptr;
     if (!ls || !plan_A || !plan_AT) return (int)hipErrorInvalidValue;
     const long long rows = plan_A->matrix_rows, cols = plan_A->dev.colA;
-    if (rows <= 0 || cols <= 0 || !whole(plan_A, rows, cols) || !whole(plan_AT, cols, rows)) return (int)hipErrorInvalidValue;   // whole plans of a rows x cols matrix and its transpose
+    if (rows <= 0 || cols <= 0 || !whole_plan(plan_A, rows, cols) || !whole_plan(plan_AT, cols, rows)) return (int)hipErrorInvalidValue;   // whole plans of a rows x cols matrix and its transpose
     if (misaligned(d_cinv)) return (int)hipErrorInvalidValue;
-    const size_t vr = ((size_t)(rows + 16) * sizeof(val_t) + 255) / 256 * 256, vc = ((size_t)(cols + 16) * sizeof(val_t) + 255) / 256 * 256;
-    const size_t parts = (size_t)LS_MAX_PARTS * sizeof(double);
-    const size_t bytes = 2 * vr + 2 * vc + 7 * parts + 256;
-    void *blk = nullptr;
-    hipError_t e = hipMalloc(&blk, bytes);
-    if (e == hipSuccess) e = hipMemset(blk, 0, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (blk) (void)hipFree(blk);
-        return (int)e;
-    }
+    const size_t vr = vec_bytes(rows), vc = vec_bytes(cols), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    DeviceBlock blk;
+    const hipError_t e = blk.alloc(2 * vr + 2 * vc + 7 * parts + 256);
+    if (e != hipSuccess) return (int)e;
     auto *c = new tilespmv_cgls();
-    c->A = plan_A; c->AT = plan_AT; c->rows = rows; c->cols = cols; c->cinv = d_cinv; c->block = blk;
-    c->npr = ls_parts(rows); c->npc = ls_parts(cols); c->grid = std::max(c->npr, c->npc);
-    char *at = (char *)blk;
-    c->r = (val_t *)at; at += vr;
-    c->q = (val_t *)at; at += vr;
-    c->p = (val_t *)at; at += vc;
-    c->s = (val_t *)at; at += vc;
-    c->pqq = (double *)at; at += parts;
-    c->ppp = (double *)at; at += parts;
-    c->prr = (double *)at; at += parts;
-    c->pss = (double *)at; at += parts;
-    c->psz = d_cinv ? (double *)at : c->pss; at += parts;
-    c->pbb = (double *)at; at += parts;
-    c->pn0 = (double *)at; at += parts;
-    c->S = (LsScal *)at;
+    c->A = plan_A; c->AT = plan_AT; c->rows = rows; c->cols = cols; c->cinv = d_cinv; c->block = blk.base;
+    c->npr = solver_parts(rows); c->npc = solver_parts(cols); c->grid = std::max(c->npr, c->npc);
+    c->r = blk.take<val_t>(vr);
+    c->q = blk.take<val_t>(vr);
+    c->p = blk.take<val_t>(vc);
+    c->s = blk.take<val_t>(vc);
+    c->pqq = blk.take<double>(parts);
+    c->ppp = blk.take<double>(parts);
+    c->prr = blk.take<double>(parts);
+    c->pss = blk.take<double>(parts);
+    double *const sz = blk.take<double>(parts);
+    c->psz = d_cinv ? sz : c->pss;
+    c->pbb = blk.take<double>(parts);
+    c->pn0 = blk.take<double>(parts);
+    c->S = blk.take<LsScal>(256);
     *ls = c;
     return 0;
 }
@@ -400,14 +339,14 @@ extern "C" int tilespmv_cgls_begin(tilespmv_cgls *ls, const MAT_VAL_TYPE *d_b, M
     const hipStream_t st = (hipStream_t)stream;
     int rc = tilespmv_plan_spmv(ls->A, d_x, ls->q, stream);                       // q = A x
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ls_begin_r, dim3(ls->npr), dim3(LSB), 0, st, ls->rows, d_b, ls->q, ls->r, ls->prr, ls->pbb, damp * damp, ls->npr, ls->S);
+    hipLaunchKernelGGL(k_ls_begin_r, dim3(ls->npr), dim3(SVB), 0, st, ls->rows, d_b, ls->q, ls->r, ls->prr, ls->pbb, damp * damp, ls->npr, ls->S);
     rc = tilespmv_plan_spmv(ls->AT, d_b, ls->s, stream);                          // s = A^T b, for |A^T b|^2 alone
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ls_normal, dim3(ls->npc), dim3(LSB), 0, st, ls->cols, ls->s, d_x, ls->cinv, ls->pn0, ls->pn0, (val_t *)nullptr, 1, ls->npc, ls->S);
+    hipLaunchKernelGGL(k_ls_normal, dim3(ls->npc), dim3(SVB), 0, st, ls->cols, ls->s, d_x, ls->cinv, ls->pn0, ls->pn0, (val_t *)nullptr, 1, ls->npc, ls->S);
     rc = tilespmv_plan_spmv(ls->AT, ls->r, ls->s, stream);                        // s = A^T r
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ls_normal, dim3(ls->npc), dim3(LSB), 0, st, ls->cols, ls->s, d_x, ls->cinv, ls->pss, ls->psz, ls->p, 0, ls->npc, ls->S);
-    hipLaunchKernelGGL(k_ls_begin_fold, dim3(1), dim3(LSB), 0, st, ls->pss, ls->psz, ls->pn0, ls->prr, ls->pbb, ls->npr, ls->npc, ls->S);
+    hipLaunchKernelGGL(k_ls_normal, dim3(ls->npc), dim3(SVB), 0, st, ls->cols, ls->s, d_x, ls->cinv, ls->pss, ls->psz, ls->p, 0, ls->npc, ls->S);
+    hipLaunchKernelGGL(k_ls_begin_fold, dim3(1), dim3(SVB), 0, st, ls->pss, ls->psz, ls->pn0, ls->prr, ls->pbb, ls->npr, ls->npc, ls->S);
     return (int)hipGetLastError();
 }
 
@@ -418,12 +357,12 @@ extern "C" int tilespmv_cgls_iterate(tilespmv_cgls *ls, MAT_VAL_TYPE *d_x, int c
     for (int i = 0; i < count; i++) {
         int rc = tilespmv_plan_spmv(ls->A, ls->p, ls->q, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_ls_dot, dim3(ls->grid), dim3(LSB), 0, st, ls->rows, ls->cols, ls->q, ls->p, ls->pqq, ls->ppp, ls->psz, ls->npr, ls->npc, ls->S);
-        hipLaunchKernelGGL(k_ls_update, dim3(ls->grid), dim3(LSB), 0, st, ls->rows, ls->cols, ls->p, ls->q, d_x, ls->r, ls->pqq, ls->ppp, ls->prr, ls->npr, ls->npc, ls->S);
+        hipLaunchKernelGGL(k_ls_dot, dim3(ls->grid), dim3(SVB), 0, st, ls->rows, ls->cols, ls->q, ls->p, ls->pqq, ls->ppp, ls->psz, ls->npr, ls->npc, ls->S);
+        hipLaunchKernelGGL(k_ls_update, dim3(ls->grid), dim3(SVB), 0, st, ls->rows, ls->cols, ls->p, ls->q, d_x, ls->r, ls->pqq, ls->ppp, ls->prr, ls->npr, ls->npc, ls->S);
         rc = tilespmv_plan_spmv(ls->AT, ls->r, ls->s, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_ls_normal, dim3(ls->npc), dim3(LSB), 0, st, ls->cols, ls->s, d_x, ls->cinv, ls->pss, ls->psz, (val_t *)nullptr, 0, ls->npc, ls->S);
-        hipLaunchKernelGGL(k_ls_direction, dim3(ls->npc), dim3(LSB), 0, st, ls->cols, ls->s, ls->p, ls->cinv, ls->pss, ls->psz, ls->prr, ls->npr, ls->npc, ls->S);
+        hipLaunchKernelGGL(k_ls_normal, dim3(ls->npc), dim3(SVB), 0, st, ls->cols, ls->s, d_x, ls->cinv, ls->pss, ls->psz, (val_t *)nullptr, 0, ls->npc, ls->S);
+        hipLaunchKernelGGL(k_ls_direction, dim3(ls->npc), dim3(SVB), 0, st, ls->cols, ls->s, ls->p, ls->cinv, ls->pss, ls->psz, ls->prr, ls->npr, ls->npc, ls->S);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -433,18 +372,15 @@ extern "C" int tilespmv_cgls_iterate(tilespmv_cgls *ls, MAT_VAL_TYPE *d_x, int c
 extern "C" int tilespmv_cgls_state_read(tilespmv_cgls *ls, void *stream, tilespmv_cgls_state *out)
 {
     if (!ls || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
-    const hipStream_t st = (hipStream_t)stream;
     LsScal h;
-    hipError_t e = hipMemcpyAsync(&h, ls->S, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    const hipError_t e = read_scalars(&h, ls->S, sizeof(h), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
     tilespmv_cgls_state s;
     memset(&s, 0, sizeof(s));
-    s.size = out->size;
     s.iterations = h.iterations;
     s.status = h.breakdown ? TILESPMV_CG_BREAKDOWN : h.nn == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
     s.nn = h.nn; s.nn0 = h.nn0; s.rr = h.rr; s.bb = h.bb;
-    memcpy(out, &s, std::min<size_t>(out->size, sizeof(s)));   // (a caller built against a shorter struct gets the fields it knows)
+    put_versioned(out, out->size, 0, s);
     return 0;
 }
 
@@ -477,6 +413,6 @@ extern "C" int tilespmv_csr_row_sqnorms_device(int rows, const MAT_PTR_TYPE *d_r
     if (rows < 0 || (rows > 0 && (!d_rowPtr || !d_val || !d_out))) return (int)hipErrorInvalidValue;
     if (tilespmv_device_count() <= 0) return (int)hipErrorNoDevice;
     if (rows > 0)
-        hipLaunchKernelGGL(k_csr_row_sqnorms, dim3((unsigned)((rows + LSB - 1) / LSB)), dim3(LSB), 0, (hipStream_t)stream, rows, d_rowPtr, d_src, d_val, d_out, invert);
+        hipLaunchKernelGGL(k_csr_row_sqnorms, dim3((unsigned)((rows + SVB - 1) / SVB)), dim3(SVB), 0, (hipStream_t)stream, rows, d_rowPtr, d_src, d_val, d_out, invert);
     return (int)hipGetLastError();
 }

@@ -7,14 +7,14 @@
 //   k_cgm_direction  reads r, p (, dinv)             beta_c = rho_new_c / rho_c;  p = z + beta p
 // 11 rows NVEC vector elements per iteration (+ 2 rows of dinv with Jacobi: dinv is shared by the columns and read once per lane vector).
 //
-// The vectors are walked as flat streams of n = rows * NVEC elements in 16-byte lane vectors, exactly as hip_solver.hip walks its vectors; flat element e belongs to column
-// e % NVEC.  A workgroup's trip stride (CG_U * CGB lane vectors), CGB and 64 are multiples of the lane vectors per row (LPR = NVEC / CG_VPL when NVEC >= CG_VPL), so a thread meets
-// the same columns in every trip: (threadIdx.x % LPR) * CG_VPL + q for element q of its lane vectors.  In fp32 with NVEC = 2 a lane vector holds two rows and element q is column
-// q % 2.  Either way a thread keeps KC = min(CG_VPL, NVEC) accumulators and as many alpha / beta, all indexed at compile time.
+// The vectors are walked as flat streams of n = rows * NVEC elements in 16-byte lane vectors by the walk of hip_solver_common.h (SV_FOR_TRIPS); flat element e belongs to column
+// e % NVEC.  A workgroup's trip stride (SV_U * SVB lane vectors), SVB and 64 are multiples of the lane vectors per row (LPR = NVEC / SV_VPL when NVEC >= SV_VPL), so a thread meets
+// the same columns in every trip: (threadIdx.x % LPR) * SV_VPL + q for element q of its lane vectors.  In fp32 with NVEC = 2 a lane vector holds two rows and element q is column
+// q % 2.  Either way a thread keeps KC = min(SV_VPL, NVEC) accumulators and as many alpha / beta, all indexed at compile time.
 // Sums per column: the wave tree runs over the shuffle offsets 32 .. LPR (lanes LPR apart hold the same columns), the four wave sums are added in wave order through LDS, one
-// partial per workgroup and column is written ([workgroup][NVEC]).  The consuming kernel folds the np * NVEC partials itself: thread t adds flat partials t, t + CGB, ... (all of
+// partial per workgroup and column is written ([workgroup][NVEC]).  The consuming kernel folds the np * NVEC partials itself: thread t adds flat partials t, t + SVB, ... (all of
 // column t % NVEC), the wave tree stops at offset NVEC, the four wave sums are added in wave order.  Every workgroup does the same additions in the same order; the number of
-// partials (cgm_parts) and every addition order are functions of (rows, NVEC) alone.  No atomics, no finishing launch, no occupancy query.
+// partials (solver_parts(rows * NVEC), hip_solver_common.h) and every addition order are functions of (rows, NVEC) alone.  No atomics, no finishing launch, no occupancy query.
 //
 // The scalar block is one CgmScal per column; the fields of hip_solver.hip's CgScal keep their one writing kernel each (k_cgm_dot: rho; k_cgm_update: breakdown; k_cgm_direction:
 // rr, iterations; k_cgm_begin_fold: all), and
@@ -22,20 +22,12 @@
 // Under the flag k_cgm_dot hands out rho = 0 for the column, which is the rho = 0 guard: alpha = beta = 0, x and r keep their bits, and k_cgm_direction leaves its iteration count.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "hip_plan_internal.h"
+#include "hip_solver_common.h"
 
 namespace tilespmv {
 namespace {
 
-// (the constants of hip_solver.hip, restated: that file stays as it is)
-constexpr int CGB = 256;                              // threads per workgroup
-constexpr int CG_VPL = 16 / (int)sizeof(val_t);       // elements per 16-byte lane load (2 in fp64, 4 in fp32)
-constexpr int CG_U = 2;                               // lane vectors per lane and trip
-constexpr int CG_MAX_PARTS = 1024;                    // partial sums per column = workgroups of the streaming kernels
 constexpr int MAX_NVEC = TILESPMV_MAX_NVEC;
-typedef val_t cvec_t __attribute__((ext_vector_type(CG_VPL)));
 
 struct CgmScal {
     double rho, rr, bb;
@@ -43,19 +35,12 @@ struct CgmScal {
 };
 
 template <int NVEC> struct Cols {
-    static constexpr int LPR = NVEC >= CG_VPL ? NVEC / CG_VPL : 1;   // lane vectors per row (1 when a lane vector holds whole rows)
-    static constexpr int KC = NVEC >= CG_VPL ? CG_VPL : NVEC;        // columns a thread meets
-    static constexpr int RPL = NVEC >= CG_VPL ? 1 : CG_VPL / NVEC;   // rows per lane vector
+    static constexpr int LPR = NVEC >= SV_VPL ? NVEC / SV_VPL : 1;   // lane vectors per row (1 when a lane vector holds whole rows)
+    static constexpr int KC = NVEC >= SV_VPL ? SV_VPL : NVEC;        // columns a thread meets
+    static constexpr int RPL = NVEC >= SV_VPL ? 1 : SV_VPL / NVEC;   // rows per lane vector
     // the first of this thread's KC consecutive columns
-    static __device__ __forceinline__ int first() { return NVEC >= CG_VPL ? ((int)threadIdx.x % LPR) * CG_VPL : 0; }
+    static __device__ __forceinline__ int first() { return NVEC >= SV_VPL ? ((int)threadIdx.x % LPR) * SV_VPL : 0; }
 };
-
-// workgroups (= partial sums per column) for rows x nvec: a function of the two alone
-inline int cgm_parts(long long rows, int nvec)
-{
-    const long long trips = (rows * nvec / CG_VPL + (long long)CG_U * CGB - 1) / ((long long)CG_U * CGB);
-    return (int)std::max<long long>(1, std::min<long long>(CG_MAX_PARTS, trips));
-}
 
 // The workgroup's sums of the per-thread accumulators, by column: left in s[wave * NVEC + column], four values per column (col_total adds them).
 template <int NVEC> __device__ __forceinline__ void block_cols(const double (&acc)[Cols<NVEC>::KC], double *s)
@@ -81,7 +66,7 @@ template <int NVEC> __device__ __forceinline__ void block_cols(const double (&ac
 __device__ __forceinline__ void fold_cols(const double *__restrict__ part, int np, int nvec, double *s)
 {
     double a = 0.0;
-    for (int i = threadIdx.x; i < np * nvec; i += CGB) a += part[i];
+    for (int i = threadIdx.x; i < np * nvec; i += SVB) a += part[i];
     for (int o = 32; o >= nvec; o >>= 1) a += __shfl_down(a, o, 64);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -99,52 +84,51 @@ template <int NVEC> __device__ __forceinline__ void write_partials(const double 
 }
 
 // dinv of the rows of lane vector v, element for element: one scalar load when the lane vector lies within a row, an 8-byte pair in fp32 with NVEC = 2
-template <int NVEC> __device__ __forceinline__ cvec_t load_dinv(const val_t *__restrict__ dinv, long long v)
+template <int NVEC> __device__ __forceinline__ svec_t load_dinv(const val_t *__restrict__ dinv, long long v)
 {
-    cvec_t d;
+    svec_t d;
     if constexpr (Cols<NVEC>::RPL == 1) {
         d = dinv[v / Cols<NVEC>::LPR];
     } else {
         typedef val_t pair_t __attribute__((ext_vector_type(Cols<NVEC>::RPL)));
         const pair_t t = reinterpret_cast<const pair_t *>(dinv)[v];
 #pragma unroll
-        for (int q = 0; q < CG_VPL; q++) d[q] = t[q / NVEC];
+        for (int q = 0; q < SV_VPL; q++) d[q] = t[q / NVEC];
     }
     return d;
 }
 
-// Element ranges as in hip_solver.hip: full lane vectors [0, nv) in trips of CG_U * CGB; the n % CG_VPL elements behind them (fp32, NVEC = 2, odd rows: one row) belong to
-// thread 0 of workgroup 0, whose columns start at 0 (scalar accesses: nothing past element n - 1 of a caller's array is touched).
-#define CGM_FOR_TRIPS(base) for (long long base = (long long)blockIdx.x * (CG_U * CGB) + threadIdx.x; base < nv; base += (long long)gridDim.x * (CG_U * CGB))
+// Element ranges as SV_FOR_TRIPS has them, over the flat stream; its n % SV_VPL tail elements (fp32, NVEC = 2, odd rows: one row) belong to thread 0 of workgroup 0, whose columns
+// start at 0.
 
 template <int NVEC>
-__global__ __launch_bounds__(CGB) void k_cgm_dot(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, double *__restrict__ ppap, const double *__restrict__ prz,
+__global__ __launch_bounds__(SVB) void k_cgm_dot(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, double *__restrict__ ppap, const double *__restrict__ prz,
                                                  int np, CgmScal *__restrict__ S)
 {
     constexpr int KC = Cols<NVEC>::KC;
-    __shared__ double s[(CGB / 64) * NVEC];
-    const long long nv = n / CG_VPL;
+    __shared__ double s[(SVB / 64) * NVEC];
+    const long long nv = n / SV_VPL;
     double acc[KC];
 #pragma unroll
     for (int k = 0; k < KC; k++) acc[k] = 0.0;
-    CGM_FOR_TRIPS(base) {
-        cvec_t a[CG_U], b[CG_U];
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t a[SV_U], b[SV_U];
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
-            if (v < nv) { a[u] = reinterpret_cast<const cvec_t *>(p)[v]; b[u] = reinterpret_cast<const cvec_t *>(Ap)[v]; }
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) { a[u] = lanes(p)[v]; b[u] = lanes(Ap)[v]; }
             else { a[u] = (val_t)0; b[u] = (val_t)0; }
         }
 #pragma unroll
-        for (int u = 0; u < CG_U; u++)
+        for (int u = 0; u < SV_U; u++)
 #pragma unroll
-            for (int q = 0; q < CG_VPL; q++) acc[q % KC] += (double)a[u][q] * (double)b[u][q];
+            for (int q = 0; q < SV_VPL; q++) acc[q % KC] += (double)a[u][q] * (double)b[u][q];
     }
-    if constexpr (NVEC < CG_VPL) {
+    if constexpr (NVEC < SV_VPL) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
             for (int k = 0; k < KC; k++) {
-                const long long i = nv * CG_VPL + k;
+                const long long i = nv * SV_VPL + k;
                 if (i < n) acc[k] += (double)p[i] * (double)Ap[i];
             }
         }
@@ -158,12 +142,12 @@ __global__ __launch_bounds__(CGB) void k_cgm_dot(long long n, const val_t *__res
 }
 
 template <int NVEC>
-__global__ __launch_bounds__(CGB) void k_cgm_update(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, val_t *__restrict__ x, val_t *__restrict__ r,
+__global__ __launch_bounds__(SVB) void k_cgm_update(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, val_t *__restrict__ x, val_t *__restrict__ r,
                                                     const val_t *__restrict__ dinv, const double *__restrict__ ppap, double *__restrict__ prr, double *__restrict__ prz, int np,
                                                     CgmScal *__restrict__ S)
 {
     constexpr int KC = Cols<NVEC>::KC, LPR = Cols<NVEC>::LPR;
-    __shared__ double s[(CGB / 64) * NVEC];
+    __shared__ double s[(SVB / 64) * NVEC];
     const int c0 = Cols<NVEC>::first();
     fold_cols(ppap, np, NVEC, s);
     val_t alpha[KC];
@@ -174,44 +158,44 @@ __global__ __launch_bounds__(CGB) void k_cgm_update(long long n, const val_t *__
         alpha[k] = (val_t)((rho > 0.0 && pap > 0.0) ? rho / pap : 0.0);
         if (broke && blockIdx.x == 0 && threadIdx.x < LPR) S[c0 + k].breakdown = 1;   // (threads 0 .. LPR - 1 hold each column once)
     }
-    cvec_t av;
+    svec_t av;
 #pragma unroll
-    for (int q = 0; q < CG_VPL; q++) av[q] = alpha[q % KC];
-    const long long nv = n / CG_VPL;
+    for (int q = 0; q < SV_VPL; q++) av[q] = alpha[q % KC];
+    const long long nv = n / SV_VPL;
     double arr[KC], arz[KC];
 #pragma unroll
     for (int k = 0; k < KC; k++) { arr[k] = 0.0; arz[k] = 0.0; }
-    CGM_FOR_TRIPS(base) {
-        cvec_t vp[CG_U], va[CG_U], vx[CG_U], vr[CG_U], vd[CG_U];
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t vp[SV_U], va[SV_U], vx[SV_U], vr[SV_U], vd[SV_U];
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                vp[u] = reinterpret_cast<const cvec_t *>(p)[v]; va[u] = reinterpret_cast<const cvec_t *>(Ap)[v];
-                vx[u] = reinterpret_cast<const cvec_t *>(x)[v]; vr[u] = reinterpret_cast<const cvec_t *>(r)[v];
+                vp[u] = lanes(p)[v]; va[u] = lanes(Ap)[v];
+                vx[u] = lanes(x)[v]; vr[u] = lanes(r)[v];
                 if (dinv) vd[u] = load_dinv<NVEC>(dinv, v);
             }
         }
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const cvec_t nx = vx[u] + av * vp[u], nr = vr[u] - av * va[u];
-                reinterpret_cast<cvec_t *>(x)[v] = nx;
-                reinterpret_cast<cvec_t *>(r)[v] = nr;
+                const svec_t nx = vx[u] + av * vp[u], nr = vr[u] - av * va[u];
+                lanes(x)[v] = nx;
+                lanes(r)[v] = nr;
 #pragma unroll
-                for (int q = 0; q < CG_VPL; q++) {
+                for (int q = 0; q < SV_VPL; q++) {
                     arr[q % KC] += (double)nr[q] * (double)nr[q];
                     if (dinv) arz[q % KC] += (double)nr[q] * (double)(val_t)(vd[u][q] * nr[q]);
                 }
             }
         }
     }
-    if constexpr (NVEC < CG_VPL) {
+    if constexpr (NVEC < SV_VPL) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
             for (int k = 0; k < KC; k++) {
-                const long long i = nv * CG_VPL + k;
+                const long long i = nv * SV_VPL + k;
                 if (i < n) {
                     const val_t nr = r[i] - alpha[k] * Ap[i];
                     x[i] = x[i] + alpha[k] * p[i];
@@ -231,11 +215,11 @@ __global__ __launch_bounds__(CGB) void k_cgm_update(long long n, const val_t *__
 }
 
 template <int NVEC>
-__global__ __launch_bounds__(CGB) void k_cgm_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ dinv,
+__global__ __launch_bounds__(SVB) void k_cgm_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ dinv,
                                                        const double *__restrict__ prr, const double *__restrict__ prz, int np, CgmScal *__restrict__ S)
 {
     constexpr int KC = Cols<NVEC>::KC;
-    __shared__ double s[(CGB / 64) * NVEC];
+    __shared__ double s[(SVB / 64) * NVEC];
     const int c0 = Cols<NVEC>::first();
     fold_cols(prz, np, NVEC, s);
     val_t beta[KC];
@@ -251,34 +235,34 @@ __global__ __launch_bounds__(CGB) void k_cgm_direction(long long n, const val_t 
             if (!S[threadIdx.x].frozen) S[threadIdx.x].iterations = S[threadIdx.x].iterations + 1;
         }
     }
-    cvec_t bv;
+    svec_t bv;
 #pragma unroll
-    for (int q = 0; q < CG_VPL; q++) bv[q] = beta[q % KC];
-    const long long nv = n / CG_VPL;
-    CGM_FOR_TRIPS(base) {
-        cvec_t vr[CG_U], vp[CG_U], vd[CG_U];
+    for (int q = 0; q < SV_VPL; q++) bv[q] = beta[q % KC];
+    const long long nv = n / SV_VPL;
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t vr[SV_U], vp[SV_U], vd[SV_U];
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                vr[u] = reinterpret_cast<const cvec_t *>(r)[v]; vp[u] = reinterpret_cast<const cvec_t *>(p)[v];
+                vr[u] = lanes(r)[v]; vp[u] = lanes(p)[v];
                 if (dinv) vd[u] = load_dinv<NVEC>(dinv, v);
             }
         }
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const cvec_t z = dinv ? vd[u] * vr[u] : vr[u];
-                reinterpret_cast<cvec_t *>(p)[v] = z + bv * vp[u];
+                const svec_t z = dinv ? vd[u] * vr[u] : vr[u];
+                lanes(p)[v] = z + bv * vp[u];
             }
         }
     }
-    if constexpr (NVEC < CG_VPL) {
+    if constexpr (NVEC < SV_VPL) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
             for (int k = 0; k < KC; k++) {
-                const long long i = nv * CG_VPL + k;
+                const long long i = nv * SV_VPL + k;
                 if (i < n) p[i] = (dinv ? (val_t)(dinv[i / NVEC] * r[i]) : r[i]) + beta[k] * p[i];
             }
         }
@@ -287,26 +271,26 @@ __global__ __launch_bounds__(CGB) void k_cgm_direction(long long n, const val_t 
 
 // the start of a solve: r = B - A X (AX holds the product), p = z, partial sums of r.r, r.z and b.b per column
 template <int NVEC>
-__global__ __launch_bounds__(CGB) void k_cgm_begin(long long n, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, val_t *__restrict__ p,
+__global__ __launch_bounds__(SVB) void k_cgm_begin(long long n, const val_t *__restrict__ b, const val_t *__restrict__ Ax, val_t *__restrict__ r, val_t *__restrict__ p,
                                                    const val_t *__restrict__ dinv, double *__restrict__ prr, double *__restrict__ prz, double *__restrict__ pbb)
 {
     constexpr int KC = Cols<NVEC>::KC;
-    __shared__ double s[(CGB / 64) * NVEC];
-    const long long nv = n / CG_VPL;
+    __shared__ double s[(SVB / 64) * NVEC];
+    const long long nv = n / SV_VPL;
     double arr[KC], arz[KC], abb[KC];
 #pragma unroll
     for (int k = 0; k < KC; k++) { arr[k] = 0.0; arz[k] = 0.0; abb[k] = 0.0; }
-    CGM_FOR_TRIPS(base) {
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
 #pragma unroll
-        for (int u = 0; u < CG_U; u++) {
-            const long long v = base + u * CGB;
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
             if (v < nv) {
-                const cvec_t vb = reinterpret_cast<const cvec_t *>(b)[v], nr = vb - reinterpret_cast<const cvec_t *>(Ax)[v];
-                const cvec_t z = dinv ? load_dinv<NVEC>(dinv, v) * nr : nr;
-                reinterpret_cast<cvec_t *>(r)[v] = nr;
-                reinterpret_cast<cvec_t *>(p)[v] = z;
+                const svec_t vb = lanes(b)[v], nr = vb - lanes(Ax)[v];
+                const svec_t z = dinv ? load_dinv<NVEC>(dinv, v) * nr : nr;
+                lanes(r)[v] = nr;
+                lanes(p)[v] = z;
 #pragma unroll
-                for (int q = 0; q < CG_VPL; q++) {
+                for (int q = 0; q < SV_VPL; q++) {
                     arr[q % KC] += (double)nr[q] * (double)nr[q];
                     arz[q % KC] += (double)nr[q] * (double)z[q];
                     abb[q % KC] += (double)vb[q] * (double)vb[q];
@@ -314,11 +298,11 @@ __global__ __launch_bounds__(CGB) void k_cgm_begin(long long n, const val_t *__r
             }
         }
     }
-    if constexpr (NVEC < CG_VPL) {
+    if constexpr (NVEC < SV_VPL) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
             for (int k = 0; k < KC; k++) {
-                const long long i = nv * CG_VPL + k;
+                const long long i = nv * SV_VPL + k;
                 if (i < n) {
                     const val_t nr = b[i] - Ax[i], z = dinv ? (val_t)(dinv[i / NVEC] * nr) : nr;
                     r[i] = nr; p[i] = z;
@@ -337,10 +321,10 @@ __global__ __launch_bounds__(CGB) void k_cgm_begin(long long n, const val_t *__r
     }
 }
 // ... and its scalars (one workgroup; prz is prr in plain CG)
-__global__ __launch_bounds__(CGB) void k_cgm_begin_fold(const double *__restrict__ prr, const double *__restrict__ prz, const double *__restrict__ pbb, int np, int nvec,
+__global__ __launch_bounds__(SVB) void k_cgm_begin_fold(const double *__restrict__ prr, const double *__restrict__ prz, const double *__restrict__ pbb, int np, int nvec,
                                                         CgmScal *__restrict__ S)
 {
-    __shared__ double s[(CGB / 64) * MAX_NVEC];
+    __shared__ double s[(SVB / 64) * MAX_NVEC];
     const int c = threadIdx.x < nvec ? threadIdx.x : 0;
     fold_cols(prr, np, nvec, s);
     const double rr = col_total(s, nvec, c);
@@ -361,15 +345,13 @@ __global__ __launch_bounds__(64) void k_cgm_freeze(CgmScal *__restrict__ S, int 
     if (threadIdx.x < nvec && ((mask >> threadIdx.x) & 1u)) S[threadIdx.x].frozen = 1;
 }
 // ... and the columns of `mask` (b = 0) are 0
-__global__ __launch_bounds__(CGB) void k_cgm_zero_columns(long long rows, int nvec, unsigned mask, val_t *__restrict__ x)
+__global__ __launch_bounds__(SVB) void k_cgm_zero_columns(long long rows, int nvec, unsigned mask, val_t *__restrict__ x)
 {
-    const long long i = (long long)blockIdx.x * CGB + threadIdx.x;
+    const long long i = (long long)blockIdx.x * SVB + threadIdx.x;
     if (i >= rows) return;
     for (int c = 0; c < nvec; c++)
         if ((mask >> c) & 1u) x[i * nvec + c] = (val_t)0;
 }
-
-inline bool misaligned(const void *p) { return ((uintptr_t)p & 15u) != 0; }
 
 }  // namespace
 }  // namespace tilespmv
@@ -392,22 +374,21 @@ namespace {
 
 template <int NVEC> void launch_begin(const tilespmv_cg_multi *c, const val_t *B, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_cgm_begin<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, B, c->Ap, c->r, c->p, c->dinv, c->prr, c->prz, c->pbb);
+    hipLaunchKernelGGL(k_cgm_begin<NVEC>, dim3(c->np), dim3(SVB), 0, st, c->n, B, c->Ap, c->r, c->p, c->dinv, c->prr, c->prz, c->pbb);
 }
 template <int NVEC> void launch_iteration(const tilespmv_cg_multi *c, val_t *X, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_cgm_dot<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, c->p, c->Ap, c->ppap, c->prz, c->np, c->S);
-    hipLaunchKernelGGL(k_cgm_update<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, c->p, c->Ap, X, c->r, c->dinv, c->ppap, c->prr, c->prz, c->np, c->S);
-    hipLaunchKernelGGL(k_cgm_direction<NVEC>, dim3(c->np), dim3(CGB), 0, st, c->n, c->r, c->p, c->dinv, c->prr, c->prz, c->np, c->S);
+    hipLaunchKernelGGL(k_cgm_dot<NVEC>, dim3(c->np), dim3(SVB), 0, st, c->n, c->p, c->Ap, c->ppap, c->prz, c->np, c->S);
+    hipLaunchKernelGGL(k_cgm_update<NVEC>, dim3(c->np), dim3(SVB), 0, st, c->n, c->p, c->Ap, X, c->r, c->dinv, c->ppap, c->prr, c->prz, c->np, c->S);
+    hipLaunchKernelGGL(k_cgm_direction<NVEC>, dim3(c->np), dim3(SVB), 0, st, c->n, c->r, c->p, c->dinv, c->prr, c->prz, c->np, c->S);
 }
 
 // the scalar blocks of all columns, after a synchronisation of the stream
 int read_columns(const tilespmv_cg_multi *c, hipStream_t st, tilespmv_cg_state *cols /* [nvec], whole structs */)
 {
     CgmScal h[MAX_NVEC];
-    hipError_t e = hipMemcpyAsync(h, c->S, sizeof(CgmScal) * c->nvec, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+    const hipError_t e = read_scalars(h, c->S, sizeof(CgmScal) * c->nvec, st);
+    if (e != hipSuccess) return (int)e;
     for (int j = 0; j < c->nvec; j++) {
         cols[j].size = sizeof(tilespmv_cg_state);
         cols[j].iterations = h[j].iterations;
@@ -415,12 +396,6 @@ int read_columns(const tilespmv_cg_multi *c, hipStream_t st, tilespmv_cg_state *
         cols[j].rr = h[j].rr; cols[j].bb = h[j].bb;
     }
     return 0;
-}
-// element j of a caller's array whose elements are `stride` bytes apart (a caller built against a shorter struct gets the fields it knows)
-void put_state(tilespmv_cg_state *out, unsigned stride, int j, tilespmv_cg_state s)
-{
-    s.size = stride;
-    memcpy((char *)out + (size_t)j * stride, &s, std::min<size_t>(stride, sizeof(s)));
 }
 
 }  // namespace
@@ -431,7 +406,7 @@ extern "C" int tilespmv_cg_multi_create(tilespmv_cg_multi **cg, tilespmv_plan *p
     if (!cg || !plan) return (int)hipErrorInvalidValue;
     if (nvec != 1 && nvec != 2 && nvec != 4 && nvec != 8) return (int)hipErrorInvalidValue;   // (before the plan is touched)
     const long long rows = plan->matrix_rows;
-    if (rows <= 0 || plan->dev.colA != rows || plan->dev.f_row0 != 0 || plan->dev.f_rows != rows) return (int)hipErrorInvalidValue;   // square, whole matrix
+    if (rows <= 0 || !whole_plan(plan, rows, rows)) return (int)hipErrorInvalidValue;   // square, whole matrix
     if (misaligned(d_dinv)) return (int)hipErrorInvalidValue;
     if (nvec == 1) {
         tilespmv_cg *one = nullptr;
@@ -444,27 +419,21 @@ extern "C" int tilespmv_cg_multi_create(tilespmv_cg_multi **cg, tilespmv_plan *p
     }
     int rc = tilespmv_plan_reserve_spmm(plan, nvec);   // plans that multiply one right-hand side at a time: their scratch now, so that iterate never allocates
     if (rc) return rc;
-    const size_t vec = ((size_t)(rows + 16) * nvec * sizeof(val_t) + 255) / 256 * 256, parts = (size_t)CG_MAX_PARTS * nvec * sizeof(double);
-    const size_t bytes = 3 * vec + 4 * parts + ((size_t)nvec * sizeof(CgmScal) + 255) / 256 * 256;
-    void *blk = nullptr;
-    hipError_t e = hipMalloc(&blk, bytes);
-    if (e == hipSuccess) e = hipMemset(blk, 0, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (blk) (void)hipFree(blk);
-        return (int)e;
-    }
+    const size_t vec = vec_bytes(rows, nvec), parts = (size_t)SV_MAX_PARTS * nvec * sizeof(double), scal = ((size_t)nvec * sizeof(CgmScal) + 255) / 256 * 256;
+    DeviceBlock blk;
+    const hipError_t e = blk.alloc(3 * vec + 4 * parts + scal);
+    if (e != hipSuccess) return (int)e;
     auto *c = new tilespmv_cg_multi();
-    c->plan = plan; c->rows = rows; c->nvec = nvec; c->n = rows * nvec; c->np = cgm_parts(rows, nvec); c->dinv = d_dinv; c->block = blk;
-    char *at = (char *)blk;
-    c->r = (val_t *)at; at += vec;
-    c->p = (val_t *)at; at += vec;
-    c->Ap = (val_t *)at; at += vec;
-    c->ppap = (double *)at; at += parts;
-    c->prr = (double *)at; at += parts;
-    c->prz = d_dinv ? (double *)at : c->prr; at += parts;
-    c->pbb = (double *)at; at += parts;
-    c->S = (CgmScal *)at;
+    c->plan = plan; c->rows = rows; c->nvec = nvec; c->n = rows * nvec; c->np = solver_parts(c->n); c->dinv = d_dinv; c->block = blk.base;
+    c->r = blk.take<val_t>(vec);
+    c->p = blk.take<val_t>(vec);
+    c->Ap = blk.take<val_t>(vec);
+    c->ppap = blk.take<double>(parts);
+    c->prr = blk.take<double>(parts);
+    double *const rz = blk.take<double>(parts);
+    c->prz = d_dinv ? rz : c->prr;
+    c->pbb = blk.take<double>(parts);
+    c->S = blk.take<CgmScal>(scal);
     *cg = c;
     return 0;
 }
@@ -489,7 +458,7 @@ extern "C" int tilespmv_cg_multi_begin(tilespmv_cg_multi *cg, const MAT_VAL_TYPE
     case 4: launch_begin<4>(cg, d_B, st); break;
     default: launch_begin<8>(cg, d_B, st); break;
     }
-    hipLaunchKernelGGL(k_cgm_begin_fold, dim3(1), dim3(CGB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->nvec, cg->S);
+    hipLaunchKernelGGL(k_cgm_begin_fold, dim3(1), dim3(SVB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->nvec, cg->S);
     return (int)hipGetLastError();
 }
 
@@ -520,7 +489,7 @@ extern "C" int tilespmv_cg_multi_state_read(tilespmv_cg_multi *cg, void *stream,
     const int rc = read_columns(cg, (hipStream_t)stream, cols);
     if (rc) return rc;
     const unsigned stride = out->size;
-    for (int j = 0; j < cg->nvec; j++) put_state(out, stride, j, cols[j]);
+    for (int j = 0; j < cg->nvec; j++) put_versioned(out, stride, j, cols[j]);
     return 0;
 }
 
@@ -549,12 +518,12 @@ extern "C" int tilespmv_cg_multi_solve(tilespmv_cg_multi *cg, const MAT_VAL_TYPE
             else if (s.bb == 0.0) { s.rr = 0.0; s.status = TILESPMV_CG_CONVERGED; fresh |= bit; zero |= bit; }   // b = 0: the solution is 0
             else if (s.rr <= rtol * rtol * s.bb) { s.status = TILESPMV_CG_CONVERGED; fresh |= bit; }
             else s.status = done >= maxiter ? TILESPMV_CG_MAXITER : TILESPMV_CG_RUNNING;
-            put_state(out, stride, j, s);
+            put_versioned(out, stride, j, s);
         }
         final_mask |= fresh;
         const bool last = final_mask == all || done >= maxiter;
         if (fresh && !last) hipLaunchKernelGGL(k_cgm_freeze, dim3(1), dim3(64), 0, st, cg->S, cg->nvec, fresh);
-        if (zero) hipLaunchKernelGGL(k_cgm_zero_columns, dim3((unsigned)((cg->rows + CGB - 1) / CGB)), dim3(CGB), 0, st, cg->rows, cg->nvec, zero, d_X);
+        if (zero) hipLaunchKernelGGL(k_cgm_zero_columns, dim3((unsigned)((cg->rows + SVB - 1) / SVB)), dim3(SVB), 0, st, cg->rows, cg->nvec, zero, d_X);
         if ((fresh && !last) || zero) {
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return (int)e;
