@@ -61,6 +61,16 @@ def test_device_tile_create_builds_hyb_tiles_where_the_rule_selects_them():
         assert same_tile_matrix(rows, cols, rp, ci, np.float64, hyb=True) == []
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("rowA", [187, 177, 1])
+def test_device_tile_create_partial_last_tile_row_with_hyb(rowA, dtype):
+    """A partial last tile-row with HYB on: a HYB tile of rowlen < 16 rows can have an odd nibble count, so its index bytes end on a half byte and the next tile's begin at the
+    byte offset of the "hybIdx bytes" scan — the smallest shape at which the shared packer's offsets (csrc/tile_pack.h) can go wrong.  The host half of these cases is pinned
+    against the oracle by tests/test_host.py::test_partial_last_tile_row."""
+    rows, cols, rp, ci = cases.SMALL["allfmt_pad5"]()
+    assert same_tile_matrix(rowA, cols, rp, ci, dtype, hyb=True) == []
+
+
 def test_device_tile_create_random_ingredients():
     """60 matrices from the fuzz generator's ingredients (every format, long rows, empty tile-rows, odd column counts; half of them with unsorted columns)."""
     for seed in range(60):

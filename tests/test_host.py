@@ -11,7 +11,7 @@ from hypothesis import given, settings, strategies as st
 from cases import SMALL, MEDIUM, truncated_rows, values_for
 from oracle.oracle import CpuImpl
 from tilespmv_amd import _lib, api, generators as G
-from tilespmv_amd.tile_matrix import to_dict
+from tilespmv_amd.tile_matrix import field_array, field_lengths, to_dict
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -284,6 +284,45 @@ def test_matrix_cache_rejects_damaged_files(tmp_path):
     tl, r2, c2, z2 = load_bytes(raw)                            # and the intact bytes still load
     assert (r2, c2, z2) == (rowA, n, nnz)
     api.Tile_destroy(tl)
+
+
+def test_matrix_cache_format_did_not_move(tmp_path):
+    """tests/golden/allfmt_pad5_r177_hyb_f64.tspmv was saved by the build before the member arrays were listed in one table (csrc/tile_fields.h): all-formats
+    matrix with a 5-column last tile column, fp64, HYB on, rowA = 177 (partial last tile-row), integer-valued data.  It must load, equal a fresh Tile_create
+    in every scalar and array, and be saved again as the identical bytes (field order, counts, header and checksum)."""
+    golden = os.path.join(HERE, "golden", "allfmt_pad5_r177_hyb_f64.tspmv")
+    m, n, rp, ci = SMALL["allfmt_pad5"]()
+    nnz, rowA = len(ci), 177
+    tl, r2, c2, z2 = api.matrix_load(golden, np.float64)
+    assert (r2, c2, z2) == (rowA, n, nnz)
+    tp = api.Tile_create(rowA, n, nnz, rp, ci, G.compat_values(nnz, np.float64), dtype=np.float64, hyb=True)
+    a, b = to_dict(tp, rowA), to_dict(tl, rowA)
+    assert a["hybsize"] > 0
+    for k in a:
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
+    for i, tm in enumerate((tl, tp)):
+        again = str(tmp_path / ("again%d.tspmv" % i))
+        api.matrix_save(tm, rowA, n, nnz, again)
+        assert open(again, "rb").read() == open(golden, "rb").read()
+    api.Tile_destroy(tl); api.Tile_destroy(tp)
+
+
+def test_python_field_lengths_agree_with_the_c_table(tmp_path):
+    """tilespmv_amd/tile_matrix.py field_lengths (what the tests view the member arrays with) against csrc/tile_fields.h (what the library allocates, saves and
+    loads with): the payload byte total that tilespmv_matrix_save writes into the header is the sum over the Python mirror's counts."""
+    header_before_total = 8 + 4 * 4 + 14 * 4 + 2 * 8
+    for name, hyb in (("allfmt", True), ("circuit8k", False), ("empty_rows", False)):
+        m, n, rp, ci = SMALL[name]()
+        nnz, rowA = len(ci), truncated_rows(m)
+        for dtype in (np.float64, np.float32):
+            tp = api.Tile_create(rowA, n, nnz, rp, ci, G.compat_values(nnz, dtype), dtype=dtype, hyb=hyb)
+            path = str(tmp_path / ("%s_%s.tspmv" % (name, np.dtype(dtype).name)))
+            api.matrix_save(tp, rowA, n, nnz, path)
+            saved = int(np.frombuffer(open(path, "rb").read()[header_before_total:header_before_total + 8], dtype=np.uint64)[0])
+            want = sum(int(cnt) * field_array(tp, k, 0).dtype.itemsize for k, cnt in field_lengths(tp, rowA).items())
+            assert saved == want, (name, dtype)
+            assert os.path.getsize(path) == header_before_total + 16 + want
+            api.Tile_destroy(tp)
 
 
 def test_csr_cache_parse_once(tmp_path):

@@ -10,6 +10,7 @@
 
 #include "hip_plan_internal.h"
 #include "hip_plan_device.h"
+#include "tile_fields.h"
 
 namespace tilespmv {
 hipError_t launch_permute_vector(const val_t *in, val_t *out, const int *perm, long long n, int scatter, hipStream_t st);   // hip_kernels.hip
@@ -869,14 +870,9 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
     if (rc != 0) return rc;
     const double t1 = now_us();
     // the tile LIST on the host (what CHOOSE / CUT / the stride detection read); everything else of the tiled matrix stays where it is
-    Tile_matrix H = D->T;
-    {
-        Tile_matrix Z;   // counts stay, every pointer member and the hyb sizes are cleared (three pointers are replaced below)
-        memset(&Z, 0, sizeof(Z));
-        Z.tilem = H.tilem; Z.tilen = H.tilen; Z.tilenum = H.tilenum;
-        Z.csrsize = H.csrsize; Z.csrptrlen = H.csrptrlen; Z.coosize = H.coosize; Z.ellsize = H.ellsize; Z.hybsize = H.hybsize; Z.hybellsize = H.hybellsize; Z.hybcoosize = H.hybcoosize; Z.dnssize = H.dnssize; Z.dnsrowsize = H.dnsrowsize; Z.dnscolsize = H.dnscolsize; Z.coototal = H.coototal;
-        H = Z;
-    }
+    Tile_matrix H;   // the counts stay, every pointer member is cleared (three pointers are replaced below)
+    memset(&H, 0, sizeof(H));
+    copy_tile_scalars(H, D->T);
     std::vector<int> h_tile_ptr((size_t)H.tilem + 1, 0), h_tile_col((size_t)std::max(1, H.tilenum), 0);
     std::vector<char> h_fmt((size_t)std::max(1, H.tilenum), 0);
     hipError_t e = hipMemcpy(h_tile_ptr.data(), D->T.tile_ptr, h_tile_ptr.size() * sizeof(int), hipMemcpyDeviceToHost);

@@ -6,9 +6,10 @@
 //   2. ONE stable radix sort by (tile-row, column block) puts the nonzeros into tile order — the reference searches the tile list per nonzero (src/csr2tile.h:406-418),
 //      the host version buckets per tile-row with a stamp array; the key carries the local coordinates through the sort outside the sorted bit range;
 //   3. run-length encoding of the sorted keys = the tile list (tile_ptr, tile_columnidx, tile_nnz);
-//   4. one thread per tile: row counts from the keys, the shared selection rule (tile_select.h), sizes -> thirteen exclusive scans;
-//   5. one thread per tile packs its payload (values gathered from the CSR array through the sorted positions); nibble streams packed by a second kernel (two tiles may
-//      share a byte); the extracted very-sparse matrix (deferredcoo_*) by one more stable sort by row.
+//   4. one thread per tile: row counts from the keys, the shared selection rule (tile_select.h), sizes -> fourteen exclusive scans;
+//   5. one thread per tile packs its payload with the shared packer (tile_pack.h; values gathered from the CSR array through the sorted positions); nibble streams packed by
+//      a second kernel (two tiles may share a byte); the extracted very-sparse matrix (deferredcoo_*) by one more stable sort by row.
+// Steps 1-3 are this builder's own; the selection rule, the packer and the table of member arrays that sizes, allocates and downloads them (tile_fields.h) are the host builder's too.
 // HYB tiles (TILESPMV_CREATE_HYB, dormant in the shipped reference: SURVEY S1; width search src/csr2tile.h:279-306 = tile_select.h, pack :505-548, index bytes :984-1008) are built
 // too (round 6): a tile's index bytes are tile-byte-aligned, so the thread that packs the tile writes them itself, at a byte offset that is one more scan.
 #include <cstring>
@@ -19,9 +20,9 @@
 #include <sys/time.h>
 #include <thread>
 
-#include <type_traits>
-
 #include "hip_tile_create.h"
+#include "tile_fields.h"
+#include "tile_pack.h"
 #include "tile_select.h"
 
 namespace tilespmv {
@@ -149,118 +150,27 @@ __global__ __launch_bounds__(256) void k_tc_totals(ScanSet S, int K, long long n
 }
 
 struct PackArrays {
-    val_t *Blockcsr_Val; unsigned char *Blockcsr_Ptr, *csr_col;   // csr_col / ell_col: one byte per slot, packed into nibbles afterwards
-    val_t *Blockcoo_Val; unsigned char *coo_compressed_Idx;
-    val_t *Blockell_Val; unsigned char *ell_col;
-    val_t *Blockdense_Val, *Blockdenserow_Val, *Blockdensecol_Val;
-    char *denserowid, *densecolid;
-    val_t *Blockhyb_Val; unsigned char *hybIdx; const int *hyb_byte_off;   // HYB: values, index bytes, every tile's byte offset in hybIdx
+    PackOut out;               // (tile_pack.h)
+    const int *hyb_byte_off;   // every tile's byte offset in hybIdx
     unsigned *x_key; int *x_col; val_t *x_val;   // extracted entries in tile order: global row, column, value (nullptr: not wanted)
     int *deferredcoo_ptr;                          // per-row counts (atomics), scanned afterwards
 };
 
-// ---- 5. packing: one thread per tile (src/csr2tile.h:420-622)
-__global__ __launch_bounds__(256) void k_tc_pack(int tilenum, int tilem, int tilen, int rowA, int colA, const Tile_matrix T, const int *__restrict__ tile_bi, const u64 *__restrict__ key,
-                                                   const int *__restrict__ ent, const int *__restrict__ colidx, const val_t *__restrict__ vals, PackArrays P)
+// ---- 5. packing: one thread per tile (tile_pack.h)
+__global__ __launch_bounds__(256) void k_tc_pack(int tilenum, int tilem, int rowA, const Tile_matrix T, const int *__restrict__ tile_bi, const u64 *__restrict__ key, const int *__restrict__ ent,
+                                                   const int *__restrict__ colidx, const val_t *__restrict__ vals, PackArrays P)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= tilenum) return;
-    const int bi = tile_bi[t], cb = T.tile_columnidx[t];
-    const int rowlen = tile_rowlen(bi, tilem, rowA);
-    (void)cb; (void)tilen; (void)colA;
-    const int e0 = T.tile_nnz[t], n = T.tile_nnz[t + 1] - e0, fmt = T.Format[t];
-    const u64 *kp = key + e0; const int *src = ent + e0;
-    int rcur = 0, rstart = 0;   // the row the walk is in and where it starts (entries of a tile are in row order)
-    switch (fmt) {
-    case TILESPMV_FMT_CSR: {
-        const int off = T.csr_offset[t], poff = T.csrptr_offset[t];
-        P.Blockcsr_Ptr[poff] = 0;
-        for (int k = 0; k < n; k++) {
-            const int rc = (int)(kp[k] & 255ull), r = rc >> 4;
-            while (rcur < r) { rcur++; if (rcur < rowlen) P.Blockcsr_Ptr[poff + rcur] = (unsigned char)k; }
-            P.Blockcsr_Val[off + k] = vals[src[k]]; P.csr_col[off + k] = (unsigned char)(rc & 15);
-        }
-        while (rcur < rowlen - 1) { rcur++; P.Blockcsr_Ptr[poff + rcur] = (unsigned char)n; }
-        break;
-    }
-    case TILESPMV_FMT_COO: {
-        const int off = T.coo_offset[t], xo = T.new_coocount[t];
-        for (int k = 0; k < n; k++) {
-            const int rc = (int)(kp[k] & 255ull);
-            const val_t v = vals[src[k]];
-            P.Blockcoo_Val[off + k] = v;
-            P.coo_compressed_Idx[off + k] = (unsigned char)rc;
-            if (P.x_key) {
-                const unsigned row = (unsigned)bi * 16u + (unsigned)(rc >> 4);
-                P.x_key[xo + k] = row; P.x_col[xo + k] = colidx[src[k]]; P.x_val[xo + k] = v;
-                atomicAdd(&P.deferredcoo_ptr[row], 1);
-            }
-        }
-        break;
-    }
-    case TILESPMV_FMT_ELL: {
-        const int off = T.ell_offset[t];
-        for (int k = 0; k < n; k++) {
-            const int rc = (int)(kp[k] & 255ull), r = rc >> 4;
-            if (r != rcur) { rcur = r; rstart = k; }
-            const int p = off + (k - rstart) * rowlen + r;
-            P.Blockell_Val[p] = vals[src[k]]; P.ell_col[p] = (unsigned char)(rc & 15);
-        }
-        break;
-    }
-    case TILESPMV_FMT_HYB: {   // ELL part of width w (slot-major, zero padded) + the entries beyond it in row order (src/csr2tile.h:505-548); index bytes :984-1008
-        const int off = T.hyb_offset[t], xo = T.new_coocount[t], w = T.tilewidth[t], nell = w * rowlen;
-        unsigned char *ib = P.hybIdx + P.hyb_byte_off[t];   // this tile's bytes (nobody else's: the stream is tile-byte-aligned)
-        int spill = 0;
-        for (int k = 0; k < n; k++) {
-            const int rc = (int)(kp[k] & 255ull), r = rc >> 4;
-            if (r != rcur) { rcur = r; rstart = k; }
-            const int sl = k - rstart;
-            const val_t v = vals[src[k]];
-            if (sl < w) {
-                const int q = sl * rowlen + r;
-                P.Blockhyb_Val[off + q] = v;
-                ib[q >> 1] = (unsigned char)(ib[q >> 1] | ((q & 1) ? (rc & 15) : ((rc & 15) << 4)));   // nibble at position q of the tile's own stream: high nibble first
-            } else {
-                P.Blockhyb_Val[off + nell + spill] = v;
-                ib[(nell + 1) / 2 + spill] = (unsigned char)rc;   // (row << 4) | column
-                if (P.x_key) {
-                    const unsigned row = (unsigned)bi * 16u + (unsigned)r;
-                    P.x_key[xo + spill] = row; P.x_col[xo + spill] = colidx[src[k]]; P.x_val[xo + spill] = v;
-                    atomicAdd(&P.deferredcoo_ptr[row], 1);
-                }
-                spill++;
-            }
-        }
-        break;
-    }
-    case TILESPMV_FMT_DNS: {
-        const int off = T.dns_offset[t];
-        for (int k = 0; k < n; k++) { const int rc = (int)(kp[k] & 255ull); P.Blockdense_Val[off + (rc & 15) * rowlen + (rc >> 4)] = vals[src[k]]; }
-        break;
-    }
-    case TILESPMV_FMT_DNSROW: {   // every row is full or empty: the values of the full rows back to back, their row ids in order
-        const int off = T.dnsrow_offset[t], ro = T.dnsrowptr[t];
-        int nr = 0, last = -1;
-        for (int k = 0; k < n; k++) {
-            const int r = (int)(kp[k] >> 4) & 15;
-            if (r != last) { P.denserowid[ro + nr++] = (char)r; last = r; }
-            P.Blockdenserow_Val[off + k] = vals[src[k]];
-        }
-        break;
-    }
-    case TILESPMV_FMT_DNSCOL: {
-        const int off = T.dnscol_offset[t], co = T.dnscolptr[t];
-        for (int k = 0; k < n; k++) {
-            const int rc = (int)(kp[k] & 255ull), r = rc >> 4;
-            if (r != rcur) { rcur = r; rstart = k; }
-            if (r == 0) P.densecolid[co + k] = (char)(rc & 15);   // the columns present = the columns of row 0
-            P.Blockdensecol_Val[off + (k - rstart) * rowlen + r] = vals[src[k]];
-        }
-        break;
-    }
-    default: break;
-    }
+    const int bi = tile_bi[t];
+    const u64 *kp = key + T.tile_nnz[t]; const int *src = ent + T.tile_nnz[t];
+    pack_tile(T, t, tile_rowlen(bi, tilem, rowA), P.hyb_byte_off[t], [kp](int k) { return (int)(kp[k] & 255ull); }, [src, vals](int k) { return vals[src[k]]; },
+              [&](int slot, int r, int k) {
+                  if (!P.x_key) return;
+                  const unsigned row = (unsigned)bi * 16u + (unsigned)r;
+                  P.x_key[slot] = row; P.x_col[slot] = colidx[src[k]]; P.x_val[slot] = vals[src[k]];
+                  atomicAdd(&P.deferredcoo_ptr[row], 1);
+              }, P.out);
 }
 
 // two index bytes -> one byte of a nibble stream (src/encode.h:29-50)
@@ -323,21 +233,36 @@ int pool_begin(DevTile *D, size_t bytes)
     return 0;
 }
 inline void pool_end() { t_pool = Pool(); }
-template <class V>
-int dalloc(DevTile *D, V **out, size_t n, bool zero)
+int dalloc_raw(DevTile *D, void **out, size_t n, size_t elem, bool zero)
 {
-    const size_t need = pool_need(n, sizeof(V));
+    const size_t need = pool_need(n, elem);
     if (t_pool.left >= need) {   // (pool memory is zeroed already)
-        *out = (V *)t_pool.at; t_pool.at += need; t_pool.left -= need;
+        *out = t_pool.at; t_pool.at += need; t_pool.left -= need;
         return 0;
     }
     void *p = nullptr;
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(V) + 16;
+    const size_t bytes = std::max<size_t>(n, 1) * elem + 16;
     TC_TRY(hipMalloc(&p, bytes));
     D->allocs.push_back(p);
     if (zero) TC_TRY(hipMemsetAsync(p, 0, bytes, 0));
-    *out = (V *)p;
+    *out = p;
     return 0;
+}
+template <class V>
+int dalloc(DevTile *D, V **out, size_t n, bool zero) { return dalloc_raw(D, (void **)out, n, sizeof(V), zero); }
+// the member arrays of D->T (tile_fields.h) that are not allocated yet: what a pool must hold for them, and the arrays themselves (zeroed)
+inline size_t dev_count(const TileField &f) { return (size_t)(f.count + f.slack + f.dev_slack); }
+size_t fields_need(DevTile *D, const TileExtents &X, unsigned groups)
+{
+    size_t bytes = 0;
+    for_each_tile_field(D->T, X, groups, [&](const TileField &f) { if (!*f.ptr) bytes += pool_need(dev_count(f), f.elem); });
+    return bytes;
+}
+int dalloc_fields(DevTile *D, const TileExtents &X, unsigned groups)
+{
+    int rc = 0;
+    for_each_tile_field(D->T, X, groups, [&](const TileField &f) { if (rc == 0 && !*f.ptr) rc = dalloc_raw(D, f.ptr, dev_count(f), f.elem, true); });
+    return rc;
 }
 // hipFree waits for the whole device — also for the values' upload that runs beside the first steps of create_impl: while that is under way, memory to be released is only noted
 thread_local std::vector<void *> *t_free_later = nullptr;
@@ -441,9 +366,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
 
     // ---- tile list
     int tilenum = 0;
-    int *d_tile_ptr = nullptr;
-    if (dalloc(D, &d_tile_ptr, (size_t)tilem + 1, true)) return -3;
-    T.tile_ptr = d_tile_ptr;
+    if (dalloc(D, &T.tile_ptr, (size_t)tilem + 1, true)) return -3;
     u64 *d_uniq = nullptr; int *d_counts = nullptr, *d_nruns = nullptr;
     if (nnz > 0) {
         if (dalloc(D, &d_uniq, (size_t)nnz, false) || dalloc(D, &d_counts, (size_t)nnz + 1, false) || dalloc(D, &d_nruns, 1, true)) return -3;
@@ -458,20 +381,22 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     T.tilenum = tilenum;
     if (!(flags & TILESPMV_CREATE_QUIET)) printf("\n  The number of tile = %i\n", tilenum);
     const size_t np1 = (size_t)tilenum + 1;
-    // ---- pool of the per-tile arrays: 3 + 9 + 7 arrays of tilenum (+ 1) elements
-    if (pool_begin(D, 3 * pool_need(np1, 4) + 3 * pool_need(np1, 1) + 6 * pool_need(np1, 4) + 7 * pool_need(np1, 4) + pool_need(16, 8))) return -3;
-    int *d_tile_columnidx = nullptr, *d_tile_nnz = nullptr, *d_tile_bi = nullptr;
-    if (dalloc(D, &d_tile_columnidx, (size_t)tilenum, true) || dalloc(D, &d_tile_nnz, np1, true) || dalloc(D, &d_tile_bi, (size_t)tilenum, true)) return -3;
-    T.tile_columnidx = d_tile_columnidx; T.tile_nnz = d_tile_nnz; D->tile_bi = d_tile_bi;
+    // ---- pool of the arrays of tilenum (+ 1) elements: the table's (tile_ptr exists already), and beside them every tile's tile-row, the HYB tiles' byte counts and the scans' totals
+    constexpr int NS = 14;
+    TileExtents X; X.rowA = rowA;
+    if (pool_begin(D, fields_need(D, X, TF_LIST | TF_TILE) + pool_need((size_t)tilenum, 4) + pool_need(np1, 4) + pool_need(NS, 8))) return -3;
+    int *d_tile_bi = nullptr, *d_hyb_bytes = nullptr;
+    if (dalloc_fields(D, X, TF_LIST | TF_TILE) || dalloc(D, &d_tile_bi, (size_t)tilenum, true) || dalloc(D, &d_hyb_bytes, np1, true)) return -3;
+    D->tile_bi = d_tile_bi;
     if (tilenum > 0) {
-        hipLaunchKernelGGL(k_tc_tiles, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, cb_bits, d_uniq, d_tile_columnidx, d_tile_bi, d_tile_ptr);
+        hipLaunchKernelGGL(k_tc_tiles, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, cb_bits, d_uniq, T.tile_columnidx, d_tile_bi, T.tile_ptr);
         TC_TRY(hipGetLastError());
         // tile_nnz = exclusive scan of the run lengths (np1 elements: the last one is the total)
         TC_TRY(hipMemsetAsync(d_counts + tilenum, 0, sizeof(int), 0));
         size_t tmp_b = 0; void *tmp = nullptr;
-        TC_TRY(prims::scan_int(nullptr, tmp_b, d_counts, d_tile_nnz, np1, (hipStream_t)0));
+        TC_TRY(prims::scan_int(nullptr, tmp_b, d_counts, T.tile_nnz, np1, (hipStream_t)0));
         TC_TRY(hipMalloc(&tmp, std::max<size_t>(tmp_b, 16)));
-        hipError_t e = prims::scan_int(tmp, tmp_b, d_counts, d_tile_nnz, np1, (hipStream_t)0);
+        hipError_t e = prims::scan_int(tmp, tmp_b, d_counts, T.tile_nnz, np1, (hipStream_t)0);
         if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)0);
         free_now_or_later(tmp);
         TC_TRY(e);
@@ -480,25 +405,15 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     D->ms_tiles = now_ms() - t0; t0 = now_ms();
 
     // ---- per-tile metadata + format selection + scans
-    TileArrays A{};
-    int *off7[7];
-    if (dalloc(D, &A.Format, (size_t)tilenum, true) || dalloc(D, &A.blknnz, np1, true) || dalloc(D, &A.blknnznnz, np1, true) || dalloc(D, &A.dnsrowptr, np1, true) ||
-        dalloc(D, &A.dnscolptr, np1, true) || dalloc(D, &A.tilewidth, (size_t)tilenum, true) || dalloc(D, &A.csrptr_offset, np1, true) || dalloc(D, &A.hyb_coocount, np1, true) ||
-        dalloc(D, &A.new_coocount, np1, true) || dalloc(D, &A.hyb_bytes, np1, true))
-        return -3;
-    for (int f = 0; f < 7; f++) { if (dalloc(D, &off7[f], np1, true)) return -3; A.fmt_offset[f] = off7[f]; }
-    T.Format = A.Format; T.blknnz = A.blknnz; T.blknnznnz = A.blknnznnz; T.dnsrowptr = A.dnsrowptr; T.dnscolptr = A.dnscolptr; T.tilewidth = A.tilewidth;
-    T.csrptr_offset = A.csrptr_offset; T.hyb_coocount = A.hyb_coocount; T.new_coocount = A.new_coocount;
-    T.csr_offset = off7[TILESPMV_FMT_CSR]; T.coo_offset = off7[TILESPMV_FMT_COO]; T.ell_offset = off7[TILESPMV_FMT_ELL]; T.hyb_offset = off7[TILESPMV_FMT_HYB];
-    T.dns_offset = off7[TILESPMV_FMT_DNS]; T.dnsrow_offset = off7[TILESPMV_FMT_DNSROW]; T.dnscol_offset = off7[TILESPMV_FMT_DNSCOL];
+    const TileArrays A{T.Format, T.blknnz, T.blknnznnz, T.dnsrowptr, T.dnscolptr, T.tilewidth, T.csrptr_offset, T.hyb_coocount, T.new_coocount,
+                       {T.csr_offset, T.coo_offset, T.ell_offset, T.hyb_offset, T.dns_offset, T.dnsrow_offset, T.dnscol_offset}, d_hyb_bytes};
     if (tilenum > 0) {
-        hipLaunchKernelGGL(k_tc_select, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, tilen, rowA, colA, allow_hyb, cdna4, d_tile_nnz, d_tile_bi, d_tile_columnidx, D->key, A);
+        hipLaunchKernelGGL(k_tc_select, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, tilen, rowA, colA, allow_hyb, cdna4, T.tile_nnz, d_tile_bi, T.tile_columnidx, D->key, A);
         TC_TRY(hipGetLastError());
     }
     ScanSet S{};
-    int *scans[] = {T.csr_offset, T.csrptr_offset, T.coo_offset, T.ell_offset, T.hyb_offset, T.dns_offset, T.dnsrow_offset, T.dnscol_offset, T.dnsrowptr, T.dnscolptr, T.hyb_coocount, T.new_coocount, T.blknnz, A.hyb_bytes};
+    int *scans[] = {T.csr_offset, T.csrptr_offset, T.coo_offset, T.ell_offset, T.hyb_offset, T.dns_offset, T.dnsrow_offset, T.dnscol_offset, T.dnsrowptr, T.dnscolptr, T.hyb_coocount, T.new_coocount, T.blknnz, d_hyb_bytes};
     static const char *names[] = {"csr_offset", "csrptr_offset", "coo_offset", "ell_offset", "hyb_offset", "dns_offset", "dnsrow_offset", "dnscol_offset", "dnsrowptr", "dnscolptr", "hyb_coocount", "new_coocount", "blknnz", "hybIdx bytes"};
-    constexpr int NS = 14;
     for (int k = 0; k < NS; k++) S.a[k] = scans[k];
     unsigned long long *d_totals = nullptr, h_totals[NS] = {0};
     if (dalloc(D, &d_totals, NS, true)) return -3;
@@ -521,70 +436,49 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     }
     T.csrsize = (int)h_totals[0]; T.csrptrlen = (int)h_totals[1]; T.coosize = (int)h_totals[2]; T.ellsize = (int)h_totals[3];
     T.hybsize = (int)h_totals[4]; T.hybcoosize = (int)h_totals[10]; T.hybellsize = T.hybsize - T.hybcoosize;   // (a HYB tile stores its ELL part + its remainder)
-    D->hyb_byte_off = A.hyb_bytes;   // (scanned: per tile its first byte in hybIdx)
+    D->hyb_byte_off = d_hyb_bytes;   // (scanned: per tile its first byte in hybIdx)
     if (T.hybsize > 0) {             // ... and as the 64-bit offsets the plan builders' per-tile functions take (plan_tile_ops.h hyb_off)
         long long *d_off64 = nullptr;
         if (dalloc(D, &d_off64, np1, true)) return -3;
-        hipLaunchKernelGGL(k_tc_widen, dim3(blocks_for((long long)np1, 256)), dim3(256), 0, 0, (long long)np1, (const int *)A.hyb_bytes, d_off64);
+        hipLaunchKernelGGL(k_tc_widen, dim3(blocks_for((long long)np1, 256)), dim3(256), 0, 0, (long long)np1, (const int *)d_hyb_bytes, d_off64);
         TC_TRY(hipGetLastError());
         D->hyb_off = d_off64;
     }
     T.dnssize = (int)h_totals[5]; T.dnsrowsize = (int)h_totals[6]; T.dnscolsize = (int)h_totals[7]; T.coototal = (int)h_totals[11];
-    const int ndenserow = (int)h_totals[8], ndensecol = (int)h_totals[9];
+    X.n_dnsrow = (long long)h_totals[8]; X.n_dnscol = (long long)h_totals[9];
     D->ms_select = now_ms() - t0; t0 = now_ms();
     pool_end();
 
-    // ---- payload arrays: one pool
+    // ---- payload arrays: one pool for the table's, the two one-byte-per-slot index arrays and the tile-ordered list of extracted entries
+    const unsigned payload = TF_PAYLOAD | (want_deferred ? TF_EXTRACTED : 0u);
     {
-        const size_t sv = sizeof(val_t);
-        size_t bytes = pool_need((size_t)T.csrsize, sv) + pool_need((size_t)T.csrptrlen, 1) + pool_need((size_t)T.csrsize, 1) + pool_need(((size_t)T.csrsize + 1) / 2, 1) + pool_need((size_t)T.coosize, sv) +
-                       pool_need((size_t)T.coosize, 1) + pool_need((size_t)T.ellsize, sv) + pool_need((size_t)T.ellsize, 1) + pool_need(((size_t)T.ellsize + 1) / 2, 1) + pool_need((size_t)T.hybsize + 1, sv) + pool_need(((size_t)T.hybellsize + 1) / 2 + (size_t)T.hybcoosize + (size_t)tilem + 8, 1) +
-                       pool_need((size_t)T.dnssize, sv) + pool_need((size_t)T.dnsrowsize, sv) + pool_need((size_t)ndenserow, 1) + pool_need((size_t)T.dnscolsize, sv) + pool_need((size_t)ndensecol, 1);
-        if (want_deferred) bytes += pool_need((size_t)rowA + 1, 4) + pool_need((size_t)T.coototal, 4) + pool_need((size_t)T.coototal, sv) + 2 * pool_need((size_t)T.coototal, 4) + pool_need((size_t)T.coototal, sv);
+        size_t bytes = fields_need(D, X, payload) + pool_need((size_t)T.csrsize, 1) + pool_need((size_t)T.ellsize, 1);
+        if (want_deferred) bytes += 2 * pool_need((size_t)T.coototal, 4) + pool_need((size_t)T.coototal, sizeof(val_t));
         if (pool_begin(D, bytes)) return -3;
     }
     PackArrays P{};
-    unsigned char *d_csr_idx = nullptr, *d_ell_idx = nullptr, *d_hybidx = nullptr; val_t *d_hybval = nullptr;
-    if (dalloc(D, &P.Blockcsr_Val, (size_t)T.csrsize, true) || dalloc(D, &P.Blockcsr_Ptr, (size_t)T.csrptrlen, true) || dalloc(D, &P.csr_col, (size_t)T.csrsize, true) ||
-        dalloc(D, &d_csr_idx, ((size_t)T.csrsize + 1) / 2, true) || dalloc(D, &P.Blockcoo_Val, (size_t)T.coosize, true) || dalloc(D, &P.coo_compressed_Idx, (size_t)T.coosize, true) ||
-        dalloc(D, &P.Blockell_Val, (size_t)T.ellsize, true) || dalloc(D, &P.ell_col, (size_t)T.ellsize, true) || dalloc(D, &d_ell_idx, ((size_t)T.ellsize + 1) / 2, true) ||
-        dalloc(D, &d_hybval, (size_t)T.hybsize + 1, true) || dalloc(D, &d_hybidx, ((size_t)T.hybellsize + 1) / 2 + (size_t)T.hybcoosize + (size_t)tilem + 8, true) || dalloc(D, &P.Blockdense_Val, (size_t)T.dnssize, true) ||
-        dalloc(D, &P.Blockdenserow_Val, (size_t)T.dnsrowsize, true) || dalloc(D, &P.denserowid, (size_t)ndenserow, true) || dalloc(D, &P.Blockdensecol_Val, (size_t)T.dnscolsize, true) ||
-        dalloc(D, &P.densecolid, (size_t)ndensecol, true))
-        return -3;
-    T.Blockcsr_Val = P.Blockcsr_Val; T.Blockcsr_Ptr = P.Blockcsr_Ptr; T.csr_compressedIdx = d_csr_idx;
-    T.Blockcoo_Val = P.Blockcoo_Val; T.coo_compressed_Idx = P.coo_compressed_Idx;
-    T.Blockell_Val = P.Blockell_Val; T.ell_compressedIdx = d_ell_idx;
-    T.Blockhyb_Val = d_hybval; T.hybIdx = d_hybidx;
-    P.Blockhyb_Val = d_hybval; P.hybIdx = d_hybidx; P.hyb_byte_off = A.hyb_bytes;
-    T.Blockdense_Val = P.Blockdense_Val; T.Blockdenserow_Val = P.Blockdenserow_Val; T.denserowid = P.denserowid;
-    T.Blockdensecol_Val = P.Blockdensecol_Val; T.densecolid = P.densecolid;
-    int *d_dptr = nullptr, *d_dcol = nullptr; val_t *d_dval = nullptr;
-    if (want_deferred) {
-        if (dalloc(D, &d_dptr, (size_t)rowA + 1, true) || dalloc(D, &d_dcol, (size_t)T.coototal, true) || dalloc(D, &d_dval, (size_t)T.coototal, true) ||
-            dalloc(D, &P.x_key, (size_t)T.coototal, true) || dalloc(D, &P.x_col, (size_t)T.coototal, true) || dalloc(D, &P.x_val, (size_t)T.coototal, true))
-            return -3;
-        P.deferredcoo_ptr = d_dptr;
-        T.deferredcoo_ptr = d_dptr; T.deferredcoo_colidx = d_dcol; T.deferredcoo_val = d_dval;
-    }
+    unsigned char *d_csr_col = nullptr, *d_ell_col = nullptr;
+    if (dalloc_fields(D, X, payload) || dalloc(D, &d_csr_col, (size_t)T.csrsize, true) || dalloc(D, &d_ell_col, (size_t)T.ellsize, true)) return -3;
+    if (want_deferred && (dalloc(D, &P.x_key, (size_t)T.coototal, true) || dalloc(D, &P.x_col, (size_t)T.coototal, true) || dalloc(D, &P.x_val, (size_t)T.coototal, true))) return -3;
+    P.out = pack_out_of(T, d_csr_col, d_ell_col); P.hyb_byte_off = d_hyb_bytes; P.deferredcoo_ptr = T.deferredcoo_ptr;
     pool_end();
     TC_TRY(values.wait());   // the packing reads the values
     t_free_later = nullptr;
     for (void *q : later) (void)hipFree(q);
     later.clear();
     if (tilenum > 0) {
-        hipLaunchKernelGGL(k_tc_pack, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, tilen, rowA, colA, T, d_tile_bi, D->key, D->ent, d_colidx, d_val, P);
+        hipLaunchKernelGGL(k_tc_pack, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, rowA, T, d_tile_bi, D->key, D->ent, d_colidx, d_val, P);
         TC_TRY(hipGetLastError());
     }
-    if (T.csrsize > 0) hipLaunchKernelGGL(k_tc_nibbles, dim3(blocks_for(((long long)T.csrsize + 1) / 2, 256)), dim3(256), 0, 0, P.csr_col, d_csr_idx, (long long)T.csrsize);
-    if (T.ellsize > 0) hipLaunchKernelGGL(k_tc_nibbles, dim3(blocks_for(((long long)T.ellsize + 1) / 2, 256)), dim3(256), 0, 0, P.ell_col, d_ell_idx, (long long)T.ellsize);
+    if (T.csrsize > 0) hipLaunchKernelGGL(k_tc_nibbles, dim3(blocks_for(((long long)T.csrsize + 1) / 2, 256)), dim3(256), 0, 0, d_csr_col, T.csr_compressedIdx, (long long)T.csrsize);
+    if (T.ellsize > 0) hipLaunchKernelGGL(k_tc_nibbles, dim3(blocks_for(((long long)T.ellsize + 1) / 2, 256)), dim3(256), 0, 0, d_ell_col, T.ell_compressedIdx, (long long)T.ellsize);
     TC_TRY(hipGetLastError());
     if (want_deferred) {
         // rows of the extracted matrix: counts -> pointers; entries: stable sort of the tile-ordered list by row = "order of appearance" inside every row (src/csr2tile.h:943-950)
         size_t tmp_b = 0; void *tmp = nullptr;
-        TC_TRY(prims::scan_int(nullptr, tmp_b, d_dptr, d_dptr, (size_t)rowA + 1, (hipStream_t)0));
+        TC_TRY(prims::scan_int(nullptr, tmp_b, T.deferredcoo_ptr, T.deferredcoo_ptr, (size_t)rowA + 1, (hipStream_t)0));
         TC_TRY(hipMalloc(&tmp, std::max<size_t>(tmp_b, 16)));
-        hipError_t e = prims::scan_int(tmp, tmp_b, d_dptr, d_dptr, (size_t)rowA + 1, (hipStream_t)0);
+        hipError_t e = prims::scan_int(tmp, tmp_b, T.deferredcoo_ptr, T.deferredcoo_ptr, (size_t)rowA + 1, (hipStream_t)0);
         (void)hipDeviceSynchronize();
         (void)hipFree(tmp);
         TC_TRY(e);
@@ -600,7 +494,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
             TC_TRY(hipMalloc(&tmp, std::max<size_t>(tmp_b, 16)));
             e = prims::sort_pairs_u32_int(tmp, tmp_b, k_cur, k_alt, v_cur, v_alt, (size_t)T.coototal, 0u, row_bits, (hipStream_t)0);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_tc_deferred, dim3(blocks_for(T.coototal, 256)), dim3(256), 0, 0, T.coototal, (const int *)v_cur, (const int *)P.x_col, (const val_t *)P.x_val, d_dcol, d_dval);
+                hipLaunchKernelGGL(k_tc_deferred, dim3(blocks_for(T.coototal, 256)), dim3(256), 0, 0, T.coototal, (const int *)v_cur, (const int *)P.x_col, (const val_t *)P.x_val, T.deferredcoo_colidx, T.deferredcoo_val);
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -609,7 +503,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
             dfree(D, key_b2); dfree(D, pos_a); dfree(D, pos_b);
             int *d_cnt = nullptr;
             if (dalloc(D, &d_cnt, 1, true)) return -3;
-            hipLaunchKernelGGL(k_tc_unsorted_rows, dim3(blocks_for(rowA, 256)), dim3(256), 0, 0, rowA, (const int *)d_dptr, (const int *)d_dcol, d_cnt);
+            hipLaunchKernelGGL(k_tc_unsorted_rows, dim3(blocks_for(rowA, 256)), dim3(256), 0, 0, rowA, (const int *)T.deferredcoo_ptr, (const int *)T.deferredcoo_colidx, d_cnt);
             TC_TRY(hipGetLastError());
             TC_TRY(hipMemcpy(&D->unsorted_rows, d_cnt, sizeof(int), hipMemcpyDeviceToHost));
             dfree(D, d_cnt);
@@ -618,7 +512,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
         D->have_deferred = true;
     }
     TC_TRY(hipDeviceSynchronize());
-    dfree(D, P.csr_col); dfree(D, P.ell_col);
+    dfree(D, d_csr_col); dfree(D, d_ell_col);
     D->ms_pack = now_ms() - t0;
     if (verbose)
         fprintf(stderr, "tilespmv: device Tile_create: upload of the index arrays %.1f ms (the values cross the bus behind the next three steps), keys + sort %.1f, tile list %.1f, selection + scans %.1f, packing %.1f (%d tiles, %lld nonzeros)\n", D->ms_upload, D->ms_sort, D->ms_tiles,
@@ -656,55 +550,20 @@ int devtile_download(const DevTile *D, Tile_matrix *H)
 {
     const Tile_matrix &T = D->T;
     memset(H, 0, sizeof(*H));
-    H->tilem = T.tilem; H->tilen = T.tilen; H->tilenum = T.tilenum;
-    H->csrsize = T.csrsize; H->csrptrlen = T.csrptrlen; H->coosize = T.coosize; H->ellsize = T.ellsize; H->hybsize = T.hybsize; H->hybellsize = T.hybellsize; H->hybcoosize = T.hybcoosize;
-    H->dnssize = T.dnssize; H->dnsrowsize = T.dnsrowsize; H->dnscolsize = T.dnscolsize; H->coototal = T.coototal;
-    const size_t tn = (size_t)T.tilenum, np1 = tn + 1;
+    copy_tile_scalars(*H, T);
     int rc = 0;
-    auto get = [&](auto **dst, const auto *src, size_t n) {
-        typedef typename std::remove_pointer<typename std::remove_reference<decltype(*dst)>::type>::type V;
-        *dst = zalloc<V>(n);
-        if (n && src && hipMemcpy(*dst, src, n * sizeof(V), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = -3; }
+    auto get = [&](const TileField &f) {   // a host array for the member, slack included, filled from the device's (a member the device never built stays zero)
+        zalloc_tile_field(f);
+        const void *src = same_tile_field(T, *H, f);
+        const size_t bytes = (size_t)(f.count + f.slack) * f.elem;
+        if (bytes && src && hipMemcpy(*f.ptr, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); rc = -3; }
     };
-    get(&H->tile_ptr, T.tile_ptr, (size_t)T.tilem + 1);
-    get(&H->tile_columnidx, T.tile_columnidx, tn);
-    get(&H->tile_nnz, T.tile_nnz, np1);
-    get(&H->Format, T.Format, tn);
-    get(&H->blknnz, T.blknnz, np1);
-    get(&H->blknnznnz, T.blknnznnz, np1);
-    get(&H->dnsrowptr, T.dnsrowptr, np1);
-    get(&H->dnscolptr, T.dnscolptr, np1);
-    get(&H->tilewidth, T.tilewidth, tn);
-    get(&H->csr_offset, T.csr_offset, np1);
-    get(&H->csrptr_offset, T.csrptr_offset, np1);
-    get(&H->coo_offset, T.coo_offset, np1);
-    get(&H->ell_offset, T.ell_offset, np1);
-    get(&H->hyb_offset, T.hyb_offset, np1);
-    get(&H->hyb_coocount, T.hyb_coocount, np1);
-    get(&H->dns_offset, T.dns_offset, np1);
-    get(&H->dnsrow_offset, T.dnsrow_offset, np1);
-    get(&H->dnscol_offset, T.dnscol_offset, np1);
-    get(&H->new_coocount, T.new_coocount, np1);
-    get(&H->Blockcsr_Val, T.Blockcsr_Val, (size_t)T.csrsize);
-    get(&H->Blockcsr_Ptr, T.Blockcsr_Ptr, (size_t)T.csrptrlen);
-    get(&H->csr_compressedIdx, T.csr_compressedIdx, ((size_t)T.csrsize + 1) / 2);
-    get(&H->Blockcoo_Val, T.Blockcoo_Val, (size_t)T.coosize);
-    get(&H->coo_compressed_Idx, T.coo_compressed_Idx, (size_t)T.coosize);
-    get(&H->Blockell_Val, T.Blockell_Val, (size_t)T.ellsize);
-    get(&H->ell_compressedIdx, T.ell_compressedIdx, ((size_t)T.ellsize + 1) / 2);
-    get(&H->Blockhyb_Val, T.Blockhyb_Val, (size_t)T.hybellsize + (size_t)T.hybcoosize);
-    get(&H->hybIdx, T.hybIdx, ((size_t)T.hybellsize + 1) / 2 + (size_t)T.hybcoosize + (size_t)T.tilem + 8);
-    get(&H->Blockdense_Val, T.Blockdense_Val, (size_t)T.dnssize);
-    get(&H->Blockdenserow_Val, T.Blockdenserow_Val, (size_t)T.dnsrowsize);
-    int ndr = 0, ndc = 0;
-    if (tn) { ndr = H->dnsrowptr[tn]; ndc = H->dnscolptr[tn]; }
-    get(&H->denserowid, T.denserowid, (size_t)ndr);
-    get(&H->Blockdensecol_Val, T.Blockdensecol_Val, (size_t)T.dnscolsize);
-    get(&H->densecolid, T.densecolid, (size_t)ndc);
+    TileExtents X; X.rowA = D->rowA;
+    for_each_tile_field(*H, X, TF_LIST | TF_TILE, get);   // the per-tile arrays first: two of them say how long the id arrays are
+    if (T.tilenum) { X.n_dnsrow = H->dnsrowptr[T.tilenum]; X.n_dnscol = H->dnscolptr[T.tilenum]; }
+    for_each_tile_field(*H, X, TF_PAYLOAD, get);
     if (D->have_deferred) {
-        get(&H->deferredcoo_val, T.deferredcoo_val, (size_t)T.coototal);
-        get(&H->deferredcoo_colidx, T.deferredcoo_colidx, (size_t)T.coototal);
-        get(&H->deferredcoo_ptr, T.deferredcoo_ptr, (size_t)D->rowA + 1);
+        for_each_tile_field(*H, X, TF_EXTRACTED, get);
         if (rc == 0 && D->unsorted_rows > 0)   // rows whose columns do not increase (unsorted CSR input): the reference's pivot sort, on the host (src/csr2tile.h:951-958, src/utils.h:103-137)
             parallel_chunks(D->rowA, 4096, [&](int64_t b, int64_t e, int) {
                 for (int64_t r = b; r < e; r++) {

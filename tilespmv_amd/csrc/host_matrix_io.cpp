@@ -9,6 +9,7 @@
 #include <string>
 
 #include "host_util.h"
+#include "tile_fields.h"
 
 namespace {
 
@@ -32,40 +33,8 @@ bool monotone(const int *a, long long n, long long last)   // exclusive prefix: 
     return true;
 }
 
-struct Field { void **ptr; size_t elem; long long count; };
-
-// Element counts of every member array after Tile_create.
-std::vector<Field> fields_of(Tile_matrix *T, int rowA, long long n_dnsrow, long long n_dnscol)
-{
-    const long long n = T->tilenum, n1 = n + 1, sv = sizeof(tilespmv::val_t);
-    return {
-        {(void **)&T->tile_ptr, 4, (long long)T->tilem + 1}, {(void **)&T->tile_columnidx, 4, n}, {(void **)&T->tile_nnz, 4, n1},
-        {(void **)&T->Format, 1, n}, {(void **)&T->blknnz, 4, n1}, {(void **)&T->blknnznnz, 1, n1},
-        {(void **)&T->dnsrowptr, 4, n1}, {(void **)&T->dnscolptr, 4, n1}, {(void **)&T->tilewidth, 1, n},
-        {(void **)&T->csr_offset, 4, n1}, {(void **)&T->csrptr_offset, 4, n1}, {(void **)&T->coo_offset, 4, n1},
-        {(void **)&T->ell_offset, 4, n1}, {(void **)&T->hyb_offset, 4, n1}, {(void **)&T->hyb_coocount, 4, n1},
-        {(void **)&T->dns_offset, 4, n1}, {(void **)&T->dnsrow_offset, 4, n1}, {(void **)&T->dnscol_offset, 4, n1},
-        {(void **)&T->new_coocount, 4, n1},
-        {(void **)&T->Blockcsr_Val, (size_t)sv, T->csrsize}, {(void **)&T->Blockcsr_Ptr, 1, T->csrptrlen},
-        {(void **)&T->csr_compressedIdx, 1, ((long long)T->csrsize + 1) / 2},
-        {(void **)&T->Blockcoo_Val, (size_t)sv, T->coosize}, {(void **)&T->coo_compressed_Idx, 1, T->coosize},
-        {(void **)&T->Blockell_Val, (size_t)sv, T->ellsize}, {(void **)&T->ell_compressedIdx, 1, ((long long)T->ellsize + 1) / 2},
-        {(void **)&T->Blockhyb_Val, (size_t)sv, (long long)T->hybellsize + T->hybcoosize},
-        {(void **)&T->hybIdx, 1, ((long long)T->hybellsize + 1) / 2 + T->hybcoosize},
-        {(void **)&T->Blockdense_Val, (size_t)sv, T->dnssize},
-        {(void **)&T->Blockdenserow_Val, (size_t)sv, T->dnsrowsize}, {(void **)&T->denserowid, 1, n_dnsrow},
-        {(void **)&T->Blockdensecol_Val, (size_t)sv, T->dnscolsize}, {(void **)&T->densecolid, 1, n_dnscol},
-        {(void **)&T->deferredcoo_val, (size_t)sv, T->coototal}, {(void **)&T->deferredcoo_colidx, 4, T->coototal},
-        {(void **)&T->deferredcoo_ptr, 4, (long long)rowA + 1},
-    };
-}
-
-int *scalars_of(Tile_matrix *T, int i)
-{
-    int *s[] = {&T->tilem, &T->tilen, &T->tilenum, &T->csrsize, &T->csrptrlen, &T->coosize, &T->ellsize, &T->hybsize,
-                &T->hybellsize, &T->hybcoosize, &T->dnssize, &T->dnsrowsize, &T->dnscolsize, &T->coototal};
-    return s[i];
-}
+using tilespmv::TileExtents; using tilespmv::TileField; using tilespmv::TF_ALL; using tilespmv::N_TILE_SCALARS;
+using tilespmv::for_each_tile_field; using tilespmv::tile_scalar;   // (tile_fields.h: the member arrays in file order, with their element counts, and the scalars)
 
 }  // namespace
 
@@ -76,20 +45,21 @@ extern "C" int tilespmv_matrix_save(const Tile_matrix *matrix, int rowA, int col
     if (!f) return -1;
     int head[4] = {(int)sizeof(tilespmv::val_t), rowA, colA, nnzA};
     bool ok = fwrite(MAGIC, 1, 8, f) == 8 && fwrite(head, sizeof(int), 4, f) == 4;
-    for (int i = 0; i < 14 && ok; i++) ok = fwrite(scalars_of(T, i), sizeof(int), 1, f) == 1;
+    for (int i = 0; i < N_TILE_SCALARS && ok; i++) ok = fwrite(&tile_scalar(*T, i), sizeof(int), 1, f) == 1;
     long long extra[2] = {T->tilenum >= 0 ? T->dnsrowptr[T->tilenum] : 0, T->tilenum >= 0 ? T->dnscolptr[T->tilenum] : 0};
     ok = ok && fwrite(extra, sizeof(long long), 2, f) == 2;
     unsigned long long sum[2] = {0, 0xCBF29CE484222325ull};   // payload bytes, FNV-1a-64 of header fields + payload
     sum[1] = fnv1a(head, sizeof(head), sum[1]);
-    for (int i = 0; i < 14; i++) sum[1] = fnv1a(scalars_of(T, i), sizeof(int), sum[1]);
+    for (int i = 0; i < N_TILE_SCALARS; i++) sum[1] = fnv1a(&tile_scalar(*T, i), sizeof(int), sum[1]);
     sum[1] = fnv1a(extra, sizeof(extra), sum[1]);
-    for (auto &fd : fields_of(T, rowA, extra[0], extra[1]))
+    const TileExtents X{rowA, extra[0], extra[1]};
+    for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) {
         if (fd.count > 0) { sum[0] += (unsigned long long)fd.count * fd.elem; sum[1] = fnv1a(*fd.ptr, (size_t)fd.count * fd.elem, sum[1]); }
+    });
     ok = ok && fwrite(sum, sizeof(unsigned long long), 2, f) == 2;
-    for (auto &fd : fields_of(T, rowA, extra[0], extra[1])) {
-        if (!ok) break;
-        if (fd.count > 0) ok = fwrite(*fd.ptr, fd.elem, (size_t)fd.count, f) == (size_t)fd.count;
-    }
+    for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) {
+        if (ok && fd.count > 0) ok = fwrite(*fd.ptr, fd.elem, (size_t)fd.count, f) == (size_t)fd.count;
+    });
     ok = (fclose(f) == 0) && ok;
     return ok ? 0 : -3;
 }
@@ -103,7 +73,7 @@ extern "C" int tilespmv_matrix_load(Tile_matrix *matrix, int *rowA, int *colA, M
     if (fread(magic, 1, 8, f) != 8 || memcmp(magic, MAGIC, 8) != 0 || fread(head, sizeof(int), 4, f) != 4) { fclose(f); return -2; }
     if (head[0] != (int)sizeof(tilespmv::val_t)) { fclose(f); return -5; }  // written by the library of the other value type
     bool ok = true;
-    for (int i = 0; i < 14 && ok; i++) ok = fread(scalars_of(matrix, i), sizeof(int), 1, f) == 1;
+    for (int i = 0; i < N_TILE_SCALARS && ok; i++) ok = fread(&tile_scalar(*matrix, i), sizeof(int), 1, f) == 1;
     long long extra[2] = {0, 0};
     ok = ok && fread(extra, sizeof(long long), 2, f) == 2;
     unsigned long long sum[2] = {0, 0};
@@ -112,23 +82,24 @@ extern "C" int tilespmv_matrix_load(Tile_matrix *matrix, int *rowA, int *colA, M
     // ---- the header must describe a possible matrix before anything is allocated from it
     Tile_matrix *T = matrix;
     bool sane = head[1] >= 0 && head[2] >= 0 && head[3] >= 0 && extra[0] >= 0 && extra[1] >= 0;
-    for (int i = 0; i < 14 && sane; i++) sane = *scalars_of(T, i) >= 0;
+    for (int i = 0; i < N_TILE_SCALARS && sane; i++) sane = tile_scalar(*T, i) >= 0;
     sane = sane && T->tilem == (head[1] + 15) / 16 && T->tilen == (head[2] + 15) / 16 && T->hybsize == T->hybellsize + T->hybcoosize;
     unsigned long long bytes = 0;
-    if (sane) for (auto &fd : fields_of(T, head[1], extra[0], extra[1])) bytes += (unsigned long long)std::max<long long>(fd.count, 0) * fd.elem;
+    const TileExtents X{head[1], extra[0], extra[1]};
+    if (sane) for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) { bytes += (unsigned long long)std::max<long long>(fd.count, 0) * fd.elem; });
     const long here = ftell(f);
     sane = sane && bytes == sum[0] && fseek(f, 0, SEEK_END) == 0 && (unsigned long long)(ftell(f) - here) == bytes && fseek(f, here, SEEK_SET) == 0;
     if (!sane) { fclose(f); memset(matrix, 0, sizeof(*matrix)); return -6; }   // corrupt, truncated or stale cache
     unsigned long long h = 0xCBF29CE484222325ull;
     h = fnv1a(head, sizeof(head), h);
-    for (int i = 0; i < 14; i++) h = fnv1a(scalars_of(matrix, i), sizeof(int), h);
+    for (int i = 0; i < N_TILE_SCALARS; i++) h = fnv1a(&tile_scalar(*matrix, i), sizeof(int), h);
     h = fnv1a(extra, sizeof(extra), h);
-    for (auto &fd : fields_of(matrix, head[1], extra[0], extra[1])) {
+    for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) {
+        if (!ok) return;
         *fd.ptr = calloc((size_t)std::max<long long>(fd.count, 1), fd.elem);
-        if (!*fd.ptr) { ok = false; break; }
-        if (fd.count > 0 && fread(*fd.ptr, fd.elem, (size_t)fd.count, f) != (size_t)fd.count) { ok = false; break; }
-        if (fd.count > 0) h = fnv1a(*fd.ptr, (size_t)fd.count * fd.elem, h);
-    }
+        ok = *fd.ptr && (fd.count <= 0 || fread(*fd.ptr, fd.elem, (size_t)fd.count, f) == (size_t)fd.count);
+        if (ok && fd.count > 0) h = fnv1a(*fd.ptr, (size_t)fd.count * fd.elem, h);
+    });
     fclose(f);
     if (!ok) { Tile_destroy(matrix); return -3; }
     // ---- payload intact, and the prefix arrays that everything else indexes with are consistent

@@ -8,11 +8,15 @@
 //   * all sizes are accumulated in 64 bits and checked against the int32 offsets that the
 //     Tile_matrix API exposes (the reference overflows silently, e.g. :912);
 //   * threads come from std::thread (no OpenMP runtime dependency).
+// Shared with the device builder (hip_tile_create.hip): the selection rule (tile_select.h), the per-tile packer (tile_pack.h) and the table of member arrays
+// (tile_fields.h).  Its own: how entries get into tile order (passes 1 and 2: stamp arrays per tile-row; the device sorts once).
 // What each output field means: SURVEY.md Appendix A.  Selection rules: src/csr2tile.h:143-325.
 #include <sys/time.h>
 #include <cmath>
 
 #include "host_util.h"
+#include "tile_fields.h"
+#include "tile_pack.h"
 #include "tile_select.h"
 
 namespace tilespmv {
@@ -87,8 +91,8 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
 
     const int64_t nnz_used = rowptr[rowA];
     const size_t np1 = (size_t)tilenum + 1;
-    T->tile_columnidx = zalloc<int>(tilenum);
-    T->tile_nnz = zalloc<int>(np1);
+    TileExtents X; X.rowA = rowA;
+    for_each_tile_field(*T, X, TF_LIST, zalloc_tile_field);
     uint8_t *cnt_row = zalloc<uint8_t>((size_t)tilenum * BS);
     int *ent = zalloc<int>((size_t)nnz_used);        // CSR position of each entry, tile order
     uint8_t *lrc = zalloc<uint8_t>((size_t)nnz_used);  // (local row << 4) | local col, tile order
@@ -133,22 +137,8 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
 
     lap("pass 2 (tile columns, tile-ordered gather)");
     // ---- per-tile metadata + format selection
-    T->Format = zalloc<char>(tilenum);
-    T->blknnz = zalloc<int>(np1);
-    T->blknnznnz = zalloc<unsigned char>(np1);
-    T->dnsrowptr = zalloc<int>(np1);
-    T->dnscolptr = zalloc<int>(np1);
-    T->tilewidth = zalloc<char>(tilenum);
-    T->csr_offset = zalloc<int>(np1);
-    T->csrptr_offset = zalloc<int>(np1);
-    T->coo_offset = zalloc<int>(np1);
-    T->ell_offset = zalloc<int>(np1);
-    T->hyb_offset = zalloc<int>(np1);
-    T->hyb_coocount = zalloc<int>(np1);
-    T->dns_offset = zalloc<int>(np1);
-    T->dnsrow_offset = zalloc<int>(np1);
-    T->dnscol_offset = zalloc<int>(np1);
-    T->new_coocount = zalloc<int>(np1);
+    for_each_tile_field(*T, X, TF_TILE, zalloc_tile_field);
+    int *hyb_bytes = zalloc<int>(np1);   // HYB tiles: bytes of the tile in hybIdx (scanned into the tile's byte offset)
 
     parallel_chunks(tilem, 256, [&](int64_t b, int64_t e, int) {
         for (int bi = (int)b; bi < (int)e; bi++) {
@@ -168,136 +158,45 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
                 int *dst[7] = { T->csr_offset, T->coo_offset, T->ell_offset, T->hyb_offset, T->dns_offset,
                                 T->dnsrow_offset, T->dnscol_offset };
                 dst[c.fmt][t] = c.stored;
+                if (c.fmt == TILESPMV_FMT_HYB) hyb_bytes[t] = (c.width * rowlen + 1) / 2 + c.hybcoo;   // ELL part in nibbles (rounded up to a byte), then one byte per remainder entry
             }
         }
     });
     lap("format selection");
-    int64_t hybell = 0;
-    {
-        std::vector<int64_t> part((size_t)host_threads(), 0);
-        parallel_chunks(tilem, 4096, [&](int64_t b, int64_t e, int tid) {
-            int64_t acc = 0;
-            for (int bi = (int)b; bi < (int)e; bi++) {
-                const int rowlen = tile_rowlen(bi, tilem, rowA);
-                for (int t = T->tile_ptr[bi]; t < T->tile_ptr[bi + 1]; t++)
-                    if (T->Format[t] == TILESPMV_FMT_HYB) acc += (int64_t)T->tilewidth[t] * rowlen;
-            }
-            part[(size_t)tid] += acc;
-        });
-        for (int64_t v : part) hybell += v;
-    }
     int *scans[] = { T->csr_offset, T->csrptr_offset, T->coo_offset, T->ell_offset, T->hyb_offset, T->dns_offset,
                      T->dnsrow_offset, T->dnscol_offset, T->dnsrowptr, T->dnscolptr, T->hyb_coocount,
-                     T->new_coocount, T->blknnz };
+                     T->new_coocount, T->blknnz, hyb_bytes };
     static const char *names[] = { "csr_offset", "csrptr_offset", "coo_offset", "ell_offset", "hyb_offset", "dns_offset",
                                    "dnsrow_offset", "dnscol_offset", "dnsrowptr", "dnscolptr", "hyb_coocount",
-                                   "new_coocount", "blknnz" };
+                                   "new_coocount", "blknnz", "hybIdx bytes" };
     exclusive_scan_checked_multi(scans, names, (int)(sizeof(scans) / sizeof(*scans)), (int64_t)np1);
     T->csrsize = T->csr_offset[tilenum]; T->csrptrlen = T->csrptr_offset[tilenum];
     T->coosize = T->coo_offset[tilenum]; T->ellsize = T->ell_offset[tilenum];
-    T->hybsize = T->hyb_offset[tilenum]; T->hybellsize = (int)hybell; T->hybcoosize = T->hyb_coocount[tilenum];
+    T->hybsize = T->hyb_offset[tilenum]; T->hybcoosize = T->hyb_coocount[tilenum]; T->hybellsize = T->hybsize - T->hybcoosize;   // (a HYB tile stores its ELL part + its remainder)
     T->dnssize = T->dns_offset[tilenum]; T->dnsrowsize = T->dnsrow_offset[tilenum];
     T->dnscolsize = T->dnscol_offset[tilenum]; T->coototal = T->new_coocount[tilenum];
 
     lap("scans");
     // ---- payload arrays
-    T->Blockcsr_Val = zalloc<val_t>(T->csrsize);
-    T->Blockcsr_Ptr = zalloc<unsigned char>(T->csrptrlen);
-    T->csr_compressedIdx = zalloc<unsigned char>(((size_t)T->csrsize + 1) / 2);
-    T->Blockcoo_Val = zalloc<val_t>(T->coosize);
-    T->coo_compressed_Idx = zalloc<unsigned char>(T->coosize);
-    T->Blockell_Val = zalloc<val_t>(T->ellsize);
-    T->ell_compressedIdx = zalloc<unsigned char>(((size_t)T->ellsize + 1) / 2);
-    T->Blockhyb_Val = zalloc<val_t>((size_t)T->hybellsize + T->hybcoosize);
-    T->hybIdx = zalloc<unsigned char>(((size_t)T->hybellsize + 1) / 2 + T->hybcoosize + (size_t)tilem + 8);
-    T->Blockdense_Val = zalloc<val_t>(T->dnssize);
-    T->Blockdenserow_Val = zalloc<val_t>(T->dnsrowsize);
-    T->denserowid = zalloc<char>(T->dnsrowptr[tilenum]);
-    T->Blockdensecol_Val = zalloc<val_t>(T->dnscolsize);
-    T->densecolid = zalloc<char>(T->dnscolptr[tilenum]);
-    T->deferredcoo_val = zalloc<val_t>(T->coototal);
-    T->deferredcoo_colidx = zalloc<int>(T->coototal);
-    T->deferredcoo_ptr = zalloc<int>((size_t)rowA + 1);
+    X.n_dnsrow = T->dnsrowptr[tilenum]; X.n_dnscol = T->dnscolptr[tilenum];
+    for_each_tile_field(*T, X, TF_PAYLOAD | TF_EXTRACTED, zalloc_tile_field);   // (zeroed: hybIdx's nibbles are OR-ed in)
 
-    uint8_t *csr_col = zalloc<uint8_t>(T->csrsize), *ell_col = zalloc<uint8_t>(T->ellsize);
-    uint8_t *hyb_col = zalloc<uint8_t>((size_t)T->hybellsize + T->hybcoosize), *hyb_row = zalloc<uint8_t>(T->hybcoosize);
+    uint8_t *csr_col = zalloc<uint8_t>(T->csrsize), *ell_col = zalloc<uint8_t>(T->ellsize);   // one byte per slot, packed into nibbles below
     int *x_row = zalloc<int>(T->coototal);  // extracted entries in tile order: local row | column | value
     int *x_col = zalloc<int>(T->coototal);
     val_t *x_val = zalloc<val_t>(T->coototal);
 
     lap("payload allocation");
-    // ---- pass 3: pack every tile into its format's arrays (src/csr2tile.h:420-622) and, per
+    // ---- pass 3: pack every tile into its format's arrays (tile_pack.h) and, per
     // tile-row, turn its slice of the extracted list into CSR rows (src/csr2tile.h:899-960).
+    const PackOut out = pack_out_of(*T, csr_col, ell_col);
     parallel_chunks(tilem, 128, [&](int64_t b, int64_t e, int) {
         for (int bi = (int)b; bi < (int)e; bi++) {
             const int rowlen = tile_rowlen(bi, tilem, rowA);
             for (int t = T->tile_ptr[bi]; t < T->tile_ptr[bi + 1]; t++) {
-                const int cb = T->tile_columnidx[t], collen = tile_collen(cb, tilen, colA);
-                const int e0 = T->tile_nnz[t], n = T->tile_nnz[t + 1] - e0, w = T->tilewidth[t];
-                const uint8_t *rc = lrc + e0; const int *src = ent + e0;
-                int start[BS + 1]; start[0] = 0;
-                for (int r = 0; r < BS; r++) start[r + 1] = start[r] + cnt_row[(size_t)t * BS + r];
-                switch (T->Format[t]) {
-                case TILESPMV_FMT_CSR: {
-                    const int off = T->csr_offset[t], poff = T->csrptr_offset[t];
-                    for (int k = 0; k < n; k++) { T->Blockcsr_Val[off + k] = vals[src[k]]; csr_col[off + k] = rc[k] & 15; }
-                    for (int r = 0; r < rowlen; r++) T->Blockcsr_Ptr[poff + r] = (unsigned char)start[r];
-                    break;
-                }
-                case TILESPMV_FMT_COO: {
-                    const int off = T->coo_offset[t], xo = T->new_coocount[t];
-                    for (int k = 0; k < n; k++) {
-                        T->Blockcoo_Val[off + k] = vals[src[k]];
-                        T->coo_compressed_Idx[off + k] = rc[k];
-                        x_row[xo + k] = rc[k] >> 4; x_col[xo + k] = colidx[src[k]]; x_val[xo + k] = vals[src[k]];
-                    }
-                    break;
-                }
-                case TILESPMV_FMT_ELL: {
-                    const int off = T->ell_offset[t];
-                    for (int k = 0; k < n; k++) {
-                        int r = rc[k] >> 4, p = off + (k - start[r]) * rowlen + r;
-                        T->Blockell_Val[p] = vals[src[k]]; ell_col[p] = rc[k] & 15;
-                    }
-                    break;
-                }
-                case TILESPMV_FMT_HYB: {
-                    const int off = T->hyb_offset[t], xo = T->new_coocount[t], ro = T->hyb_coocount[t];
-                    int spill = 0;
-                    for (int k = 0; k < n; k++) {
-                        int r = rc[k] >> 4, s = k - start[r];
-                        if (s < w) { T->Blockhyb_Val[off + s * rowlen + r] = vals[src[k]]; hyb_col[off + s * rowlen + r] = rc[k] & 15; }
-                        else {
-                            T->Blockhyb_Val[off + w * rowlen + spill] = vals[src[k]]; hyb_col[off + w * rowlen + spill] = rc[k] & 15;
-                            hyb_row[ro + spill] = (uint8_t)r;
-                            x_row[xo + spill] = r; x_col[xo + spill] = colidx[src[k]]; x_val[xo + spill] = vals[src[k]];
-                            spill++;
-                        }
-                    }
-                    break;
-                }
-                case TILESPMV_FMT_DNS: {
-                    const int off = T->dns_offset[t];
-                    for (int k = 0; k < n; k++) T->Blockdense_Val[off + (rc[k] & 15) * rowlen + (rc[k] >> 4)] = vals[src[k]];
-                    break;
-                }
-                case TILESPMV_FMT_DNSROW: {
-                    const int off = T->dnsrow_offset[t], ro = T->dnsrowptr[t];
-                    int nr = 0;
-                    for (int r = 0; r < rowlen; r++) {
-                        if (start[r + 1] - start[r] != collen) continue;
-                        T->denserowid[ro + nr++] = (char)r;
-                        for (int k = start[r]; k < start[r + 1]; k++) T->Blockdenserow_Val[off + k] = vals[src[k]];
-                    }
-                    break;
-                }
-                case TILESPMV_FMT_DNSCOL: {
-                    const int off = T->dnscol_offset[t], co = T->dnscolptr[t];
-                    for (int k = start[0]; k < start[1]; k++) T->densecolid[co + k] = (char)(rc[k] & 15);
-                    for (int k = 0; k < n; k++) { int r = rc[k] >> 4; T->Blockdensecol_Val[off + (k - start[r]) * rowlen + r] = vals[src[k]]; }
-                    break;
-                }
-                }
+                const uint8_t *rc = lrc + T->tile_nnz[t]; const int *src = ent + T->tile_nnz[t];
+                pack_tile(*T, t, rowlen, hyb_bytes[t], [rc](int k) { return (int)rc[k]; }, [src, vals](int k) { return vals[src[k]]; },
+                          [&](int slot, int r, int k) { x_row[slot] = r; x_col[slot] = colidx[src[k]]; x_val[slot] = vals[src[k]]; }, out);
             }
             // extracted entries of this tile-row -> per-row counts (rows of other tile-rows never appear here)
             const int x0 = T->new_coocount[T->tile_ptr[bi]], x1 = T->new_coocount[T->tile_ptr[bi + 1]];
@@ -328,23 +227,8 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
     // ---- index compression (src/csr2tile.h:973-1008; nibble layout src/encode.h:29-50)
     pack_nibble_stream(csr_col, T->csr_compressedIdx, T->csrsize);
     pack_nibble_stream(ell_col, T->ell_compressedIdx, T->ellsize);
-    if (T->hybsize > 0) {
-        int64_t src = 0, dst = 0, seen = 0;
-        for (int bi = 0; bi < tilem; bi++) {
-            const int rowlen = tile_rowlen(bi, tilem, rowA);
-            for (int t = T->tile_ptr[bi]; t < T->tile_ptr[bi + 1]; t++) {
-                if (T->Format[t] != TILESPMV_FMT_HYB) continue;
-                const int nell = T->tilewidth[t] * rowlen, ncoo = T->blknnz[t + 1] - T->blknnz[t] - nell;
-                for (int p = 0; p < nell; p += 2)
-                    T->hybIdx[dst + (p >> 1)] = (uint8_t)((hyb_col[src + p] << 4) + (p + 1 < nell ? hyb_col[src + p + 1] : 0));
-                dst += (nell + 1) / 2;
-                for (int i = 0; i < ncoo; i++) T->hybIdx[dst + i] = (uint8_t)((hyb_row[seen + i] << 4) + hyb_col[src + nell + i]);
-                seen += ncoo; src += nell + ncoo; dst += ncoo;
-            }
-        }
-    }
     lap("pass 3 (packing, extraction, nibble streams)");
-    free_later({csr_col, ell_col, hyb_col, hyb_row, x_row, x_col, x_val, cnt_row, ent, lrc});   // (0.5 GB for config 4: given back on a detached thread)
+    free_later({csr_col, ell_col, hyb_bytes, x_row, x_col, x_val, cnt_row, ent, lrc});   // (0.5 GB for config 4: given back on a detached thread)
     lap("frees");
 }
 
@@ -379,13 +263,7 @@ void Tile_create(Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA, MAT
 
 void Tile_destroy(Tile_matrix *T)
 {
-    void *all[] = { T->tile_ptr, T->tile_columnidx, T->tile_nnz, T->Format, T->blknnz, T->blknnznnz, T->dnsrowptr,
-        T->dnscolptr, T->tilewidth, T->csr_offset, T->csrptr_offset, T->coo_offset, T->ell_offset, T->hyb_offset,
-        T->hyb_coocount, T->dns_offset, T->dnsrow_offset, T->dnscol_offset, T->new_coocount, T->Blockcsr_Val,
-        T->Blockcsr_Ptr, T->csr_compressedIdx, T->Blockcoo_Val, T->coo_compressed_Idx, T->Blockell_Val,
-        T->ell_compressedIdx, T->Blockhyb_Val, T->hybIdx, T->Blockdense_Val, T->Blockdenserow_Val, T->denserowid,
-        T->Blockdensecol_Val, T->densecolid, T->deferredcoo_val, T->deferredcoo_colidx, T->deferredcoo_ptr };
-    for (void *p : all) free(p);
+    tilespmv::for_each_tile_field(*T, tilespmv::TileExtents(), tilespmv::TF_ALL, [](const tilespmv::TileField &f) { free(*f.ptr); });
     memset(T, 0, sizeof(*T));
 }
 
