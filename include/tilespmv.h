@@ -344,6 +344,13 @@ typedef struct {
                            that tile's padding slots — the unit's 16-column window of x is shifted by -3 .. 3 columns — instead of going to the strip's entry list; and a
                            unit whose columns are the previous unit's moved one to the right (consecutive diagonals of a band tile) takes that unit's x one lane up
                            instead of gathering.  unset / 1 = both, where they apply (classic unit plans); 2 = absorbed entries only; 0 = neither                                                    TILESPMV_ABSORB */
+    int value_narrow;   /* fp64 build: a plan whose unit values all survive double -> float -> double unchanged (finite, and ±0 or |v| >= FLT_MIN: constant-coefficient stencils,
+                           graph Laplacians, integer / pattern matrices, anything assembled in single precision) stores them as 4-byte floats, four units per 16-byte lane load;
+                           the kernels widen them in registers and the arithmetic stays fp64, so y keeps every bit.  Classic (non-pooled) unit plans of the stream kernel with
+                           entry mode 0 or 2 and 16 strips per workgroup, built without TILESPMV_CREATE_VALUE_MAP and without nt_stream = 0; a narrow plan always reads its
+                           streams nontemporally (nt_stream 1).  0 = never; 1 = wherever eligible and narrowable; unset = where the narrowed launch still moves more than the
+                           400 MB above which nt_stream is 1 by rule (smaller plans live in the caches and are bound by latency, not bytes).  Ignored by the fp32 build.
+                           TILESPMV_INFO_UNIT_VALUE_BYTES tells which form a plan has                                                      TILESPMV_VALUE_NARROW */
     int reserved[1];    /* must be TILESPMV_KNOB_DEFAULT or 0 */
 } tilespmv_plan_options;
 void tilespmv_plan_options_init(tilespmv_plan_options *opts);
@@ -398,7 +405,8 @@ int tilespmv_plan_create_from_device_csr(tilespmv_plan **plan, int rowA, int col
  * Contract: a plan created with the flag from values v1 and updated to v2 holds exactly the bytes a plan created with the flag from v2 holds (tilespmv_plan_stream_digests agree,
  * the facts agree, y agrees bit for bit where TILESPMV_INFO_ENTRY_ORDERED is 1).  To make that possible a flagged plan's layout follows the PATTERN alone: an explicit zero of
  * the CSR is a stored entry like any other (an unflagged plan treats an ELL slot that holds 0 at column nibble 0 as padding, and a packed entry record of value 0, offset 0 and
- * destination 0 as null).  On data without explicit zeros a flagged and an unflagged plan of the same matrix and options have identical SpMV streams.
+ * destination 0 as null).  On data without explicit zeros a flagged and an unflagged plan of the same matrix and options have identical SpMV streams — except
+ * where the unflagged plan stores its unit values as floats (value_narrow): a flagged plan never does, because its layout may not depend on the values.
  * The pattern is the caller's promise: a changed pattern cannot be detected.  Values must be finite, like every value a plan multiplies.
  * Returns a hipError_t value (0 = success, hipErrorInvalidValue for a NULL argument), or TILESPMV_ERR_NO_VALUE_MAP (-4) — plan untouched — for a plan created without the flag or
  * by tilespmv_plan_create (a host Tile_matrix has no link back to CSR order).  TILESPMV_INFO_VALUE_MAP_BYTES is the map's size. */
@@ -497,7 +505,7 @@ enum {
     TILESPMV_INFO_BRICK_ORDER = 19,       /* 1: the strips were regrouped into bricks of the grid (stencil-like shard) */
     TILESPMV_INFO_DESC_BYTES = 20,        /* bytes per unit descriptor in HBM: 12, or 4 (column-pattern dictionary); pooled plans 20, or 8 (pattern dictionary); wide pooled plans 28 */
     TILESPMV_INFO_NT_STREAM = 21,         /* 1: the unit kernel reads the value / entry-record streams with nontemporal loads */
-    TILESPMV_INFO_RETIRED_22 = 22,        /* always 0 (slab-paced entry phase, retired in round 6) */
+    TILESPMV_INFO_UNIT_VALUE_BYTES = 22,  /* bytes per stored unit value: 8, or 4 in a narrow plan (value_narrow); the fp32 build always reports 4 */
     TILESPMV_INFO_RETIRED_23 = 23,        /* always 0 */
     TILESPMV_INFO_PLACEMENT_TRIES = 24,   /* arena placements timed at plan creation (large plans; 0 / 1 = the first one was kept) */
     TILESPMV_INFO_RETIRED_25 = 25,        /* always 0 */

@@ -528,11 +528,15 @@ extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
 // nibble); there is no register accumulator, no end-of-row handling and no "rows without units": the slab is zeroed up front, entries and units add into it, y is stored from it.
 // The row nibbles travel like the descriptors (8 bytes per unit, one coalesced lane load per chunk of 16 units, parked in LDS: + 2 KB per workgroup -> 7 workgroups per CU).
 // WIDE (with POOL; hip_plan.h "wide pooled units", csr_form 3): windows of 256 columns — a slot's column offset is a byte (16 bytes per unit in S.ucol, parked in s_c), the descriptor's nibble words hold the ROW nibbles.
-template <int UB, int ECOO, int GPB, bool CD, bool NTS, bool POOL = false, bool WIDE = false>
+// NARROW (fp64 build; DevStream::uval_narrow): the plan's unit values are floats in groups of 4 units — one 16-byte lane load per batch instead of two —, widened in registers;
+// the arithmetic is the wide kernel's.  Classic plans, entry mode 0 / 2, 16 strips per workgroup, nontemporal streams.
+template <int UB, int ECOO, int GPB, bool CD, bool NTS, bool POOL = false, bool WIDE = false, bool NARROW = false>
 __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_ECOO2_MIN_WAVES : ECOO2_MIN_WAVES) : POOL ? (WIDE ? 6 : POOL_MIN_WAVES) : UNITS_MIN_WAVES) void k_units(DevStream S, int rowA, int colA, int xcd_chunk, val_t *__restrict__ partial,
                                                const val_t *__restrict__ x, val_t *__restrict__ y)
 {
-    static_assert(DCHUNK % UB == 0 && UB % UNIT_GROUP == 0, "a batch never straddles a descriptor chunk and is whole value groups");
+    static_assert(!NARROW || (sizeof(val_t) == 8 && !POOL && ECOO != 1 && GPB == 16 && NTS), "narrow values: fp64 classic plans, entry mode 0 / 2, 16 strips, nontemporal streams");
+    constexpr int G = NARROW ? UNIT_GROUP_NARROW : UNIT_GROUP;   // units whose values share one 16-byte lane load
+    static_assert(DCHUNK % UB == 0 && UB % G == 0, "a batch never straddles a descriptor chunk and is whole value groups");
     static_assert(GPB == 16 || (GPB == 32 && ECOO == 2) || (GPB == 8 && ECOO != 2 && !NTS), "512-thread workgroups exist for the workgroup entry mode only, 128-thread ones for small grids without it");
     static_assert(!(NTS && ECOO == 1), "nontemporal streams: large plans only (entry mode 1 = small grids)");
     static_assert(!POOL || GPB == 16 || GPB == 8, "pooled plans: 256-thread workgroups (128 on small grids)");
@@ -589,11 +593,11 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
     // values are stored in groups of G = UNIT_GROUP units of one task (hip_plan.hip): row r of the group that starts at
     // task-relative unit j (a multiple of G) sits at uval[(unit_begin + j) * 16 + G r .. + G - 1]; a batch of UB units
     // is UB / G sixteen-byte loads per lane
-    constexpr int G = UNIT_GROUP;
-    typedef val_t grp_t __attribute__((ext_vector_type(UNIT_GROUP)));
+    typedef std::conditional_t<NARROW, float, val_t> sval_t;   // a value as the plan stores it
+    typedef sval_t grp_t __attribute__((ext_vector_type(G)));
     const grp_t *__restrict__ ugrp = reinterpret_cast<const grp_t *>(S.uval) + r;
     const int last = unit_end - 1;
-    const int last_grp = unit_begin + (unit_end - 1 - unit_begin) / UNIT_GROUP * UNIT_GROUP;  // first unit of the task's last group
+    const int last_grp = unit_begin + (unit_end - 1 - unit_begin) / G * G;  // first unit of the task's last group
     const bool have_units = unit_begin < unit_end;
     const long long xlast = (long long)colA - 1;  // row units of a partial last column block: zero payload, clamped x index
     const int ncoo = coo_end - coo_begin;
@@ -849,7 +853,7 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
                 } else dnext = load_udesc_raw(S.udesc, min(chunk_end + r, last));
             }
             if (!(ECOO == 1 && u == unit_begin)) fetch_batch(u - (chunk_end - DCHUNK));
-            val_t vn[UB];
+            sval_t vn[UB];   // (narrow plans: the prefetched batch waits as floats and is widened when it becomes `v`)
 #pragma unroll
             for (int k = 0; k < UB; k += G) {  // unconditional (clamped to the task's last group): exact vmcnt
                 const grp_t pv = stream_load<NT>(ugrp + (long long)min(u + UB + k, last_grp) * (16 / G));
@@ -1297,11 +1301,27 @@ __global__ __launch_bounds__(256, MV_MIN_WAVES) void k_units_mv(DevStream S, int
     lacc_t (*s_e)[NV] = reinterpret_cast<lacc_t (*)[NV]>(s_dyn) + (size_t)g * slab_rows * 16;
     typedef val_t grp_t __attribute__((ext_vector_type(UNIT_GROUP)));
     const grp_t *__restrict__ ugrp = reinterpret_cast<const grp_t *>(S.uval) + r;  // group layout (hip_plan.hip): one 16-byte load = UNIT_GROUP units
+#if !defined(TILESPMV_F32)
+    // narrow plans (DevStream::uval_narrow, a wavefront-uniform branch): the values are floats in groups of 4 units; a batch of 2 units is the 8-byte half `(u - unit_begin) / 2 & 1` of
+    // row r's 16 bytes of the group it falls into (tasks are padded to whole groups of 4, so the clamped last pair exists)
+    const bool narrow = S.uval_narrow != 0;
+    typedef float pair_t __attribute__((ext_vector_type(2)));
+    const pair_t *__restrict__ upair = reinterpret_cast<const pair_t *>(S.uval) + 2 * r;
+    static_assert(UNIT_GROUP * MV_UBX == 2, "the narrow value load of k_units_mv is written for batches of 2 units");
+#endif
     const vec_t *__restrict__ Xv = reinterpret_cast<const vec_t *>(X) + q;   // row i, slice q: Xv[i * Q]
     vec_t *__restrict__ Yv = reinterpret_cast<vec_t *>(Y) + q;
     const int last = unit_end - 1;
     const int last_grp = unit_begin + (unit_end - 1 - unit_begin) / UNIT_GROUP * UNIT_GROUP;
     auto load_grp = [&](int u, val_t (&out)[UB]) {
+#if !defined(TILESPMV_F32)
+        if (narrow) {
+            const int rel = min(u, last_grp) - unit_begin;   // (last_grp: the task's last pair)
+            const pair_t pv = stream_load<NTS>(upair + (long long)(unit_begin + (rel & ~3)) * 8 + ((rel >> 1) & 1));
+            out[0] = pv[0]; out[1] = pv[1];
+            return;
+        }
+#endif
 #pragma unroll
         for (int gk = 0; gk < UB; gk += UNIT_GROUP) {
             const grp_t pv = stream_load<NTS>(ugrp + (long long)min(u + gk, last_grp) * (16 / UNIT_GROUP));
@@ -1947,22 +1967,26 @@ hipError_t launch_columns_to_rows(const val_t *YT, int nvec, long long row0, lon
 // over the plan's largest array (0.67 GB for config 4) into a staging copy; here the emitted values are uploaded as they are and one workgroup per task writes them to their final
 // place.  map[i] = {first unit of task i in src, first unit in dst, units, -}.  Padding slots of a task's last group are never written: the arena block they lie in was zeroed.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pair_values(const val_t *__restrict__ src, val_t *__restrict__ dst, const int4 *__restrict__ map, int ntasks)
+// narrow (fp64 plans whose values are all floats, DevStream::uval_narrow): dst holds floats in groups of UNIT_GROUP_NARROW units
+__global__ __launch_bounds__(256) void k_pair_values(const val_t *__restrict__ src, val_t *__restrict__ dst, const int4 *__restrict__ map, int ntasks, int narrow)
 {
-    constexpr int G = UNIT_GROUP;
+    const int G = narrow ? UNIT_GROUP_NARROW : UNIT_GROUP;
+    float *__restrict__ dstn = reinterpret_cast<float *>(dst);
     for (int t = blockIdx.x; t < ntasks; t += gridDim.x) {
         const int4 m = map[t];
         const long long so = (long long)m.x * 16, dofs = (long long)m.y * 16;
         for (int i = threadIdx.x; i < m.z * 16; i += 256) {
             const int j = i >> 4, r = i & 15;
-            dst[dofs + (long long)(j / G * G) * 16 + G * r + (j % G)] = src[so + i];
+            const long long at = dofs + (long long)(j / G * G) * 16 + G * r + (j % G);
+            if (narrow) dstn[at] = (float)src[so + i];
+            else dst[at] = src[so + i];
         }
     }
 }
 
-hipError_t launch_pair_values(const val_t *src, val_t *dst, const int4 *map, int ntasks)
+hipError_t launch_pair_values(const val_t *src, val_t *dst, const int4 *map, int ntasks, bool narrow)
 {
-    if (ntasks > 0) hipLaunchKernelGGL(k_pair_values, dim3((unsigned)std::min(ntasks, 1 << 20)), dim3(256), 0, nullptr, src, dst, map, ntasks);
+    if (ntasks > 0) hipLaunchKernelGGL(k_pair_values, dim3((unsigned)std::min(ntasks, 1 << 20)), dim3(256), 0, nullptr, src, dst, map, ntasks, narrow ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -1972,6 +1996,7 @@ hipError_t launch_tiles_stream(const DevPlan &P, const DevStream &S, const DevDe
     if (S.ntasks > 0) {
         const int xc = xcd_remap == 2 ? xcd_chunk : 0;   // workgroup -> XCD windows: a kernel argument (0 = dispatch order)
         // k_units<UB, entry mode, strips per workgroup, dictionary descriptors, nontemporal streams, pooled, wide>
+#define TSPMV_KN(W, CD) hipLaunchKernelGGL((k_units<TILESPMV_UB, W, 16, CD, true, false, false, true>), dim3((unsigned)((S.ntasks + 15) / 16)), dim3(256), (size_t)lds_pad_bytes, st, S, P.rowA, P.colA, xc, P.partial, x, y)
 #define TSPMV_K(W, B, CD, NTS, PL, WD) hipLaunchKernelGGL((k_units<TILESPMV_UB, W, B, CD, NTS, PL, WD>), dim3((unsigned)((S.ntasks + B - 1) / B)), dim3(16 * B), (size_t)lds_pad_bytes, st, S, P.rowA, P.colA, xc, P.partial, x, y)
 #define TSPMV_NTS(W, B, CD, PL, WD) do { if (S.nt_stream) TSPMV_K(W, B, CD, true, PL, WD); else TSPMV_K(W, B, CD, false, PL, WD); } while (0)
         // the descriptor form of the plan: classic 12-B / dictionary; pooled 20-B / pooled dictionary / wide
@@ -1984,6 +2009,13 @@ hipError_t launch_tiles_stream(const DevPlan &P, const DevStream &S, const DevDe
         // Grids that would give fewer than half the CUs a 256-thread workgroup run 128-thread workgroups of 8 strips instead: twice the workgroups, the same strips
         // (per-strip and per-wavefront entry modes only: the workgroup mode merges the lists of its 16 strips at plan creation)
         const bool small_grid = entry_mode != 2 && !S.nt_stream && (S.ntasks + 15) / 16 < SMALL_GRID_WORKGROUPS;
+#if !defined(TILESPMV_F32)
+        if (S.uval_narrow) {   // narrow values: four forms (entry mode 0 / 2 x 12-B / dictionary descriptors); the builder narrows no other plan
+            if (S.pooled || !S.nt_stream || entry_mode == 1 || wg_strips != 16) return hipErrorInvalidValue;
+            if (entry_mode == 2) { if (S.cb_bits > 0) TSPMV_KN(2, true); else TSPMV_KN(2, false); }
+            else { if (S.cb_bits > 0) TSPMV_KN(0, true); else TSPMV_KN(0, false); }
+        } else
+#endif
         if (small_grid) { if (entry_mode == 1) TSPMV_FORM_SMALL(1, 8); else TSPMV_FORM_SMALL(0, 8); }
         else if (entry_mode == 1) TSPMV_FORM_SMALL(1, 16);                                    // (entry mode 1 = small grids: never nontemporal)
         else if (entry_mode == 2 && wg_strips == 32 && !S.pooled) {                          // 512-thread workgroups: classic / dictionary descriptors only
@@ -1997,6 +2029,7 @@ hipError_t launch_tiles_stream(const DevPlan &P, const DevStream &S, const DevDe
 #undef TSPMV_FORM_
 #undef TSPMV_NTS
 #undef TSPMV_K
+#undef TSPMV_KN
     }
     // whole-tile passes (y += ...): CSR tiles kept as tiles, dense tiles on the matrix cores; then the split-row fix-up
     hipError_t e = launch_tiles_direct(P, dense_mfma, /*accumulate=*/true, /*fixup=*/false, x, y, st);

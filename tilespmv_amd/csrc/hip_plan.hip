@@ -66,6 +66,7 @@ static Knobs resolve_knobs(const tilespmv_plan_options *opts)
     k.x_panel_merge = pick(o.x_panel_merge, "TILESPMV_X_PANEL_MERGE", -1);
     k.x_slice_passes = pick(o.x_slice_passes, "TILESPMV_X_SLICE_PASSES", -1);
     k.absorb = pick(o.absorb, "TILESPMV_ABSORB", -1); if (k.absorb < 0 || k.absorb > 2) k.absorb = 1;
+    k.value_narrow = pick(o.value_narrow, "TILESPMV_VALUE_NARROW", -1);
     k.deterministic = pick(o.deterministic, "TILESPMV_DETERMINISTIC", 0) > 0 ? 1 : 0;
     if (k.deterministic) {   // no stopwatch, no unordered sum: whatever the caller left unset among the timed choices is switched off
         if (k.placement_tries < 0) k.placement_tries = 1;
@@ -257,7 +258,7 @@ const char *tilespmv_plan_options_layout(void)
         TSPMV_F(entry_mode) TSPMV_F(entry_ordered) TSPMV_F(strip_cost) TSPMV_F(split_above) TSPMV_F(split_cap) TSPMV_F(xcd_remap) TSPMV_F(xcd_chunk)
         TSPMV_F(csr_split) TSPMV_F(fix_inline) TSPMV_F(coo_cost) TSPMV_F(coo_heavy_min) TSPMV_F(coo_piece) TSPMV_F(strip_even) TSPMV_F(wg_strips)
         TSPMV_F(x_window) TSPMV_F(x_stride1) TSPMV_F(x_stride2) TSPMV_F(mv_native) TSPMV_F(mv_xcd_chunk) TSPMV_F(lds_pad) TSPMV_F(y_store)
-        TSPMV_F(desc_dict) TSPMV_F(nt_stream) TSPMV_F(x_panel_kb) TSPMV_F(x_panel_merge) TSPMV_F(placement_tries) TSPMV_F(x_slice_passes) TSPMV_F(deterministic) TSPMV_F(absorb) TSPMV_F(reserved)
+        TSPMV_F(desc_dict) TSPMV_F(nt_stream) TSPMV_F(x_panel_kb) TSPMV_F(x_panel_merge) TSPMV_F(placement_tries) TSPMV_F(x_slice_passes) TSPMV_F(deterministic) TSPMV_F(absorb) TSPMV_F(value_narrow) TSPMV_F(reserved)
 #undef TSPMV_F
         return o;
     }();
@@ -407,7 +408,7 @@ static int plan_create_tuned(tilespmv_plan **out, const Tile_matrix *T, int rowA
     // cache policy of the once-read streams: the size rule (nontemporal above 400 MB per launch) switches somewhere between 340 and 500 MB; a measured selection
     // just times both (the kernels differ by a template flag only: nothing is rebuilt).  Entry mode 1 and x-window plans have no nontemporal form.
     log += "], \"stream_policy\": [";
-    if (best && best->kernel == TILESPMV_KERNEL_STREAM && K0.nt_stream < 0 && best->entry_mode != 1) {
+    if (best && best->kernel == TILESPMV_KERNEL_STREAM && K0.nt_stream < 0 && best->entry_mode != 1 && !best->st.uval_narrow) {   // (a narrow plan has the nontemporal form only)
         const int rule = best->st.nt_stream;
         double ms2[2] = {0, 0};
         for (int k = 0; k < 2; k++) {
@@ -792,6 +793,7 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
     I[TILESPMV_INFO_COO_MODE] = coo_mode; I[TILESPMV_INFO_DENSE_MODE] = dense_mode; I[TILESPMV_INFO_KERNEL] = plan->kernel;
     I[TILESPMV_INFO_NUM_TASKS] = n_tasks; I[TILESPMV_INFO_NUM_SPLIT_ROWS] = (long long)fix.size();
     I[TILESPMV_INFO_FALLBACK_NNZ] = f_nnz;
+    I[TILESPMV_INFO_UNIT_VALUE_BYTES] = plan->st.uval_narrow ? 4 : sv;
     if (plan->kernel != TILESPMV_KERNEL_STREAM) { I[TILESPMV_INFO_ENTRY_ORDERED] = 1; I[TILESPMV_INFO_STRIP_COST] = target; }
     I[TILESPMV_INFO_BUILD_US] = (long long)(now_us() - t_create0) - I[TILESPMV_INFO_UPLOAD_US];
     // bytes one SpMV has to move at least: the three streams + tasks + x once + y once (+ fallback)
@@ -882,6 +884,7 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
     H.tile_ptr = h_tile_ptr.data(); H.tile_columnidx = h_tile_col.data(); H.Format = h_fmt.data();
     if (K.verbose) fprintf(stderr, "tilespmv: plan from CSR: device Tile_create %.1f ms (CSR upload included), tile list to the host %.1f ms\n", (t1 - t0) * 1e-3, (now_us() - t1) * 1e-3);
     Knobs Kd = K;
+    Kd.value_map = value_map;
     if (Kd.kernel == TILESPMV_KERNEL_AUTO) Kd.kernel = TILESPMV_KERNEL_STREAM;
     if (Kd.coo_mode == TILESPMV_COO_AUTO) Kd.coo_mode = TILESPMV_COO_IN_TILE;
     const double t2 = now_us();

@@ -626,6 +626,33 @@ int dev_pack_desc(const uint4 *d_udesc, const uint2 *d_urow, const uint4 *d_ucol
     return 0;
 }
 
+// every slot of EMIT's unit-value array narrowable (plan_tile_ops.h value_narrowable)?  counts the slots that are not
+#if !defined(TILESPMV_F32)
+__global__ __launch_bounds__(256) void k_pd_not_narrowable(const val_t *__restrict__ v, long long n, unsigned long long *__restrict__ bad)
+{
+    unsigned mine = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) mine += value_narrowable(v[i]) ? 0u : 1u;
+    if (mine) atomicAdd(bad, (unsigned long long)mine);
+}
+#endif
+int dev_all_narrowable(const val_t *d_uval, long long n, bool *all)
+{
+    *all = false;
+#if !defined(TILESPMV_F32)
+    if (n <= 0) { *all = true; return 0; }
+    Tmp<unsigned long long> bad;
+    PD_TRY(bad.alloc(1, true));
+    hipLaunchKernelGGL(k_pd_not_narrowable, dim3((unsigned)std::min<long long>(nblk(n, 256), 8192)), dim3(256), 0, 0, d_uval, n, bad.p);
+    PD_TRY(hipGetLastError());
+    unsigned long long h = 1;
+    PD_TRY(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
+    *all = h == 0;
+#else
+    (void)d_uval; (void)n;
+#endif
+    return 0;
+}
+
 int dev_shift_histogram(const UDesc *d_packed, long long NUP, unsigned long long hist[8])
 {
     for (int c = 0; c < 8; c++) hist[c] = 0;

@@ -132,6 +132,10 @@ struct StreamBuilder {
     // ENCODE / ENTRIES
     long long NUP = 0, n_rec = 0, n_chunk = 0, n_groups = 0, panel_rmw_rows = 0;
     bool pool_dict = false;   // pooled plan with 8-B descriptors + pattern dictionary
+    bool narrow = false;      // fp64: the unit values are stored as floats, 4 units per group (hip_plan.h DevStream::uval_narrow); decided at the start of ENCODE
+    long long value_bytes() const { return narrow ? 4 : sv; }   // bytes per stored unit value
+    long long value_group() const { return narrow ? UNIT_GROUP_NARROW : UNIT_GROUP; }
+    void choose_value_width();
     long long desc_bytes() const { return S.cb_bits > 0 ? 4 : wide ? 28 : pooled ? (pool_dict ? 8 : 20) : 12; }
     std::vector<long long> old_begin;
 
@@ -717,10 +721,42 @@ void StreamBuilder::order()
     if (hashing()) { Hash h; h.vec(tasks); h.num(brick); stage_done(TILESPMV_STAGE_ORDER, h); }
 }
 
+// Narrow unit values (include/tilespmv.h value_narrow; fp64 build): taken at the start of ENCODE, because the groups of 4 change the padded unit numbering everything
+// after it uses.  Eligible: classic units, entry mode 0 / 2 with 16 strips per workgroup (the forms k_units has a narrow instantiation of), no value map (a flagged plan's
+// layout follows the pattern alone), nontemporal streams not refused by the caller.  With the knob unset the narrowed launch must still move more than NT_STREAM_MIN_BYTES —
+// judged by a LOWER bound of FINISH's byte model (4-byte descriptors, one record per list entry, no whole-tile passes: what is known here), so that a plan narrowed by
+// rule is also nontemporal by FINISH's rule.  Narrowable: every slot of EMIT's value array passes value_narrowable — host loop or device reduction over the same array.
+void StreamBuilder::choose_value_width()
+{
+    narrow = false;
+    if (sizeof(val_t) != 8 || K.value_narrow == 0 || pooled || K.value_map || K.nt_stream == 0 || NU <= 0) return;
+    if (!(entry_mode == 0 || entry_mode == 2) || wg_strips != 16) return;
+    if (K.value_narrow < 0) {
+        long long nup4 = 0;
+        for (const STask &k : tasks) nup4 += (k.unit_end - k.unit_begin + UNIT_GROUP_NARROW - 1) / UNIT_GROUP_NARROW * UNIT_GROUP_NARROW;
+        const long long launch_min = nup4 * (4 + 16LL * 4) + NC * (entry_mode == 0 ? sv + 5LL : (long long)sizeof(ERec)) + (long long)tasks.size() * (long long)sizeof(STask) + ((long long)colA + 16LL * ntr) * sv;
+        if (launch_min <= NT_STREAM_MIN_BYTES) return;
+    }
+    const long long n = NU * 16;
+    if (DT) {
+        bool all = false;
+        if (dev_all_narrowable(d_uval, n, &all) != 0) { rc = -3; return; }
+        narrow = all;
+    } else {
+        std::atomic<int> bad(0);
+        parallel_chunks(n, 1 << 18, [&](int64_t b, int64_t e, int) {
+            if (bad.load(std::memory_order_relaxed)) return;
+            for (int64_t i = b; i < e; i++) if (!value_narrowable((double)h_uval[i])) { bad.store(1); return; }
+        });
+        narrow = bad.load() == 0;
+    }
+    if (K.verbose) fprintf(stderr, "tilespmv: unit values: %s\n", narrow ? "every one is a float: stored in 4 bytes" : "8 bytes (not all of them survive double -> float -> double)");
+}
+
 // ENCODE in device mode: the same final forms, produced from EMIT's device scratch (hip_plan_device.h)
 void StreamBuilder::encode_device()
 {
-    constexpr long long G = UNIT_GROUP;
+    const long long G = value_group();
     auto padded = [&](long long n) { return (n + G - 1) / G * G; };
     std::vector<int4> pair_map(tasks.size());
     old_begin.assign(tasks.size(), 0);
@@ -794,9 +830,10 @@ void StreamBuilder::encode_device()
     plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
     if (rc == 0 && !pooled) { unsigned long long hist[8]; if (dev_shift_histogram(d_packed, NUP, hist) != 0) rc = -3; else plan->info[TILESPMV_INFO_DERIVED_UNITS] = (long long)hist[UNIT_DERIVED_CODE]; }
     // the value pass (as in host mode: k_pair_values), its source already on the device
-    rc |= plan->reserve((size_t)NUP * 16, &S.uval);
+    if (narrow) rc |= plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
+    else rc |= plan->reserve((size_t)NUP * 16, &S.uval);
     if (rc == 0) {
-        e = launch_pair_values(d_uval, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size());
+        e = launch_pair_values(d_uval, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size(), narrow);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) fail("value pass", e);
     }
@@ -814,7 +851,11 @@ void StreamBuilder::encode()
     // the G units interleaved per row, so that a lane fetches G units with one 16-byte load (row r of the group at
     // +16 r bytes).  A task whose unit count is not a multiple of G gets padding units (zero values, never executed:
     // unit_end excludes them) so that its last group exists.
-    constexpr long long G = UNIT_GROUP;
+    // Narrow plans (fp64, choose_value_width): the values are floats and G = 4, the fp32 build's layout.
+    choose_value_width();
+    if (rc) return;
+    S.uval_narrow = narrow ? 1 : 0;
+    const long long G = value_group();
     auto padded = [&](long long n) { return (n + G - 1) / G * G; };
     NUP = 0;
     for (const STask &k : tasks) NUP += padded(k.unit_end - k.unit_begin);
@@ -832,7 +873,8 @@ void StreamBuilder::encode()
         // the host pass — which stays as the checker: TILESPMV_ENCODE_CHECK=1 runs both and compares the device's stream with the host's, byte for byte (tests/test_gpu_parity.py)
         const bool encode_check = !plan->dry && K.encode_check;
         const bool on_device = !plan->dry && NUP > 0 && !K.encode_on_host;
-        val_t *paired = (on_device && !encode_check) ? nullptr : zalloc<val_t>((size_t)NUP * 16);
+        val_t *paired = (on_device && !encode_check) || narrow ? nullptr : zalloc<val_t>((size_t)NUP * 16);
+        float *paired_n = (on_device && !encode_check) || !narrow ? nullptr : zalloc<float>((size_t)NUP * 16);   // narrow plans: the same groups, of floats
         std::vector<int4> pair_map(on_device ? tasks.size() : 0);
         std::vector<long long> new_begin(tasks.size());
         old_begin.assign(tasks.size(), 0);
@@ -852,6 +894,11 @@ void StreamBuilder::encode()
                         const val_t *src = h_uval + (ub + j) * 16;
                         val_t *dst = paired + (nb + j / G * G) * 16 + (j % G);
                         for (int r = 0; r < 16; r++) dst[G * r] = src[r];
+                    }
+                    if (paired_n) {
+                        const val_t *src = h_uval + (ub + j) * 16;
+                        float *dst = paired_n + (nb + j / G * G) * 16 + (j % G);
+                        for (int r = 0; r < 16; r++) dst[G * r] = (float)src[r];
                     }
                 }
                 if (on_device) pair_map[(size_t)i] = make_int4((int)ub, (int)nb, (int)n, 0);
@@ -982,25 +1029,27 @@ void StreamBuilder::encode()
             const double t0 = now_us();
             void *d_src = nullptr, *d_map = nullptr;
             const size_t src_b = (size_t)NU * 16 * sizeof(val_t), map_b = pair_map.size() * sizeof(int4);
-            rc |= plan->reserve((size_t)NUP * 16, &S.uval);
+            if (narrow) rc |= plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
+            else rc |= plan->reserve((size_t)NUP * 16, &S.uval);
             hipError_t e = hipMalloc(&d_src, std::max<size_t>(src_b, 16));
             if (e == hipSuccess) e = hipMalloc(&d_map, std::max<size_t>(map_b, 16));
             if (e == hipSuccess) e = hipMemcpy(d_src, h_uval, src_b, hipMemcpyHostToDevice);
             if (e == hipSuccess) e = hipMemcpy(d_map, pair_map.data(), map_b, hipMemcpyHostToDevice);
-            if (e == hipSuccess && rc == 0) e = launch_pair_values((const val_t *)d_src, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size());
+            if (e == hipSuccess && rc == 0) e = launch_pair_values((const val_t *)d_src, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size(), narrow);
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e == hipSuccess && encode_check) {
-                std::vector<val_t> back((size_t)NUP * 16);
-                e = hipMemcpy(back.data(), S.uval, back.size() * sizeof(val_t), hipMemcpyDeviceToHost);
-                if (e == hipSuccess && memcmp(back.data(), paired, back.size() * sizeof(val_t)) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
+                std::vector<unsigned char> back((size_t)NUP * 16 * (size_t)value_bytes());
+                e = hipMemcpy(back.data(), S.uval, back.size(), hipMemcpyDeviceToHost);
+                if (e == hipSuccess && memcmp(back.data(), narrow ? (const void *)paired_n : (const void *)paired, back.size()) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
                 else if (e == hipSuccess && K.verbose) fprintf(stderr, "tilespmv: encode check: %lld units, device value stream == host value stream\n", NUP);
             }
             if (d_src) (void)hipFree(d_src);
             if (d_map) (void)hipFree(d_map);
             if (e != hipSuccess) { fprintf(stderr, "tilespmv: value pass on the device failed: %s\n", hipGetErrorString(e)); (void)hipGetLastError(); rc = -3; }
             plan->info[TILESPMV_INFO_UPLOAD_US] += (long long)(now_us() - t0);
-        } else rc |= plan->upload(paired, (size_t)NUP * 16, &S.uval);
-        free_later({paired, h_uval}, (size_t)NUP * 16 * sizeof(val_t));   // (h_uval was read for the last time above)
+        } else if (narrow) rc |= plan->upload(paired_n, (size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
+        else rc |= plan->upload(paired, (size_t)NUP * 16, &S.uval);
+        free_later({paired, paired_n, h_uval}, (size_t)NUP * 16 * sizeof(val_t));   // (h_uval was read for the last time above)
         h_uval = nullptr;
         S.udesc_cb = S.udesc;
     }
@@ -1176,7 +1225,7 @@ void StreamBuilder::finish(long long &n_tasks, long long &model_bytes)
     // 7-pt 256^3 0.2533 -> 0.2432, power-law 8 M 0.1078 -> 0.1043 — plain where it is a few per cent: there the streaming form buys nothing and makes the time
     // depend on where the CALLER's y happens to sit (nlpkkt160 stand-in fp64: 0.413 or 0.459 ms by the copy of y; plain: 0.408-0.411 with every copy)
     {
-        const long long stream_b = NU * (desc_bytes() + 16LL * sv) + NC * (sv + 4LL), y_b = 16LL * ntr * sv;
+        const long long stream_b = NU * (desc_bytes() + 16LL * value_bytes()) + NC * (sv + 4LL), y_b = 16LL * ntr * sv;
         S.y_streaming = K.y_store >= 0 ? (K.y_store != 0) : (y_b * 20 >= stream_b);   // >= 5 %
     }
     plan->info[TILESPMV_INFO_ENTRY_MODE] = entry_mode;
@@ -1192,7 +1241,7 @@ void StreamBuilder::finish(long long &n_tasks, long long &model_bytes)
     }
     plan->mv_by_columns = entry_dominated && target >= 800;   // (small strips hold few entries each: scircuit-like 18 / 22 / 32 us native against 22 / 41 / 78 us)
     n_tasks = (long long)tasks.size();
-    model_bytes = NUP * (desc_bytes() + 16LL * sv) + (entry_mode == 0 ? NC * (sv + 5LL) : n_rec * (long long)sizeof(ERec) + n_chunk * 4 + n_groups * 16) + NH * 8 + NHV * sv + NHI + n_tasks * (long long)sizeof(STask) +
+    model_bytes = NUP * (desc_bytes() + 16LL * value_bytes()) + (entry_mode == 0 ? NC * (sv + 5LL) : n_rec * (long long)sizeof(ERec) + n_chunk * 4 + n_groups * 16) + NH * 8 + NHV * sv + NHI + n_tasks * (long long)sizeof(STask) +
                   (long long)htasks.size() * ((long long)sizeof(Task) + 32LL * sv) +  // whole-tile passes re-read and re-write their rows of y
                   ND * (4 + 256LL * sv) + (long long)drows.size() * (16 + 32LL * sv);
     // The once-read streams (values, entry records) are loaded nontemporally when the launch moves clearly more than the Infinity Cache holds: they then do
@@ -1204,6 +1253,7 @@ void StreamBuilder::finish(long long &n_tasks, long long &model_bytes)
     {
         const long long launch_b = model_bytes + ((long long)colA + 16LL * ntr) * sv;
         S.nt_stream = (entry_mode != 1 && (K.nt_stream >= 0 ? K.nt_stream != 0 : launch_b > NT_STREAM_MIN_BYTES)) ? 1 : 0;
+        if (narrow) S.nt_stream = 1;   // (the narrow kernels exist in the nontemporal form only; by rule they are chosen above the same size)
     }
     plan->info[TILESPMV_INFO_NT_STREAM] = S.nt_stream;
     if (hashing()) {

@@ -10,6 +10,21 @@ namespace tilespmv {
 
 TILESPMV_HD inline int nib_at(const unsigned char *s, long long p) { return (p & 1) ? (s[p >> 1] & 15) : (s[p >> 1] >> 4); }
 
+// Narrow unit values (fp64 build, DevStream::uval_narrow): a value may be stored as a float iff it is finite, comes back from double -> float -> double with the same
+// bits, and is +-0 or at least FLT_MIN in magnitude (so that neither the conversion at plan creation nor the widening in the kernels depends on the fp32 denormal mode).
+// A plan is narrowable iff EVERY slot of its emitted unit-value array is (padding zeros included); the host builder asks this in a loop, the device builder in a reduction
+// kernel, both of the same array.
+TILESPMV_HD inline bool value_narrowable(double v)
+{
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    const unsigned ex = (unsigned)(b >> 52) & 0x7FFu;
+    if (ex == 0x7FFu) return false;                               // infinity, NaN
+    if ((b << 1) == 0) return true;                               // +-0
+    if (ex < 1023u - 126u || ex > 1023u + 127u) return false;     // below FLT_MIN (fp32 denormals included) / above FLT_MAX
+    return (b & ((1ull << 29) - 1ull)) == 0;                      // the 29 mantissa bits a float does not have
+}
+
 // A CSR tile is executed as w ELL-style units (the first w entries of every row) plus the rest of its entries on the strip's COO list; w minimises the bytes moved
 // (HYB's idea, src/csr2tile.h:279-306, with this kernel's byte costs).  Returns w and the number of remainder entries.
 TILESPMV_HD inline int csr_split_width(const unsigned char *ptr, int rowlen, int nnz, int *remainder)
