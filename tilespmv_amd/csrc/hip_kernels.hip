@@ -335,6 +335,10 @@ __device__ __forceinline__ X unit_x_use(X gathered, X prev, unsigned w0, int r)
 }
 // first column of a classic unit's window of x: column block * 16, moved by the signed shift of a unit that took list entries (hip_plan.h UNIT_SHIFT_SHIFT)
 __device__ __forceinline__ long long unit_x_base(unsigned w0) { return (long long)(w0 & 0xFFFFFFu) * 16 + ((int)w0 >> UNIT_SHIFT_SHIFT); }
+// ... the same in 32 bits (24 bits of column block * 16 + a shift of -4 .. 3: below 2^28 + 3), and the clamped index of a gather: a window offset below 256 on top of a base below
+// 2^28.  The plan's nibbles and offsets never point in front of column 0 (plan_tile_ops.h: a window starts at its lowest used column), so the index is an unsigned number.
+__device__ __forceinline__ int unit_x_base32(unsigned w0) { return (int)((w0 & 0xFFFFFFu) << 4) + ((int)w0 >> UNIT_SHIFT_SHIFT); }
+__device__ __forceinline__ unsigned x_index32(int base, unsigned off, int xlast) { return (unsigned)min(base + (int)off, xlast); }
 
 // Descriptor word layout in LDS (16 B per unit, two identical-purpose halves so that a lane reads 8 B; HBM holds the
 // 12-B form without the duplicate word, UDesc):
@@ -366,6 +370,12 @@ typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
 #endif
 #ifndef UNITS_MIN_WAVES
 #define UNITS_MIN_WAVES 8  // waves per SIMD asked of the register allocator (64 VGPRs)
+#endif
+#ifndef UNIT_X32
+#define UNIT_X32 1   // x index of a unit's gather in 32 bits (column block * 16 + shift + nibble < 2^28 + 19, colA is an int): one signed min, one 64-bit scale-and-add (0: 64-bit base, add, compare and two selects).  405 -> 373 instructions per batch in the hot narrow kernel; config 4 0.1190 -> 0.1182 ms: profiles/unit_loop_pipeline_ab.txt
+#endif
+#ifndef UNIT_TAIL_HOT
+#define UNIT_TAIL_HOT 1   // the value prefetch of a task's last iteration (there is no next batch; the load stays for the exact vmcnt) reads the plan's first 16 bytes — one word, the same for every lane of every task — instead of the task's last group once more (0), a second trip to memory for 256 B per strip of a stream that is not kept in the caches.  With UNIT_X32: config 4 0.1169 -> 0.1133 / 0.1153 ms, KKT fp32 -5.5 %: profiles/unit_loop_pipeline_ab.txt
 #endif
 #ifndef POOL_ECOO2_MIN_WAVES
 #define POOL_ECOO2_MIN_WAVES 5   // pooled plans, workgroup entry mode: 96 VGPRs (at 6 waves = 80 VGPRs the kernel spills 12 bytes)
@@ -600,6 +610,7 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
     const int last_grp = unit_begin + (unit_end - 1 - unit_begin) / G * G;  // first unit of the task's last group
     const bool have_units = unit_begin < unit_end;
     const long long xlast = (long long)colA - 1;  // row units of a partial last column block: zero payload, clamped x index
+    const int xlast32 = colA - 1;
     const int ncoo = coo_end - coo_begin;
     uint4 dcur = make_uint4(0u, 0u, 0u, 0u), dnext = dcur;
     uint2 rcur = make_uint2(0u, 0u), rnext = rcur;   // POOL: row nibbles of the chunks in dcur / dnext
@@ -664,14 +675,20 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
 #pragma unroll
             for (int k = 0; k < UB; k++) rw[k] = d[k].y;
 #pragma unroll
-            for (int k = 0; k < UB; k++) xv[k] = x[min((long long)(d[k].x & POOL_BASE_MASK) + (long long)sc[16 * (j0 + k)], xlast)];
+            for (int k = 0; k < UB; k++) {
+                if constexpr (UNIT_X32) xv[k] = x[x_index32((int)(d[k].x & POOL_BASE_MASK), sc[16 * (j0 + k)], xlast32)];
+                else xv[k] = x[min((long long)(d[k].x & POOL_BASE_MASK) + (long long)sc[16 * (j0 + k)], xlast)];
+            }
             return;
         }
         if constexpr (POOL) {
 #pragma unroll
             for (int k = 0; k < UB; k++) rw[k] = sr[2 * (j0 + k)];
 #pragma unroll
-            for (int k = 0; k < UB; k++) xv[k] = x[min((long long)(d[k].x & POOL_BASE_MASK) + (long long)((d[k].y >> (28 - 4 * (r & 7))) & 15u), xlast)];
+            for (int k = 0; k < UB; k++) {
+                if constexpr (UNIT_X32) xv[k] = x[x_index32((int)(d[k].x & POOL_BASE_MASK), (d[k].y >> (28 - 4 * (r & 7))) & 15u, xlast32)];
+                else xv[k] = x[min((long long)(d[k].x & POOL_BASE_MASK) + (long long)((d[k].y >> (28 - 4 * (r & 7))) & 15u), xlast)];
+            }
             return;
         }
 #pragma unroll
@@ -679,6 +696,7 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             const unsigned fl = d[k].x >> 24;
             const unsigned nib = (fl & UNIT_ROWUNIT) ? (unsigned)r : (d[k].y >> (28 - 4 * (r & 7))) & 15u;
             if ((d[k].x >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE && r != 15) xv[k] = 0;   // derived unit: only lane 15 loads (unit_x_use gives the others the previous unit's x)
+            else if constexpr (UNIT_X32) xv[k] = x[x_index32(unit_x_base32(d[k].x), nib, xlast32)];
             else xv[k] = x[min(unit_x_base(d[k].x) + nib, xlast)];
         }
     };
@@ -856,7 +874,9 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             sval_t vn[UB];   // (narrow plans: the prefetched batch waits as floats and is widened when it becomes `v`)
 #pragma unroll
             for (int k = 0; k < UB; k += G) {  // unconditional (clamped to the task's last group): exact vmcnt
-                const grp_t pv = stream_load<NT>(ugrp + (long long)min(u + UB + k, last_grp) * (16 / G));
+                const grp_t *pa = ugrp + (long long)min(u + UB + k, last_grp) * (16 / G);
+                if constexpr (UNIT_TAIL_HOT) pa = (u + UB + k <= last_grp) ? pa : reinterpret_cast<const grp_t *>(S.uval);   // behind the task's end: nobody uses what this loads
+                const grp_t pv = stream_load<NT>(pa);
 #pragma unroll
                 for (int q = 0; q < G; q++) vn[k + q] = pv[q];
             }
