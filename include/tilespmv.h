@@ -348,9 +348,11 @@ typedef struct {
                            graph Laplacians, integer / pattern matrices, anything assembled in single precision) stores them as 4-byte floats, four units per 16-byte lane load;
                            the kernels widen them in registers and the arithmetic stays fp64, so y keeps every bit.  Classic (non-pooled) unit plans of the stream kernel with
                            entry mode 0 or 2 and 16 strips per workgroup, built without TILESPMV_CREATE_VALUE_MAP and without nt_stream = 0; a narrow plan always reads its
-                           streams nontemporally (nt_stream 1).  0 = never; 1 = wherever eligible and narrowable; unset = where the narrowed launch still moves more than the
-                           400 MB above which nt_stream is 1 by rule (smaller plans live in the caches and are bound by latency, not bytes).  Ignored by the fp32 build.
-                           TILESPMV_INFO_UNIT_VALUE_BYTES tells which form a plan has                                                      TILESPMV_VALUE_NARROW */
+                           streams nontemporally (nt_stream 1).  Where every value is moreover +-0 or a NORMAL IEEE binary16 number (every integer up to 2048, coefficients such as 0.25) the
+                           plan can store 2-byte halves instead, four units per 8-byte lane load, widened half -> float -> double (both exact): y still keeps every bit.
+                           0 = never; 1 = floats wherever eligible and narrowable (never halves); 2 = the narrowest width every value allows, wherever eligible: 2, else 4, else 8 bytes;
+                           unset = the narrowest width whose launch still moves more than the 400 MB above which nt_stream is 1 by rule (smaller plans live in the caches and are bound by
+                           latency, not bytes).  Ignored by the fp32 build.  TILESPMV_INFO_UNIT_VALUE_BYTES tells which form a plan has             TILESPMV_VALUE_NARROW */
     int reserved[1];    /* must be TILESPMV_KNOB_DEFAULT or 0 */
 } tilespmv_plan_options;
 void tilespmv_plan_options_init(tilespmv_plan_options *opts);
@@ -505,7 +507,7 @@ enum {
     TILESPMV_INFO_BRICK_ORDER = 19,       /* 1: the strips were regrouped into bricks of the grid (stencil-like shard) */
     TILESPMV_INFO_DESC_BYTES = 20,        /* bytes per unit descriptor in HBM: 12, or 4 (column-pattern dictionary); pooled plans 20, or 8 (pattern dictionary); wide pooled plans 28 */
     TILESPMV_INFO_NT_STREAM = 21,         /* 1: the unit kernel reads the value / entry-record streams with nontemporal loads */
-    TILESPMV_INFO_UNIT_VALUE_BYTES = 22,  /* bytes per stored unit value: 8, or 4 in a narrow plan (value_narrow); the fp32 build always reports 4 */
+    TILESPMV_INFO_UNIT_VALUE_BYTES = 22,  /* bytes per stored unit value: 8, or 4 (floats) / 2 (halves) in a narrow plan (value_narrow); the fp32 build always reports 4 */
     TILESPMV_INFO_RETIRED_23 = 23,        /* always 0 */
     TILESPMV_INFO_PLACEMENT_TRIES = 24,   /* arena placements timed at plan creation (large plans; 0 / 1 = the first one was kept) */
     TILESPMV_INFO_RETIRED_25 = 25,        /* always 0 */

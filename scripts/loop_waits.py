@@ -1,7 +1,7 @@
 """The unit loop of every k_units / k_units_mv / k_pool_mv instantiation as the gfx950 compiler scheduled it (device assembly, no GPU):
     python scripts/loop_waits.py [f64|f32] [filter]
 For each kernel: the innermost loop that holds the value-stream load (the last 16-byte global load that sits in a loop: the entry phases come before the unit loop, the
-fix-up and y loops behind it load less), its `s_waitcnt vmcnt` values in program order, its instruction count, the waits that follow the first load behind the park inside the
+fix-up and y loops behind it load less; in the kernels of hip_kernels_half.hip, whose values are halves, the last nontemporal 8-byte load — HALF_VALUE_LOAD), its `s_waitcnt vmcnt` values in program order, its instruction count, the waits that follow the first load behind the park inside the
 chunk refill (the block, in a loop, that parks a descriptor chunk with ds_write_b128: the pattern gather of a dictionary plan, the descriptor load of a 12-byte one), and the kernel's VGPRs and scratch.  tests/test_unit_loop_waits_cpu.py asserts on `unit_loops()`."""
 import os
 import re
@@ -39,8 +39,13 @@ def _blocks(body):
     return out
 
 
-def unit_loops(asm, kinds=("k_units",)):
-    """{demangled kernel: dict(vmcnt=[...], insns=n, refill_waits=[...] or None, vgpr=n, scratch=n)} for the kernels whose name starts with one of ``kinds``."""
+HALF_VALUE_LOAD = r"global_load_dwordx2 .*\bnt\b"   # the value-stream load of k_units_half (the x gathers are 8-byte loads too, but not nontemporal)
+
+
+def unit_loops(asm, kinds=("k_units",), value_load=r"global_load_dwordx4\b"):
+    """{demangled kernel: dict(vmcnt=[...], insns=n, refill_waits=[...] or None, vgpr=n, scratch=n)} for the kernels whose name starts with one of ``kinds``;
+    ``value_load``: regular expression (mnemonic + operands) of the value-stream load that marks the unit loop."""
+    value_load = re.compile(value_load)
     funcs = re.findall(r"^(_Z\w+):\s*; @\1\n(.*?)^\s+s_endpgm", asm, re.S | re.M)
     meta = {n: b for n, b in re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S)}
     names = [n for n, _ in funcs]
@@ -53,7 +58,7 @@ def unit_loops(asm, kinds=("k_units",)):
         blocks = _blocks(body)
         hdr = None
         for _, h, insns in blocks:
-            if h is not None and any(op == "global_load_dwordx4" for op, _ in insns):
+            if h is not None and any(value_load.match(op + a) for op, a in insns):
                 hdr = h
         g = lambda k: int(re.search(r"\.amdhsa_%s (\d+)" % k, meta[name]).group(1))
         rec = dict(vmcnt=[], insns=0, refill_waits=None, vgpr=g("next_free_vgpr"), scratch=g("private_segment_fixed_size"))
@@ -76,7 +81,10 @@ def main():
     dt = sys.argv[1] if len(sys.argv) > 1 else "f64"
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
     asm = device_asm("hip_kernels.hip", dt, os.environ.get("LOOP_WAITS_ASM", "/tmp/loop_waits_%s.s" % dt))
-    for d, r in unit_loops(asm, ("k_units", "k_units_mv", "k_pool_mv")).items():
+    recs = list(unit_loops(asm, ("k_units", "k_units_mv", "k_pool_mv")).items())
+    if dt == "f64":   # the kernels whose values are halves: a file of their own
+        recs += list(unit_loops(device_asm("hip_kernels_half.hip", dt, os.environ.get("LOOP_WAITS_ASM_HALF", "/tmp/loop_waits_half.s")), ("k_units_half",), HALF_VALUE_LOAD).items())
+    for d, r in recs:
         if flt in d:
             print("%-62s vgpr %3d scratch %3d loop insns %4d vmcnt %-22s refill waits after the gather: %s" %
                   (d, r["vgpr"], r["scratch"], r["insns"], ",".join(map(str, r["vmcnt"])), "-" if r["refill_waits"] is None else (" | ".join(r["refill_waits"]) or "none")))

@@ -36,7 +36,7 @@ for k, t in per.items():
     t["bytes_per_launch"] = int((t.get("FETCH_SIZE_kb", 0) * factor + t.get("WRITE_SIZE_kb", 0)) * 1024)
 # a SpMV of a panelled / dense-tile plan is several launches: bytes per SpMV = sum over the kernels of bytes per launch x launches per SpMV (k_units runs once per SpMV)
 calls = {k["name"]: k["calls"] for k in kern}
-unit_calls = max([c for n, c in calls.items() if "k_units<" in n or "k_tiles_direct" in n] or [0])
+unit_calls = max([c for n, c in calls.items() if "k_units<" in n or "k_units_half<" in n or "k_tiles_direct" in n] or [0])
 per_spmv = None
 if unit_calls:
     per_spmv = 0

@@ -99,7 +99,7 @@ constexpr int UNIT_SHIFT_SHIFT = 29;      // unit flag bits 5-7 (word 0 bits 29-
 constexpr int ABSORB_SHIFT_MIN = -3, ABSORB_SHIFT_MAX = 3;   //   x index = column block * 16 + shift + nibble.  Dictionary plans keep the shift with the pattern (DevStream::udict)
 constexpr unsigned UNIT_DERIVED_CODE = 4u;                   //   shift code -4: a DERIVED unit — lanes 0-14 take the previous unit's x one lane up, lane 15 loads (plan_tile_ops.h)
 constexpr int UNIT_GROUP = 16 / (int)sizeof(val_t);  // units whose values share one 16-byte lane load (2 in fp64, 4 in fp32)
-constexpr int UNIT_GROUP_NARROW = 4;      // ... and in a narrow fp64 plan (DevStream::uval_narrow: 4-byte values), the fp32 build's grouping
+constexpr int UNIT_GROUP_NARROW = 4;      // ... and in a narrow fp64 plan (DevStream::uval_narrow: 4-byte or 2-byte values), the fp32 build's grouping
 constexpr long long NT_STREAM_MIN_BYTES = 400ll << 20;   // launches that move more than this (about 1.6 x the 256 MB Infinity Cache) read their once-read streams nontemporally
 constexpr int DICT_MAX_BITS = 10;         // dictionary plans: at most 1024 column patterns (8 KB: stays in the vector L1)
 constexpr int UNIT_FLAG_SHIFT = 24;       // flags live above the 24-bit column block in words 0 and 2
@@ -179,7 +179,7 @@ struct DevStream {
     const uint4 *udict;                   // dictionary plans: the column patterns (nibbles of rows 0-7, of rows 8-15, window shift << UNIT_SHIFT_SHIFT, 0), ordered by (shift, nibbles); udesc / udesc_cb then hold 4-B words
     int cb_bits;                          // ... column block (cb_bits) | pattern id | flags << 27;  0 = 12-B descriptors.  Pooled dictionary plans: bits of the window base in the 4-byte word, 0 = 8-byte pairs
     int nt_stream;                        // 1: value / entry-record loads are nontemporal (the plan's streams do not fit the Infinity Cache)
-    int uval_narrow;                      // fp64 build, 1: uval holds FLOATS in groups of UNIT_GROUP_NARROW units (plan_tile_ops.h value_narrowable; the kernels widen them in registers).  Classic plans, entry mode 0 / 2, 16 strips, nt_stream 1
+    int uval_narrow;                      // fp64 build, the form of uval: 0 = val_t; 1 = FLOATS, 2 = HALVES (IEEE binary16), both in groups of UNIT_GROUP_NARROW units (plan_tile_ops.h value_narrowable / value_halvable; the kernels widen them in registers).  Classic plans, entry mode 0 / 2, 16 strips, nt_stream 1
     // column panels (round 4): a group's merged list is in column order, so the entries of column panel p (2^k columns, a few MB of x) are the run
     // [panel_off[group * (x_panels + 1) + p], panel_off[.. + p + 1]) of it.  A launch either walks whole lists in k_units (panel_merge = 0) or gives k_units the first
     // panel_merge panels and each further run of panel_merge panels a launch of k_entries_acc (y +=): all gathers of one pass then fall into one slice of x.
@@ -229,5 +229,9 @@ inline void tile_stream_sizes(int fmt, int p1, int p2, int *nv, int *ni)
     default: *nv = 0; *ni = 0; break;
     }
 }
+
+// hip_kernels_half.hip: the k_units launch of a plan whose unit values are halves (DevStream::uval_narrow 2), called by launch_tiles_stream (hip_kernels.hip);
+// hipErrorInvalidValue for any other plan and in the fp32 build
+hipError_t launch_units_half(const DevPlan &P, const DevStream &S, int entry_mode, int wg_strips, int lds_pad_bytes, int xcd_chunk, const val_t *x, val_t *y, hipStream_t st);
 
 }  // namespace tilespmv

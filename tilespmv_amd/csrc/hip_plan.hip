@@ -793,7 +793,7 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
     I[TILESPMV_INFO_COO_MODE] = coo_mode; I[TILESPMV_INFO_DENSE_MODE] = dense_mode; I[TILESPMV_INFO_KERNEL] = plan->kernel;
     I[TILESPMV_INFO_NUM_TASKS] = n_tasks; I[TILESPMV_INFO_NUM_SPLIT_ROWS] = (long long)fix.size();
     I[TILESPMV_INFO_FALLBACK_NNZ] = f_nnz;
-    I[TILESPMV_INFO_UNIT_VALUE_BYTES] = plan->st.uval_narrow ? 4 : sv;
+    I[TILESPMV_INFO_UNIT_VALUE_BYTES] = plan->st.uval_narrow == 2 ? 2 : plan->st.uval_narrow ? 4 : sv;
     if (plan->kernel != TILESPMV_KERNEL_STREAM) { I[TILESPMV_INFO_ENTRY_ORDERED] = 1; I[TILESPMV_INFO_STRIP_COST] = target; }
     I[TILESPMV_INFO_BUILD_US] = (long long)(now_us() - t_create0) - I[TILESPMV_INFO_UPLOAD_US];
     // bytes one SpMV has to move at least: the three streams + tasks + x once + y once (+ fallback)

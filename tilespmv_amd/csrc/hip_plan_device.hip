@@ -626,27 +626,33 @@ int dev_pack_desc(const uint4 *d_udesc, const uint2 *d_urow, const uint4 *d_ucol
     return 0;
 }
 
-// every slot of EMIT's unit-value array narrowable (plan_tile_ops.h value_narrowable)?  counts the slots that are not
+// every slot of EMIT's unit-value array narrowable / halvable (plan_tile_ops.h)?  one pass counts the slots that are not floats (bad[0]) and those that are not halves (bad[1])
 #if !defined(TILESPMV_F32)
 __global__ __launch_bounds__(256) void k_pd_not_narrowable(const val_t *__restrict__ v, long long n, unsigned long long *__restrict__ bad)
 {
-    unsigned mine = 0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) mine += value_narrowable(v[i]) ? 0u : 1u;
-    if (mine) atomicAdd(bad, (unsigned long long)mine);
+    unsigned nf = 0, nh = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const val_t a = v[i];
+        nf += value_narrowable(a) ? 0u : 1u;
+        nh += value_halvable(a) ? 0u : 1u;
+    }
+    if (nf) atomicAdd(bad, (unsigned long long)nf);
+    if (nh) atomicAdd(bad + 1, (unsigned long long)nh);
 }
 #endif
-int dev_all_narrowable(const val_t *d_uval, long long n, bool *all)
+int dev_all_narrowable(const val_t *d_uval, long long n, bool *all_float, bool *all_half)
 {
-    *all = false;
+    *all_float = *all_half = false;
 #if !defined(TILESPMV_F32)
-    if (n <= 0) { *all = true; return 0; }
+    if (n <= 0) { *all_float = *all_half = true; return 0; }
     Tmp<unsigned long long> bad;
-    PD_TRY(bad.alloc(1, true));
+    PD_TRY(bad.alloc(2, true));
     hipLaunchKernelGGL(k_pd_not_narrowable, dim3((unsigned)std::min<long long>(nblk(n, 256), 8192)), dim3(256), 0, 0, d_uval, n, bad.p);
     PD_TRY(hipGetLastError());
-    unsigned long long h = 1;
-    PD_TRY(hipMemcpy(&h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
-    *all = h == 0;
+    unsigned long long h[2] = {1, 1};
+    PD_TRY(hipMemcpy(h, bad.p, sizeof(h), hipMemcpyDeviceToHost));
+    *all_float = h[0] == 0;
+    *all_half = h[1] == 0;
 #else
     (void)d_uval; (void)n;
 #endif

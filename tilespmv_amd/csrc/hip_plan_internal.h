@@ -64,7 +64,7 @@ struct Knobs {
     int placement_tries; // large plans: arena placements timed at plan creation (-1 by size, 0 / 1 off, n)
     int deterministic;   // 1: nothing is chosen by timing, every sum in a plan-fixed order (tilespmv_plan_options.deterministic)
     int absorb;          // 1 (default): list entries next to an ELL tile go into its padding slots (plan_tile_ops.h "absorbed list entries"); 0 = never
-    int value_narrow;    // fp64: unit values stored as floats where every one survives the round trip: 0 never, 1 wherever eligible, -1 where the narrowed launch stays above NT_STREAM_MIN_BYTES
+    int value_narrow;    // fp64: unit values stored as floats / halves where every one survives the round trip: 0 never, 1 floats wherever eligible, 2 the narrowest form the values allow wherever eligible, -1 the narrowest form whose launch stays above NT_STREAM_MIN_BYTES
     bool value_map;      // the plan is built from stand-in values (TILESPMV_CREATE_VALUE_MAP): its layout follows the pattern alone
     int desc_dict;       // 0 = always 12-B unit descriptors; -1 = 4-B descriptors + pattern dictionary where the shard allows and it pays; 1 = wherever it allows; 2 = like 1 (pooled plans: 8-byte pairs instead of 4-byte words)
     bool xcd_from_caller, entry_from_caller, strip_from_caller;   // the autotuner leaves alone what the caller pinned
@@ -329,8 +329,9 @@ inline bool pack_list(const std::vector<PEnt> &ents, int dest_bits, std::vector<
     return j == ents.size() && base.size() - base0 == (rec.size() - rec0 + ECHUNK - 1) / ECHUNK;
 }
 
+// (launch_units_half, the k_units launch of a plan whose unit values are halves, is declared in hip_plan.h: hip_kernels.hip, which calls it, includes only that header)
 // the value pass of the ENCODE stage on the device (hip_kernels.hip k_pair_values)
-hipError_t launch_pair_values(const val_t *src, val_t *dst, const int4 *map, int ntasks, bool narrow);   // narrow: dst holds floats in groups of UNIT_GROUP_NARROW units
+hipError_t launch_pair_values(const val_t *src, val_t *dst, const int4 *map, int ntasks, int narrow);   // narrow (DevStream::uval_narrow) 1 / 2: dst holds floats / halves in groups of UNIT_GROUP_NARROW units
 
 // hip_value_map.hip: reads the value map off the streams of a plan built from stand-in values (hip_tile_create.h vmap_encode), positions below `limit`, then writes the values of
 // d_val in (d_val indexed by those positions).  Returns 0, -3 HIP error, -6 a slot names a position outside [0, limit) (internal error)

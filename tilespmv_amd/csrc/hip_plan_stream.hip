@@ -132,10 +132,16 @@ struct StreamBuilder {
     // ENCODE / ENTRIES
     long long NUP = 0, n_rec = 0, n_chunk = 0, n_groups = 0, panel_rmw_rows = 0;
     bool pool_dict = false;   // pooled plan with 8-B descriptors + pattern dictionary
-    bool narrow = false;      // fp64: the unit values are stored as floats, 4 units per group (hip_plan.h DevStream::uval_narrow); decided at the start of ENCODE
-    long long value_bytes() const { return narrow ? 4 : sv; }   // bytes per stored unit value
+    int narrow = 0;           // fp64: 1 / 2 = the unit values are stored as floats / halves, 4 units per group (hip_plan.h DevStream::uval_narrow); decided at the start of ENCODE
+    long long value_bytes() const { return narrow == 2 ? 2 : narrow ? 4 : sv; }   // bytes per stored unit value
     long long value_group() const { return narrow ? UNIT_GROUP_NARROW : UNIT_GROUP; }
     void choose_value_width();
+    int reserve_values()      // arena space for the NUP * 16 stored values, in the plan's form
+    {
+        if (narrow == 2) return plan->reserve((size_t)NUP * 16, reinterpret_cast<const unsigned short **>(&S.uval));
+        if (narrow) return plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
+        return plan->reserve((size_t)NUP * 16, &S.uval);
+    }
     long long desc_bytes() const { return S.cb_bits > 0 ? 4 : wide ? 28 : pooled ? (pool_dict ? 8 : 20) : 12; }
     std::vector<long long> old_begin;
 
@@ -722,35 +728,45 @@ void StreamBuilder::order()
 }
 
 // Narrow unit values (include/tilespmv.h value_narrow; fp64 build): taken at the start of ENCODE, because the groups of 4 change the padded unit numbering everything
-// after it uses.  Eligible: classic units, entry mode 0 / 2 with 16 strips per workgroup (the forms k_units has a narrow instantiation of), no value map (a flagged plan's
-// layout follows the pattern alone), nontemporal streams not refused by the caller.  With the knob unset the narrowed launch must still move more than NT_STREAM_MIN_BYTES —
-// judged by a LOWER bound of FINISH's byte model (4-byte descriptors, one record per list entry, no whole-tile passes: what is known here), so that a plan narrowed by
-// rule is also nontemporal by FINISH's rule.  Narrowable: every slot of EMIT's value array passes value_narrowable — host loop or device reduction over the same array.
+// after it uses.  Eligible: classic units, entry mode 0 / 2 with 16 strips per workgroup (the forms k_units has narrow instantiations of), no value map (a flagged plan's
+// layout follows the pattern alone), nontemporal streams not refused by the caller.  The width is 8, 4 (floats) or 2 bytes (halves): every slot of EMIT's value array must
+// pass value_narrowable / value_halvable — host loop or device reduction over the same array, one pass for both.  Knob 1 = floats (never halves), 2 = the narrowest width
+// the values allow.  With the knob unset the narrowed launch must still move more than NT_STREAM_MIN_BYTES — judged by a LOWER bound of FINISH's byte model (4-byte
+// descriptors, one record per list entry, no whole-tile passes: what is known here), so that a plan narrowed by rule is also nontemporal by FINISH's rule; the rule is
+// tried narrowest first, so a plan too small for halves can still get floats.
 void StreamBuilder::choose_value_width()
 {
-    narrow = false;
+    narrow = 0;
     if (sizeof(val_t) != 8 || K.value_narrow == 0 || pooled || K.value_map || K.nt_stream == 0 || NU <= 0) return;
     if (!(entry_mode == 0 || entry_mode == 2) || wg_strips != 16) return;
+    bool may_float = true, may_half = K.value_narrow != 1;   // what the knob and the size rule allow
     if (K.value_narrow < 0) {
         long long nup4 = 0;
         for (const STask &k : tasks) nup4 += (k.unit_end - k.unit_begin + UNIT_GROUP_NARROW - 1) / UNIT_GROUP_NARROW * UNIT_GROUP_NARROW;
-        const long long launch_min = nup4 * (4 + 16LL * 4) + NC * (entry_mode == 0 ? sv + 5LL : (long long)sizeof(ERec)) + (long long)tasks.size() * (long long)sizeof(STask) + ((long long)colA + 16LL * ntr) * sv;
-        if (launch_min <= NT_STREAM_MIN_BYTES) return;
+        auto launch_min = [&](long long vb) { return nup4 * (4 + 16LL * vb) + NC * (entry_mode == 0 ? sv + 5LL : (long long)sizeof(ERec)) + (long long)tasks.size() * (long long)sizeof(STask) + ((long long)colA + 16LL * ntr) * sv; };
+        may_half = launch_min(2) > NT_STREAM_MIN_BYTES;
+        may_float = launch_min(4) > NT_STREAM_MIN_BYTES;
+        if (!may_float) return;   // (the 2-byte bound is the smaller one)
     }
     const long long n = NU * 16;
+    bool all_float = false, all_half = false;
     if (DT) {
-        bool all = false;
-        if (dev_all_narrowable(d_uval, n, &all) != 0) { rc = -3; return; }
-        narrow = all;
+        if (dev_all_narrowable(d_uval, n, &all_float, &all_half) != 0) { rc = -3; return; }
     } else {
-        std::atomic<int> bad(0);
+        std::atomic<int> not_float(0), not_half(0);
         parallel_chunks(n, 1 << 18, [&](int64_t b, int64_t e, int) {
-            if (bad.load(std::memory_order_relaxed)) return;
-            for (int64_t i = b; i < e; i++) if (!value_narrowable((double)h_uval[i])) { bad.store(1); return; }
+            if (not_float.load(std::memory_order_relaxed)) return;
+            bool h = !not_half.load(std::memory_order_relaxed);
+            for (int64_t i = b; i < e; i++) {
+                if (h && !value_halvable((double)h_uval[i])) { not_half.store(1); h = false; }
+                if (!h && !value_narrowable((double)h_uval[i])) { not_float.store(1); not_half.store(1); return; }   // (every half is a float)
+            }
         });
-        narrow = bad.load() == 0;
+        all_float = not_float.load() == 0;
+        all_half = not_half.load() == 0;
     }
-    if (K.verbose) fprintf(stderr, "tilespmv: unit values: %s\n", narrow ? "every one is a float: stored in 4 bytes" : "8 bytes (not all of them survive double -> float -> double)");
+    narrow = may_half && all_half ? 2 : may_float && all_float ? 1 : 0;
+    if (K.verbose) fprintf(stderr, "tilespmv: unit values: %s\n", narrow == 2 ? "every one is a half: stored in 2 bytes" : narrow ? "every one is a float: stored in 4 bytes" : "8 bytes (not all of them survive the narrowing the knob and the size rule allow)");
 }
 
 // ENCODE in device mode: the same final forms, produced from EMIT's device scratch (hip_plan_device.h)
@@ -830,8 +846,7 @@ void StreamBuilder::encode_device()
     plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
     if (rc == 0 && !pooled) { unsigned long long hist[8]; if (dev_shift_histogram(d_packed, NUP, hist) != 0) rc = -3; else plan->info[TILESPMV_INFO_DERIVED_UNITS] = (long long)hist[UNIT_DERIVED_CODE]; }
     // the value pass (as in host mode: k_pair_values), its source already on the device
-    if (narrow) rc |= plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
-    else rc |= plan->reserve((size_t)NUP * 16, &S.uval);
+    rc |= reserve_values();
     if (rc == 0) {
         e = launch_pair_values(d_uval, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size(), narrow);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -851,10 +866,13 @@ void StreamBuilder::encode()
     // the G units interleaved per row, so that a lane fetches G units with one 16-byte load (row r of the group at
     // +16 r bytes).  A task whose unit count is not a multiple of G gets padding units (zero values, never executed:
     // unit_end excludes them) so that its last group exists.
-    // Narrow plans (fp64, choose_value_width): the values are floats and G = 4, the fp32 build's layout.
+    // Narrow plans (fp64, choose_value_width): the values are floats or halves and G = 4, the fp32 build's unit numbering; row r of a group is 16 or 8 bytes.
     choose_value_width();
     if (rc) return;
-    S.uval_narrow = narrow ? 1 : 0;
+    S.uval_narrow = narrow;
+    // the estimate that sizes the arena blocks priced the values at sizeof(val_t); a plan of halves is up to four times smaller.  (The float form keeps the estimate — an upper
+    // bound — it has always had, so that its plans are placed in memory as before.)
+    if (narrow == 2) plan->size_hint -= std::min(plan->size_hint, (size_t)(NU * 16 * (sv - value_bytes())));
     const long long G = value_group();
     auto padded = [&](long long n) { return (n + G - 1) / G * G; };
     NUP = 0;
@@ -874,7 +892,8 @@ void StreamBuilder::encode()
         const bool encode_check = !plan->dry && K.encode_check;
         const bool on_device = !plan->dry && NUP > 0 && !K.encode_on_host;
         val_t *paired = (on_device && !encode_check) || narrow ? nullptr : zalloc<val_t>((size_t)NUP * 16);
-        float *paired_n = (on_device && !encode_check) || !narrow ? nullptr : zalloc<float>((size_t)NUP * 16);   // narrow plans: the same groups, of floats
+        float *paired_n = (on_device && !encode_check) || narrow != 1 ? nullptr : zalloc<float>((size_t)NUP * 16);   // narrow plans: the same groups, of floats
+        unsigned short *paired_h = (on_device && !encode_check) || narrow != 2 ? nullptr : zalloc<unsigned short>((size_t)NUP * 16);   // ... or of halves
         std::vector<int4> pair_map(on_device ? tasks.size() : 0);
         std::vector<long long> new_begin(tasks.size());
         old_begin.assign(tasks.size(), 0);
@@ -899,6 +918,11 @@ void StreamBuilder::encode()
                         const val_t *src = h_uval + (ub + j) * 16;
                         float *dst = paired_n + (nb + j / G * G) * 16 + (j % G);
                         for (int r = 0; r < 16; r++) dst[G * r] = (float)src[r];
+                    }
+                    if (paired_h) {
+                        const val_t *src = h_uval + (ub + j) * 16;
+                        unsigned short *dst = paired_h + (nb + j / G * G) * 16 + (j % G);
+                        for (int r = 0; r < 16; r++) dst[G * r] = value_half_bits((double)src[r]);
                     }
                 }
                 if (on_device) pair_map[(size_t)i] = make_int4((int)ub, (int)nb, (int)n, 0);
@@ -1029,8 +1053,7 @@ void StreamBuilder::encode()
             const double t0 = now_us();
             void *d_src = nullptr, *d_map = nullptr;
             const size_t src_b = (size_t)NU * 16 * sizeof(val_t), map_b = pair_map.size() * sizeof(int4);
-            if (narrow) rc |= plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
-            else rc |= plan->reserve((size_t)NUP * 16, &S.uval);
+            rc |= reserve_values();
             hipError_t e = hipMalloc(&d_src, std::max<size_t>(src_b, 16));
             if (e == hipSuccess) e = hipMalloc(&d_map, std::max<size_t>(map_b, 16));
             if (e == hipSuccess) e = hipMemcpy(d_src, h_uval, src_b, hipMemcpyHostToDevice);
@@ -1040,16 +1063,17 @@ void StreamBuilder::encode()
             if (e == hipSuccess && encode_check) {
                 std::vector<unsigned char> back((size_t)NUP * 16 * (size_t)value_bytes());
                 e = hipMemcpy(back.data(), S.uval, back.size(), hipMemcpyDeviceToHost);
-                if (e == hipSuccess && memcmp(back.data(), narrow ? (const void *)paired_n : (const void *)paired, back.size()) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
+                if (e == hipSuccess && memcmp(back.data(), narrow == 2 ? (const void *)paired_h : narrow ? (const void *)paired_n : (const void *)paired, back.size()) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
                 else if (e == hipSuccess && K.verbose) fprintf(stderr, "tilespmv: encode check: %lld units, device value stream == host value stream\n", NUP);
             }
             if (d_src) (void)hipFree(d_src);
             if (d_map) (void)hipFree(d_map);
             if (e != hipSuccess) { fprintf(stderr, "tilespmv: value pass on the device failed: %s\n", hipGetErrorString(e)); (void)hipGetLastError(); rc = -3; }
             plan->info[TILESPMV_INFO_UPLOAD_US] += (long long)(now_us() - t0);
-        } else if (narrow) rc |= plan->upload(paired_n, (size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
+        } else if (narrow == 2) rc |= plan->upload(paired_h, (size_t)NUP * 16, reinterpret_cast<const unsigned short **>(&S.uval));
+        else if (narrow) rc |= plan->upload(paired_n, (size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
         else rc |= plan->upload(paired, (size_t)NUP * 16, &S.uval);
-        free_later({paired, paired_n, h_uval}, (size_t)NUP * 16 * sizeof(val_t));   // (h_uval was read for the last time above)
+        free_later({paired, paired_n, paired_h, h_uval}, (size_t)NUP * 16 * sizeof(val_t));   // (h_uval was read for the last time above)
         h_uval = nullptr;
         S.udesc_cb = S.udesc;
     }

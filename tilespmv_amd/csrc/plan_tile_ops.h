@@ -24,6 +24,28 @@ TILESPMV_HD inline bool value_narrowable(double v)
     if (ex < 1023u - 126u || ex > 1023u + 127u) return false;     // below FLT_MIN (fp32 denormals included) / above FLT_MAX
     return (b & ((1ull << 29) - 1ull)) == 0;                      // the 29 mantissa bits a float does not have
 }
+// ... and as an IEEE binary16 (DevStream::uval_narrow 2) iff it is +-0 or a NORMAL half: unbiased exponent in [-14, 15] and none of the 42 mantissa bits a half does not
+// have (every integer up to 2048, dyadic coefficients such as 0.25; fp16 denormals are refused for the reason fp32 denormals are).  The kernels widen half -> float -> double,
+// both exact.  Every halvable value is narrowable.
+TILESPMV_HD inline bool value_halvable(double v)
+{
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    const unsigned ex = (unsigned)(b >> 52) & 0x7FFu;
+    if ((b << 1) == 0) return true;                               // +-0
+    if (ex < 1023u - 14u || ex > 1023u + 15u) return false;       // below 2^-14 (fp16 denormals included) / above 65504, infinity, NaN
+    return (b & ((1ull << 42) - 1ull)) == 0;
+}
+// the 16 bits of a halvable value: sign, exponent re-biased from 1023 to 15, the top 10 mantissa bits (valid only where value_halvable holds)
+TILESPMV_HD inline unsigned short value_half_bits(double v)
+{
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    const unsigned sign = (unsigned)(b >> 63) << 15;
+    if ((b << 1) == 0) return (unsigned short)sign;
+    const unsigned ex = ((unsigned)(b >> 52) & 0x7FFu) - (1023u - 15u);
+    return (unsigned short)(sign | (ex << 10) | ((unsigned)(b >> 42) & 0x3FFu));
+}
 
 // A CSR tile is executed as w ELL-style units (the first w entries of every row) plus the rest of its entries on the strip's COO list; w minimises the bytes moved
 // (HYB's idea, src/csr2tile.h:279-306, with this kernel's byte costs).  Returns w and the number of remainder entries.
