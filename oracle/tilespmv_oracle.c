@@ -245,6 +245,7 @@ void oracle_Tile_create(Tile_matrix *T, int rowA, int colA, MAT_PTR_TYPE nnzA,
     T->new_coocount = zalloc(np1, sizeof(int));
 
     /* ---- selection (step3) and size totals (:742-794) */
+    size_t hyb_idx_bytes = 0;   /* of hybIdx: per HYB tile its ELL part in nibbles, rounded up to a byte, then one byte per remainder entry */
     for (int bi = 0; bi < tilem; bi++) {
         int rowlen = (bi == tilem - 1) ? rowA - (tilem - 1) * BS : BS;
         for (int t = T->tile_ptr[bi]; t < T->tile_ptr[bi + 1]; t++) {
@@ -263,7 +264,7 @@ void oracle_Tile_create(Tile_matrix *T, int rowA, int colA, MAT_PTR_TYPE nnzA,
             case TILESPMV_FMT_CSR: T->csr_offset[t] = c.stored; T->csrsize += c.stored; T->csrptrlen += rowlen; break;
             case TILESPMV_FMT_COO: T->coo_offset[t] = c.stored; T->coosize += c.stored; break;
             case TILESPMV_FMT_ELL: T->ell_offset[t] = c.stored; T->ellsize += c.stored; break;
-            case TILESPMV_FMT_HYB: T->hyb_offset[t] = c.stored; T->hybsize += c.stored; T->hybellsize += c.width * rowlen; break;
+            case TILESPMV_FMT_HYB: T->hyb_offset[t] = c.stored; T->hybsize += c.stored; T->hybellsize += c.width * rowlen; hyb_idx_bytes += (size_t)(c.width * rowlen + 1) / 2 + c.hybcoo; break;
             case TILESPMV_FMT_DNS: T->dns_offset[t] = c.stored; T->dnssize += c.stored; break;
             case TILESPMV_FMT_DNSROW: T->dnsrow_offset[t] = c.stored; T->dnsrowsize += c.stored; break;
             case TILESPMV_FMT_DNSCOL: T->dnscol_offset[t] = c.stored; T->dnscolsize += c.stored; break;
@@ -287,7 +288,7 @@ void oracle_Tile_create(Tile_matrix *T, int rowA, int colA, MAT_PTR_TYPE nnzA,
     T->Blockell_Val = zalloc(T->ellsize, sizeof(val_t));
     T->ell_compressedIdx = zalloc((T->ellsize + 1) / 2, 1);
     T->Blockhyb_Val = zalloc((size_t)T->hybellsize + T->hybcoosize, sizeof(val_t));
-    T->hybIdx = zalloc((size_t)(T->hybellsize + 1) / 2 + T->hybcoosize, 1);
+    T->hybIdx = zalloc(hyb_idx_bytes, 1);   /* whole bytes per tile (the packing below): more than (hybellsize + 1) / 2 + hybcoosize where a partial last tile-row holds HYB tiles of odd width */
     T->Blockdense_Val = zalloc(T->dnssize, sizeof(val_t));
     T->Blockdenserow_Val = zalloc(T->dnsrowsize, sizeof(val_t));
     T->denserowid = zalloc(T->dnsrowptr[tilenum], 1);

@@ -12,7 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cases  # noqa: E402
-from gpu_fuzz import random_matrix  # noqa: E402
+from random_matrices import random_matrix  # noqa: E402
 from tilespmv_amd import api, generators as G  # noqa: E402
 from tilespmv_amd.tile_matrix import to_dict  # noqa: E402
 

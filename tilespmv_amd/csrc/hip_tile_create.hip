@@ -445,7 +445,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
         D->hyb_off = d_off64;
     }
     T.dnssize = (int)h_totals[5]; T.dnsrowsize = (int)h_totals[6]; T.dnscolsize = (int)h_totals[7]; T.coototal = (int)h_totals[11];
-    X.n_dnsrow = (long long)h_totals[8]; X.n_dnscol = (long long)h_totals[9];
+    X.n_dnsrow = (long long)h_totals[8]; X.n_dnscol = (long long)h_totals[9]; X.hyb_idx_bytes = (long long)h_totals[13];
     D->ms_select = now_ms() - t0; t0 = now_ms();
     pool_end();
 
@@ -560,7 +560,7 @@ int devtile_download(const DevTile *D, Tile_matrix *H)
     };
     TileExtents X; X.rowA = D->rowA;
     for_each_tile_field(*H, X, TF_LIST | TF_TILE, get);   // the per-tile arrays first: two of them say how long the id arrays are
-    if (T.tilenum) { X.n_dnsrow = H->dnsrowptr[T.tilenum]; X.n_dnscol = H->dnscolptr[T.tilenum]; }
+    if (T.tilenum) { X.n_dnsrow = H->dnsrowptr[T.tilenum]; X.n_dnscol = H->dnscolptr[T.tilenum]; X.hyb_idx_bytes = hyb_idx_bytes(*H, D->rowA); }
     for_each_tile_field(*H, X, TF_PAYLOAD, get);
     if (D->have_deferred) {
         for_each_tile_field(*H, X, TF_EXTRACTED, get);

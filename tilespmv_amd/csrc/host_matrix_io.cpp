@@ -52,7 +52,7 @@ extern "C" int tilespmv_matrix_save(const Tile_matrix *matrix, int rowA, int col
     sum[1] = fnv1a(head, sizeof(head), sum[1]);
     for (int i = 0; i < N_TILE_SCALARS; i++) sum[1] = fnv1a(&tile_scalar(*T, i), sizeof(int), sum[1]);
     sum[1] = fnv1a(extra, sizeof(extra), sum[1]);
-    const TileExtents X{rowA, extra[0], extra[1]};
+    const TileExtents X{rowA, extra[0], extra[1], T->tilenum > 0 ? tilespmv::hyb_idx_bytes(*T, rowA) : 0};
     for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) {
         if (fd.count > 0) { sum[0] += (unsigned long long)fd.count * fd.elem; sum[1] = fnv1a(*fd.ptr, (size_t)fd.count * fd.elem, sum[1]); }
     });
@@ -84,22 +84,37 @@ extern "C" int tilespmv_matrix_load(Tile_matrix *matrix, int *rowA, int *colA, M
     bool sane = head[1] >= 0 && head[2] >= 0 && head[3] >= 0 && extra[0] >= 0 && extra[1] >= 0;
     for (int i = 0; i < N_TILE_SCALARS && sane; i++) sane = tile_scalar(*T, i) >= 0;
     sane = sane && T->tilem == (head[1] + 15) / 16 && T->tilen == (head[2] + 15) / 16 && T->hybsize == T->hybellsize + T->hybcoosize;
-    unsigned long long bytes = 0;
-    const TileExtents X{head[1], extra[0], extra[1]};
-    if (sane) for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) { bytes += (unsigned long long)std::max<long long>(fd.count, 0) * fd.elem; });
+    // ---- the tile list and the per-tile arrays first: hybIdx's length is computed from them (tile_fields.h hyb_idx_bytes), and the file's length is checked at every step
     const long here = ftell(f);
-    sane = sane && bytes == sum[0] && fseek(f, 0, SEEK_END) == 0 && (unsigned long long)(ftell(f) - here) == bytes && fseek(f, here, SEEK_SET) == 0;
+    sane = sane && fseek(f, 0, SEEK_END) == 0;
+    const unsigned long long in_file = sane ? (unsigned long long)(ftell(f) - here) : 0;
+    sane = sane && fseek(f, here, SEEK_SET) == 0;
+    TileExtents X{head[1], extra[0], extra[1], 0};
+    unsigned long long bytes = 0;
+    auto measure = [&](const TileField &fd) { bytes += (unsigned long long)std::max<long long>(fd.count, 0) * fd.elem; };
+    if (sane) for_each_tile_field(*T, X, tilespmv::TF_LIST | tilespmv::TF_TILE, measure);
+    sane = sane && bytes <= sum[0] && sum[0] == in_file;
     if (!sane) { fclose(f); memset(matrix, 0, sizeof(*matrix)); return -6; }   // corrupt, truncated or stale cache
     unsigned long long h = 0xCBF29CE484222325ull;
     h = fnv1a(head, sizeof(head), h);
     for (int i = 0; i < N_TILE_SCALARS; i++) h = fnv1a(&tile_scalar(*matrix, i), sizeof(int), h);
     h = fnv1a(extra, sizeof(extra), h);
-    for_each_tile_field(*T, X, TF_ALL, [&](const TileField &fd) {
+    auto read = [&](const TileField &fd) {
         if (!ok) return;
         *fd.ptr = calloc((size_t)std::max<long long>(fd.count, 1), fd.elem);
         ok = *fd.ptr && (fd.count <= 0 || fread(*fd.ptr, fd.elem, (size_t)fd.count, f) == (size_t)fd.count);
         if (ok && fd.count > 0) h = fnv1a(*fd.ptr, (size_t)fd.count * fd.elem, h);
-    });
+    };
+    for_each_tile_field(*T, X, tilespmv::TF_LIST | tilespmv::TF_TILE, read);
+    if (ok) {   // (what hyb_idx_bytes indexes with is checked before it runs: the tile list, and hyb_coocount)
+        const long long n = T->tilenum;
+        sane = monotone(T->tile_ptr, (long long)T->tilem + 1, n) && monotone(T->hyb_coocount, n + 1, T->hybcoosize);
+        if (sane) X.hyb_idx_bytes = tilespmv::hyb_idx_bytes(*T, head[1]);
+        if (sane) for_each_tile_field(*T, X, tilespmv::TF_PAYLOAD | tilespmv::TF_EXTRACTED, measure);
+        sane = sane && bytes == sum[0];
+        if (!sane) { fclose(f); Tile_destroy(matrix); return -6; }
+        for_each_tile_field(*T, X, tilespmv::TF_PAYLOAD | tilespmv::TF_EXTRACTED, read);
+    }
     fclose(f);
     if (!ok) { Tile_destroy(matrix); return -3; }
     // ---- payload intact, and the prefix arrays that everything else indexes with are consistent

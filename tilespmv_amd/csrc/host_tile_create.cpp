@@ -178,7 +178,7 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
 
     lap("scans");
     // ---- payload arrays
-    X.n_dnsrow = T->dnsrowptr[tilenum]; X.n_dnscol = T->dnscolptr[tilenum];
+    X.n_dnsrow = T->dnsrowptr[tilenum]; X.n_dnscol = T->dnscolptr[tilenum]; X.hyb_idx_bytes = hyb_bytes[tilenum];
     for_each_tile_field(*T, X, TF_PAYLOAD | TF_EXTRACTED, zalloc_tile_field);   // (zeroed: hybIdx's nibbles are OR-ed in)
 
     uint8_t *csr_col = zalloc<uint8_t>(T->csrsize), *ell_col = zalloc<uint8_t>(T->ellsize);   // one byte per slot, packed into nibbles below

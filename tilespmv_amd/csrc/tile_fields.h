@@ -23,7 +23,21 @@ inline void copy_tile_scalars(Tile_matrix &dst, const Tile_matrix &src)
 enum : unsigned { TF_LIST = 1u, TF_TILE = 2u, TF_PAYLOAD = 4u, TF_EXTRACTED = 8u, TF_ALL = 15u };
 
 // what the scalar members do not say
-struct TileExtents { long long rowA = 0, n_dnsrow = 0, n_dnscol = 0; };   // rows of the matrix; dnsrowptr[tilenum]; dnscolptr[tilenum]
+struct TileExtents { long long rowA = 0, n_dnsrow = 0, n_dnscol = 0, hyb_idx_bytes = 0; };   // rows of the matrix; dnsrowptr[tilenum]; dnscolptr[tilenum]; bytes of hybIdx
+
+// Bytes of hybIdx: every HYB tile has whole bytes of its own (tile_pack.h) — its ELL part in nibbles, rounded up to a byte, then one byte per remainder entry.  A builder has
+// this total from its scan of the per-tile byte counts; whoever holds a finished matrix (cache file, download) recomputes it here from the per-tile arrays.  It equals
+// (hybellsize + 1) / 2 + hybcoosize unless the partial last tile-row holds HYB tiles of odd width and odd height: each of those costs half a byte more.
+inline long long hyb_idx_bytes(const Tile_matrix &T, long long rowA)
+{
+    long long bytes = 0;
+    for (int bi = 0; bi < T.tilem; bi++) {
+        const int rowlen = tile_rowlen(bi, T.tilem, (int)rowA);
+        for (int t = T.tile_ptr[bi]; t < T.tile_ptr[bi + 1]; t++)
+            if (T.Format[t] == TILESPMV_FMT_HYB) bytes += ((int)T.tilewidth[t] * rowlen + 1) / 2 + (T.hyb_coocount[t + 1] - T.hyb_coocount[t]);
+    }
+    return bytes;
+}
 
 // `count` elements are the array (what is saved, loaded and compared); an allocation or a download takes count + slack, a device allocation dev_slack more on top.
 struct TileField { void **ptr; size_t elem; long long count, slack, dev_slack; unsigned group; };
@@ -48,7 +62,7 @@ inline void for_each_tile_field(Tile_matrix &T, const TileExtents &X, unsigned g
         TF(Blockcoo_Val, sv, T.coosize, 0, 0, TF_PAYLOAD), TF(coo_compressed_Idx, 1, T.coosize, 0, 0, TF_PAYLOAD),
         TF(Blockell_Val, sv, T.ellsize, 0, 0, TF_PAYLOAD), TF(ell_compressedIdx, 1, ((long long)T.ellsize + 1) / 2, 0, 0, TF_PAYLOAD),
         TF(Blockhyb_Val, sv, hyb, 0, 1, TF_PAYLOAD),
-        TF(hybIdx, 1, ((long long)T.hybellsize + 1) / 2 + T.hybcoosize, (long long)T.tilem + 8, 0, TF_PAYLOAD),   // (the slack both builders have always given it; ADVICE.md has an open finding on this size)
+        TF(hybIdx, 1, X.hyb_idx_bytes, (long long)T.tilem + 8, 0, TF_PAYLOAD),   // (the slack both builders have always given it; nothing relies on it)
         TF(Blockdense_Val, sv, T.dnssize, 0, 0, TF_PAYLOAD),
         TF(Blockdenserow_Val, sv, T.dnsrowsize, 0, 0, TF_PAYLOAD), TF(denserowid, 1, X.n_dnsrow, 0, 0, TF_PAYLOAD),
         TF(Blockdensecol_Val, sv, T.dnscolsize, 0, 0, TF_PAYLOAD), TF(densecolid, 1, X.n_dnscol, 0, 0, TF_PAYLOAD),

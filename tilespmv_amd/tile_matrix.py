@@ -51,6 +51,21 @@ SCALARS = ["tilem", "tilen", "tilenum", "csrsize", "csrptrlen", "coosize", "ells
 _NP = {"i": np.int32, "b": np.uint8, "s": np.int8}
 
 
+def hyb_idx_bytes(tm, rowA):
+    """Bytes of ``hybIdx``: every HYB tile has whole bytes of its own — its ELL part in nibbles, rounded up to a byte, then one byte per remainder
+    entry (csrc/tile_fields.h).  Differs from ``(hybellsize + 1) // 2 + hybcoosize`` only when the partial last tile-row holds HYB tiles of odd width."""
+    n = tm.tilenum
+    if n <= 0 or tm.hybsize == 0:
+        return 0
+    fmt = field_array(tm, "Format", n)
+    hyb = np.flatnonzero(fmt == 3)
+    width = field_array(tm, "tilewidth", n).astype(np.int64)[hyb]
+    coo = np.diff(field_array(tm, "hyb_coocount", n + 1).astype(np.int64))[hyb]
+    last = field_array(tm, "tile_ptr", tm.tilem + 1)[tm.tilem - 1]          # first tile of the last tile-row
+    rowlen = np.where(hyb >= last, rowA - 16 * (tm.tilem - 1), 16)
+    return int(((width * rowlen + 1) // 2 + coo).sum())
+
+
 def field_lengths(tm, rowA):
     """Element count of every member array of a created Tile_matrix."""
     n = tm.tilenum
@@ -66,7 +81,7 @@ def field_lengths(tm, rowA):
         "Blockcoo_Val": tm.coosize, "coo_compressed_Idx": tm.coosize,
         "Blockell_Val": tm.ellsize, "ell_compressedIdx": (tm.ellsize + 1) // 2,
         "Blockhyb_Val": tm.hybellsize + tm.hybcoosize,
-        "hybIdx": (tm.hybellsize + 1) // 2 + tm.hybcoosize,
+        "hybIdx": hyb_idx_bytes(tm, rowA),
         "Blockdense_Val": tm.dnssize,
         "Blockdenserow_Val": tm.dnsrowsize, "denserowid": last(tm.dnsrowptr),
         "Blockdensecol_Val": tm.dnscolsize, "densecolid": last(tm.dnscolptr),
