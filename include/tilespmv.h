@@ -712,6 +712,55 @@ int tilespmv_cgls_solve(tilespmv_cgls *ls, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE
 int tilespmv_csr_row_sqnorms_device(int rows, const MAT_PTR_TYPE *d_rowPtr, const int *d_src /* may be NULL */, const MAT_VAL_TYPE *d_val, MAT_VAL_TYPE *d_out, int invert,
                                     void *stream);
 
+/* ---- Nonsymmetric systems in the library: BiCGStab around a resident plan (new).  A x = b for a square A that need be neither symmetric nor
+ * definite, right-preconditioned by M^-1 = diag(d_dinv) (Jacobi: tilespmv_csr_diagonal_device(..., invert = 1) makes it; d_dinv = NULL: phat = p, shat = s).  The contract is that
+ * of tilespmv_cg_*, word for word, wherever it can be; the state is tilespmv_cg_state and the statuses are TILESPMV_CG_*.
+ *   begin     r = b - A x;  rhat = r;  p = r;  rho = rhat.r;  rr = r.r;  bb = b.b;  iteration count and breakdown flag cleared
+ *   iterate   phat = dinv o p;  v = A phat;  sigma = rhat.v;  alpha = rho / sigma;  s = r - alpha v;  shat = dinv o s;  t = A shat;  omega = (t.s) / (t.t);
+ *             x += alpha phat + omega shat;  r = s - omega t;  rho' = rhat.r, rr = r.r;  beta = (rho' / rho)(alpha / omega);  p = r + beta (p - omega v)
+ * All vectors live in the value type; every dot product and every scalar is double in both libraries; alpha, omega and beta are formed in double and rounded to the value type
+ * once, where they multiply (the rule of tilespmv_cg_*).
+ * One iteration = the two plan products and FIVE streaming kernels (rhat.v;  the half step s, stored over r;  t.s and t.t;  the update of x and r with r.r and rhat.r;  the
+ * direction).  Every scalar lives in device memory with one writing kernel per field; a reducing kernel leaves one partial per workgroup and the consuming kernel folds them itself,
+ * every workgroup in the same order: no atomics, no finishing launch, no host read.  The number of partials depends on `rows` alone: on a plan whose y is bit-reproducible
+ * (TILESPMV_INFO_ENTRY_ORDERED = 1, e.g. deterministic = 1) the iterates x_k are too, run after run and plan after plan.
+ * Vector elements read or written per iteration beside the two products, by count: 18 per row (2 + 3 + 2 + 7 + 4 over the five kernels), 23 per row with Jacobi (d_dinv read and
+ * shat stored in the half step, shat read in the update, d_dinv read and phat stored in the direction).  The loop of torch operations it replaces
+ * (tilespmv_amd.operator.bicgstab) moves 28 per row (34 with Jacobi) in about twenty launches (scripts/bicgstab_time.py measures both).  Workspace: 5 vectors of rows + 16 elements (r, rhat, p, v, t;
+ * s lives in r), 7 with Jacobi (phat, shat), and 49 KB of partial sums and scalars, in one hipMalloc.
+ * Guards, taken on the device, exact-zero tests only, in the style of the CG guards:
+ *   rr = 0 at the start of an iteration, or the breakdown flag set   alpha = omega = beta = 0: the iteration writes no vector, x, r and p do not change by a bit — a captured
+ *                                                                    graph of k iterations may overrun convergence.
+ *   rr > 0, and rho = 0 or sigma = 0                                 the breakdown flag is set; alpha = omega = beta = 0 in that and every later iteration, x keeps its last good value.
+ *   t.t = 0 (or t.s = 0: omega would be 0 all the same)              omega = 0:  x += alpha phat,  r = s,  p is left as it is.  If rr is then 0 this is convergence at the half step
+ *                                                                    (A = 2 I ends this way after one iteration); if rr > 0 the breakdown flag is set (omega = 0 with a live residual).
+ *   The iteration counter advances in every iteration whatever the guards did: a breakdown seen at the first check of solve(check_every = 8) reports 8 iterations.
+ * A tilespmv_bicgstab and its plan run on ONE stream at a time.  d_b, d_x and d_dinv are DEVICE vectors of `rows` elements, 16-byte aligned (hipErrorInvalidValue otherwise);
+ * nothing behind element rows - 1 is read or written.
+ *
+ *   tilespmv_bicgstab_create      binds a workspace to `plan`, which must be square and whole (tilerow_begin = 0, tilerow_end = tilem; a square TILESPMV_CREATE_TRANSPOSE plan
+ *                                 qualifies: it solves A^T x = b) and must outlive it; the plan is borrowed.  d_dinv: NULL, or the inverse diagonal, borrowed until destroy — its VALUES
+ *                                 may change between solves (tilespmv_plan_update_values, then tilespmv_csr_diagonal_device into the same array).  One hipMalloc (synchronises).
+ *                                 Returns 0, hipErrorInvalidValue (a NULL argument: no HIP call made; a non-square or shard plan, a misaligned d_dinv: nothing allocated), or the
+ *                                 hipMalloc error.
+ *   tilespmv_bicgstab_begin       as above, from the caller's x (pass zeros for none).
+ *   tilespmv_bicgstab_iterate     `count` iterations back to back.  Like begin: asynchronous on `stream`, no allocation, no synchronisation, no host read, one linear chain of
+ *                                 kernels — safe to capture into a hipGraph, for every kind of plan.  It stops at no tolerance.
+ *   tilespmv_bicgstab_state_read  synchronises `stream` and fills the state (set out->size = sizeof(tilespmv_cg_state) first).  status: BREAKDOWN, else CONVERGED when rr is exactly
+ *                                 0, else RUNNING.  rr is the recurrence's |r|^2, not a recomputed |b - A x|^2; BiCGStab's residual norm is not monotone.
+ *   tilespmv_bicgstab_solve       begin, then iterate(check_every) + state_read until sqrt(rr / bb) <= rtol (CONVERGED), `maxiter` iterations are done (MAXITER; the last block is cut
+ *                                 so that no more run) or a breakdown (BREAKDOWN).  bb = 0 -> x = 0, CONVERGED, 0 iterations.  check_every < 1 -> 1.  One host synchronisation per
+ *                                 check; the residual is not looked at at the half step.
+ * All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_bicgstab tilespmv_bicgstab;
+int tilespmv_bicgstab_create(tilespmv_bicgstab **s, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv /* may be NULL */);
+void tilespmv_bicgstab_destroy(tilespmv_bicgstab *s);
+int tilespmv_bicgstab_begin(tilespmv_bicgstab *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream);
+int tilespmv_bicgstab_iterate(tilespmv_bicgstab *s, MAT_VAL_TYPE *d_x, int count, void *stream);
+int tilespmv_bicgstab_state_read(tilespmv_bicgstab *s, void *stream, tilespmv_cg_state *out);
+int tilespmv_bicgstab_solve(tilespmv_bicgstab *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
+                            tilespmv_cg_state *out);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

@@ -616,6 +616,46 @@ class CGLS(_Solver):
         return self._state(st)
 
 
+class BiCGStab(_Solver):
+    """``tilespmv_bicgstab``: BiCGStab for a square, nonsymmetric A around a resident plan, right-preconditioned by a diagonal, every scalar on the device (include/tilespmv.h,
+    DESIGN.md §3.10).  It mirrors ``CG``: the same state dict, the same statuses.
+
+    ``plan``: square and whole (a square ``transpose=True`` plan solves ``A^T x = b``); it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal
+    (Jacobi: ``csr_diagonal_device(..., invert=True)``; borrowed), or None.  ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run
+    on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+
+    _destroy = "tilespmv_bicgstab_destroy"
+    _hint = "the plan must be square and whole; vectors 16-byte aligned"
+
+    def __init__(self, plan, d_dinv=None):
+        self.lib, self.plan = plan.lib, plan
+        h = C.c_void_p()
+        rc = self.lib.tilespmv_bicgstab_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None))
+        self._check(rc, "tilespmv_bicgstab_create")
+        self.h = h
+
+    def begin(self, d_b, d_x, stream=0):
+        """r = b - A x, rhat = p = r; asynchronous."""
+        self._check(self.lib.tilespmv_bicgstab_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)), "tilespmv_bicgstab_begin")
+
+    def iterate(self, d_x, count=1, stream=0):
+        """``count`` iterations; asynchronous, capturable into a graph."""
+        self._check(self.lib.tilespmv_bicgstab_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_bicgstab_iterate")
+
+    def state(self, stream=0):
+        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
+        st = _lib.CGState()
+        self._check(self.lib.tilespmv_bicgstab_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_bicgstab_state_read")
+        return CG._state(st)
+
+    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
+        """``tilespmv_bicgstab_solve``; returns the final state (as ``state``)."""
+        st = _lib.CGState()
+        self._check(self.lib.tilespmv_bicgstab_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
+                    "tilespmv_bicgstab_solve")
+        return CG._state(st)
+
+
 def algorithmic_bytes(nnz, rows, cols, itemsize):
     """B_alg = nnz*(s_v+4) + 4*(m+1) + s_v*(n+m)."""
     return nnz * (itemsize + 4) + 4 * (rows + 1) + itemsize * (cols + rows)

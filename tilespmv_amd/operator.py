@@ -8,6 +8,8 @@
     x, info = cgls(op, b)                                            # ... the same as a loop of torch operations (the A/B baseline of scripts/cgls_time.py)
     x, info = op.cg(b)                                               # A x = b, A symmetric positive definite: the solver in the library
     X, infos = op.cg(B)                                              # B of shape (rows, k): k systems in lock-step around the multi-vector product
+    x, info = op.bicgstab(b)                                         # A x = b, A square and not symmetric: the solver in the library
+    x, info = bicgstab(op, b)                                        # ... the same as a loop of torch operations (the A/B baseline of scripts/bicgstab_time.py)
 
 The plan of A^T is a plan like any other (tuned kernels, form choice, ordered sums); there is no scatter form of A^T x.
 """
@@ -254,6 +256,36 @@ class SparseOperator:
                 "converged": s["status"] == api.CG_CONVERGED, "status": s["status_name"]}
         return x, info
 
+    def bicgstab(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None):
+        """A x = b for a square A that need not be symmetric, by BiCGStab in the library (``api.BiCGStab`` over the plan of A) — the two products and five fused
+        kernels per iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a contiguous torch CUDA vector of ``rows`` elements;
+        ``dinv``: the inverse diagonal as a CUDA vector (Jacobi, applied from the right; ``api.csr_diagonal_device(..., invert=True)`` makes it), None = unpreconditioned.  Stops at
+        ``sqrt(rr / bb) <= rtol``, after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.  Returns ``(x, info)`` with ``info = {"iterations", "residual",
+        "relative_residual", "converged", "status"}`` (``residual``: the recurrence's ``|r|``)."""
+        import torch
+        rows, cols = self.shape
+        if rows != cols:
+            raise ValueError("bicgstab needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
+        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
+            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
+        if dinv is not None and (not _is_tensor(dinv) or dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
+            raise ValueError("dinv must be a contiguous vector of %d elements of b's type" % rows)
+        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != rows or x0.dtype != b.dtype):
+            raise ValueError("x0 must be a vector of %d elements of b's type" % rows)
+        maxiter = 2 * rows if maxiter is None else maxiter
+        x = torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+        if x0 is not None:
+            x.copy_(x0)
+        st = _stream(stream)
+        solver = api.BiCGStab(self.A, None if dinv is None else dinv.data_ptr())
+        try:
+            s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
+        finally:
+            solver.close()
+        info = {"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
+                "status": s["status_name"]}
+        return x, info
+
     def close(self):
         for p in (getattr(self, "A", None), getattr(self, "AT", None)):
             if p is not None:
@@ -264,6 +296,52 @@ class SparseOperator:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def bicgstab(op, b, x0=None, tol=1e-10, maxiter=None, dinv=None, check_every=1):
+    """``A x = b`` for a square operator by right-preconditioned BiCGStab as a loop of torch operations: the recurrences of ``SparseOperator.bicgstab``, without
+    its guards — the baseline of scripts/bicgstab_time.py and a second opinion in tests.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: None or the inverse diagonal.
+    Stops when ``|r| <= tol * |b|`` for the recurrence's r (checked every ``check_every`` iterations: each check is one host sync) or after ``maxiter`` iterations (default
+    ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged"}`` (``residual``: a recomputed ``|b - A x|``)."""
+    import torch
+    rows, cols = op.shape
+    if rows != cols:
+        raise ValueError("bicgstab needs a square operator; this one is %d x %d" % (rows, cols))
+    if b.numel() != rows:
+        raise ValueError("b must have %d elements" % rows)
+    maxiter = 2 * rows if maxiter is None else maxiter
+    x = torch.zeros(rows, dtype=b.dtype, device=b.device) if x0 is None else x0.clone()
+    r = b.clone()
+    if x0 is not None:
+        r -= op.matvec(x)
+    rhat, p = r.clone(), r.clone()
+    rho = torch.dot(rhat, r)
+    rr = rho.clone()
+    norm_b = float(torch.linalg.vector_norm(b))
+    v = torch.empty(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+    t = torch.empty(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+    it, converged = 0, float(rr.sqrt()) <= tol * norm_b
+    while not converged and it < maxiter:
+        phat = p if dinv is None else dinv * p
+        op.matvec(phat, v)
+        alpha = rho / torch.dot(rhat, v)
+        r.addcmul_(v, -alpha)                       # s, over r
+        shat = r if dinv is None else dinv * r
+        op.matvec(shat, t)
+        omega = torch.dot(t, r) / torch.dot(t, t)
+        x.addcmul_(phat, alpha).addcmul_(shat, omega)
+        r.addcmul_(t, -omega)
+        rho_new = torch.dot(rhat, r)
+        rr = torch.dot(r, r)
+        beta = (rho_new / rho) * (alpha / omega)
+        p.addcmul_(v, -omega).mul_(beta).add_(r)
+        rho = rho_new
+        it += 1
+        if it % check_every == 0 or it == maxiter:
+            converged = float(rr.sqrt()) <= tol * norm_b
+    res = float(torch.linalg.vector_norm(b - op.matvec(x)))
+    info = {"iterations": it, "residual": res, "relative_residual": res / norm_b if norm_b > 0 else 0.0, "converged": bool(converged)}
+    return x, info
 
 
 def cgls(op, b, x0=None, tol=1e-12, maxiter=None, check_every=1):
