@@ -15,7 +15,7 @@ namespace prims {
 constexpr int SCAN_THREADS = 256, SCAN_PER_THREAD = 8, SCAN_TILE = SCAN_THREADS * SCAN_PER_THREAD;
 
 template <bool APPLY>
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_tiles(const int *__restrict__ in, int *__restrict__ out, int *__restrict__ sums, size_t n)
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_tiles(const int *in, int *out, int *__restrict__ sums, size_t n)
 {
     __shared__ int s_wave[SCAN_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
