@@ -366,7 +366,12 @@ const char *tilespmv_plan_options_layout(void);
  * x / y of its own: plans of >= 1 GB try up to `placement_tries` memory placements, shards with column panels recorded choose the panels per pass, opt-in paced plans
  * calibrate their timetable.  Every such choice has a knob that fixes it (placement_tries = 1, x_panel_merge + x_slice_passes, pace_period_us) — a fixed choice times nothing;
  * `deterministic = 1` fixes them all.  Since round 5 the value stream's final layout is written by a kernel (the emitted values are uploaded to a scratch buffer first): peak device
- * memory during creation = the plan + one more copy of its unit values (freed before the call returns); TILESPMV_ENCODE_ON_HOST=1 keeps that pass on the host. */
+ * memory during creation = the plan + one more copy of its unit values (freed before the call returns); TILESPMV_ENCODE_ON_HOST=1 keeps that pass on the host.
+ * Dimension limits: every `int` rowA / colA is either served or refused with a status — Tile_create, tilespmv_cpu and the matrix cache serve all of them (tile counts are
+ * computed without overflow up to 2^31 - 1).  The unit-stream kernel (TILESPMV_KERNEL_STREAM) keeps column blocks in 24 bits: colA <= 2^28.  Beyond that TILESPMV_KERNEL_AUTO
+ * takes the first-generation kernel (with TILESPMV_COO_IN_TILE or the CSR fallback; 64-bit x offsets, served up to colA = 2^31 - 1), an explicit TILESPMV_KERNEL_STREAM
+ * returns -2 with a message on stderr, and the device builders (tilespmv_plan_create_from_csr / _from_device_csr) return -4 like for every option without a device path.
+ * -2 is also the status of a shard whose unit, entry or tile ids leave the int32 range.  (tests/test_gpu_dim_limits.py runs both sides of each limit.) */
 int tilespmv_plan_create(tilespmv_plan **plan, const Tile_matrix *matrix, int rowA, int colA,
                          MAT_PTR_TYPE nnzA, const tilespmv_plan_options *opts);
 void tilespmv_plan_destroy(tilespmv_plan *plan);

@@ -157,7 +157,7 @@ void oracle_Tile_create(Tile_matrix *T, int rowA, int colA, MAT_PTR_TYPE nnzA,
 {
     (void)nnzA;
     memset(T, 0, sizeof *T);
-    const int tilem = (rowA + BS - 1) / BS, tilen = (colA + BS - 1) / BS; /* :641-642 */
+    const int tilem = rowA / BS + (rowA % BS != 0), tilen = colA / BS + (colA % BS != 0); /* :641-642; (d + BS - 1) / BS overflows near INT_MAX */
     T->tilem = tilem; T->tilen = tilen;
     T->tile_ptr = zalloc((size_t)tilem + 1, sizeof(int));
 

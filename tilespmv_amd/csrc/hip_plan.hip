@@ -851,7 +851,7 @@ static int plan_from_csr(tilespmv_plan **out, int rowA, int colA, MAT_PTR_TYPE n
     // TILESPMV_CREATE_TRANSPOSE: the plan of A^T (colA x rowA); the arguments describe A, so the shape is swapped first and every rule below sees the transposed one
     const bool transpose = (create_flags & TILESPMV_CREATE_TRANSPOSE) != 0;
     if (transpose) std::swap(rowA, colA);
-    const int tilen = (colA + BS - 1) / BS;
+    const int tilen = tiles_of(colA);
     // what has no device path (include/tilespmv.h): the caller builds those plans from a host Tile_matrix
     if (K.dry || K.kernel == TILESPMV_KERNEL_DIRECT || tilen > (1 << UNIT_FLAG_SHIFT) || K.coo_mode == TILESPMV_COO_FALLBACK || K.csr_split == 0)
         return -4;

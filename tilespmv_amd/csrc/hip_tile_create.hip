@@ -287,7 +287,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     const bool verbose = getenv("TILESPMV_CREATE_VERBOSE") != nullptr, cdna4 = flags & TILESPMV_CREATE_CDNA4, allow_hyb = flags & TILESPMV_CREATE_HYB;
     pool_end();   // (no pool left over from a build that failed on this thread)
     Tile_matrix &T = D->T;
-    const int tilem = (rowA + BS - 1) / BS, tilen = (colA + BS - 1) / BS;
+    const int tilem = tiles_of(rowA), tilen = tiles_of(colA);
     // the row pointer may be a slice of a larger matrix's (a row block: pointers not rebased): the block's nonzeros are [base, base + nnz) of the column / value arrays
     long long base = 0, nnz = 0;
     if (csr_on_device) {   // (device CSR: based at 0 by contract; its last row pointer is the one number fetched)

@@ -83,7 +83,7 @@ extern "C" int tilespmv_matrix_load(Tile_matrix *matrix, int *rowA, int *colA, M
     Tile_matrix *T = matrix;
     bool sane = head[1] >= 0 && head[2] >= 0 && head[3] >= 0 && extra[0] >= 0 && extra[1] >= 0;
     for (int i = 0; i < N_TILE_SCALARS && sane; i++) sane = tile_scalar(*T, i) >= 0;
-    sane = sane && T->tilem == (head[1] + 15) / 16 && T->tilen == (head[2] + 15) / 16 && T->hybsize == T->hybellsize + T->hybcoosize;
+    sane = sane && T->tilem == tilespmv::tiles_of(head[1]) && T->tilen == tilespmv::tiles_of(head[2]) && T->hybsize == T->hybellsize + T->hybcoosize;
     // ---- the tile list and the per-tile arrays first: hybIdx's length is computed from them (tile_fields.h hyb_idx_bytes), and the file's length is checked at every step
     const long here = ftell(f);
     sane = sane && fseek(f, 0, SEEK_END) == 0;

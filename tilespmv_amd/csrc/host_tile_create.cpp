@@ -22,9 +22,16 @@
 namespace tilespmv {
 namespace {
 
-struct RowScratch {
-    std::vector<int> stamp, local, touched, cursor;
-    explicit RowScratch(int tilen) : stamp((size_t)tilen, -1), local((size_t)tilen, 0) {}
+struct RowScratch {   // stamp / local: one int per column block, zeroed by calloc — a page nobody stamps is never touched (2^27 column blocks: 1 GB per thread otherwise; plain
+    int *stamp, *local;   // calloc, not zalloc: with huge pages advised every stamped block of a hypersparse row would fault 2 MB in)
+    std::vector<int> touched, cursor;
+    explicit RowScratch(int tilen) : stamp((int *)calloc((size_t)std::max(tilen, 1), sizeof(int))), local((int *)calloc((size_t)std::max(tilen, 1), sizeof(int)))
+    {
+        if (!stamp || !local) { fprintf(stderr, "tilespmv: out of host memory (2 x %d ints of Tile_create scratch)\n", tilen); exit(2); }
+    }
+    ~RowScratch() { free(stamp); free(local); }
+    RowScratch(const RowScratch &) = delete;
+    RowScratch &operator=(const RowScratch &) = delete;
 };
 
 void pack_nibble_stream(const uint8_t *src, uint8_t *dst, int64_t n)
@@ -64,7 +71,7 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
     double tprev = now_ms();
     auto lap = [&](const char *what) { if (!tverbose) return; const double now = now_ms(); fprintf(stderr, "tilespmv: Tile_create %s %.1f ms\n", what, now - tprev); tprev = now; };
     const bool allow_hyb = flags & TILESPMV_CREATE_HYB, cdna4 = flags & TILESPMV_CREATE_CDNA4;
-    const int tilem = (rowA + BS - 1) / BS, tilen = (colA + BS - 1) / BS;
+    const int tilem = tiles_of(rowA), tilen = tiles_of(colA);
     T->tilem = tilem; T->tilen = tilen;
     T->tile_ptr = zalloc<int>((size_t)tilem + 1);
     const int nthreads = host_threads();
@@ -75,11 +82,11 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
     parallel_chunks(tilem, 512, [&](int64_t b, int64_t e, int tid) {
         RowScratch *S = get_scratch(tid);
         for (int bi = (int)b; bi < (int)e; bi++) {
-            const int r0 = bi * BS, r1 = std::min(rowA, r0 + BS);
+            const int r0 = bi * BS, r1 = r0 + tile_rowlen(bi, tilem, rowA);
             int n = 0;
             for (int j = rowptr[r0]; j < rowptr[r1]; j++) {
                 int cb = colidx[j] >> 4;
-                if (S->stamp[cb] != bi) { S->stamp[cb] = bi; n++; }
+                if (S->stamp[cb] != bi + 1) { S->stamp[cb] = bi + 1; n++; }   // (stamps start at 1: 0 is "never seen")
             }
             T->tile_ptr[bi] = n;
         }
@@ -104,9 +111,9 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
     parallel_chunks(tilem, 256, [&](int64_t b, int64_t e, int tid) {
         RowScratch *S = get_scratch(tid);
         for (int bi = (int)b; bi < (int)e; bi++) {
-            const int r0 = bi * BS, r1 = std::min(rowA, r0 + BS);
+            const int r0 = bi * BS, r1 = r0 + tile_rowlen(bi, tilem, rowA);
             const int t0 = T->tile_ptr[bi], nt = T->tile_ptr[bi + 1] - t0;
-            const int stampv = tilem + bi;  // distinct from pass 1's stamps
+            const int stampv = tilem + bi + 1;  // distinct from pass 1's stamps
             S->touched.clear();
             for (int j = rowptr[r0]; j < rowptr[r1]; j++) {
                 int cb = colidx[j] >> 4;

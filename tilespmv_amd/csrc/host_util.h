@@ -166,6 +166,8 @@ inline void free_later(std::vector<void *> ptrs)
     std::thread([ptrs]() { for (void *q : ptrs) free(q); }).detach();
 }
 
+// Tiles per dimension: ceil(d / BS) for every int d >= 0 ((d + BS - 1) / BS overflows from INT_MAX - 14 on)
+TILESPMV_HD inline int tiles_of(int d) { return d / BS + (d % BS != 0); }
 TILESPMV_HD inline int tile_rowlen(int bi, int tilem, int rowA) { return bi == tilem - 1 ? rowA - (tilem - 1) * BS : BS; }
 TILESPMV_HD inline int tile_collen(int cb, int tilen, int colA) { return cb == tilen - 1 ? colA - (tilen - 1) * BS : BS; }
 
