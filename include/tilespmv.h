@@ -766,6 +766,69 @@ int tilespmv_bicgstab_state_read(tilespmv_bicgstab *s, void *stream, tilespmv_cg
 int tilespmv_bicgstab_solve(tilespmv_bicgstab *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
                             tilespmv_cg_state *out);
 
+/* ---- Symmetric indefinite systems in the library: MINRES around a resident plan (new).  A x = b for a square SYMMETRIC A that need not be
+ * definite (saddle-point and KKT systems, on which CG breaks down), preconditioned by a POSITIVE diagonal M^-1 = diag(d_minv) (tilespmv_csr_abs_diagonal_device(..., invert = 1)
+ * makes one; d_minv = NULL: z = r2).  Preconditioned Paige-Saunders MINRES: one product per iteration, short recurrences, a residual norm that never increases, and no breakdown
+ * but the lucky one.  The contract is that of tilespmv_bicgstab_*, word for word, wherever it can be; the state is tilespmv_cg_state and the statuses are TILESPMV_CG_*.
+ *   begin     r2 = b - A x;  r1 = 0;  z = minv o r2;  beta = sqrt(r2.z);  bb = b.(minv o b);  oldb = dbar = epsln = 0;  phibar = beta;  cs = -1;  sn = 0;  w = w2 = 0;
+ *             rr = r2.z (= phibar^2; the sum itself, no square root in between);  iteration count and breakdown flag cleared
+ *   iterate   v = z / beta;  y = A v;  if oldb != 0: y -= (beta/oldb) r1;  alfa = v.y;  y -= (alfa/beta) r2;  z' = minv o y;  beta' = sqrt(y.z');
+ *             oldeps = epsln;  delta = cs dbar + sn alfa;  gbar = sn dbar - cs alfa;  gamma = hypot(gbar, beta');
+ *             r1 = r2;  r2 = y;  z = z';  oldb = beta;  beta = beta';  epsln = sn beta;  dbar = -cs beta;  cs = gbar/gamma;  sn = beta/gamma;  phi = cs phibar;  phibar = sn phibar;
+ *             w1 = w2;  w2 = w;  w = (v - oldeps w1 - delta w2) / gamma;  x += phi w;  rr = phibar^2
+ * All vectors live in the value type; every dot product and every scalar is double in both libraries; 1/beta, alfa/beta, beta/oldb, oldeps, delta, 1/gamma and phi are formed in
+ * double and rounded to the value type once, where they multiply (the rule of tilespmv_cg_*).  The library keeps z, not v: the product is taken of z and every consumer multiplies
+ * by the rounded 1/beta (y = (A z) / beta).
+ * WHAT rr AND bb ARE: without d_minv, rr is the recurrence's |r|^2 and bb is |b|^2; with d_minv, rr is r.M^-1 r and bb is b.M^-1 b — the norm MINRES minimises, and the one
+ * tilespmv_minres_solve's rtol applies to.  rr is never a recomputed |b - A x|^2.
+ * One iteration = the plan product and THREE streaming kernels (v.y;  the Lanczos step with the partial sums of beta'^2;  the rotation with the update of w, x and z).  Every
+ * scalar lives in device memory with one writing kernel per field; a reducing kernel leaves one partial per workgroup and the consuming kernel folds them itself, every workgroup in
+ * the same order: no atomics, no finishing launch, no host read.  The number of partials depends on `rows` alone: on a plan whose y is bit-reproducible
+ * (TILESPMV_INFO_ENTRY_ORDERED = 1, e.g. deterministic = 1) the iterates x_k are too, run after run and plan after plan.  The three-term history (r1 / r2, w / w2) is kept without
+ * copies and without exchanging pointers on the host: the kernels choose the roles of two buffers from the parity of the iteration counter on the DEVICE, so a captured
+ * iterate(k) may be replayed any number of times.
+ * Vector elements read or written per iteration beside the product, by count: 14 per row (2 + 4 + 8 over the three kernels), 16 per row with d_minv (read in the Lanczos step and
+ * in the update; z' is recomputed there, not stored and read back).  The loop of torch operations it replaces (tilespmv_amd.operator.minres, its scalars 0-d tensors on the device) moves
+ * 23 per row (26 with d_minv) in about thirty-five launches.  Measured, seconds per iteration against that loop on the same plan (scripts/minres_time.py,
+ * profiles/minres_fused_ab.txt): 0.631 -> 0.441 ms = 1.43 x on the 4096^2 Laplacian shifted by -I in fp64, 0.403 -> 0.254 ms = 1.59 x in fp32, 7.6 x on a launch-bound 512^2 grid.
+ * Workspace: 6 vectors of rows + 16 elements (y, z, two of r, two of w), with or without d_minv, and 16.25 KB of partial sums and scalars, in one hipMalloc.
+ * Guards, taken on the device, exact tests only, in the style of the CG guards:
+ *   phibar = 0 at the start of an iteration, or the breakdown flag set   the iteration writes no vector, x does not change by a bit (b = 0; beta' = 0, the lucky termination) — a
+ *                                                                        captured graph of k iterations may overrun convergence.
+ *   r2.z < 0 (begin) or y.z' < 0                                         M is not positive definite: the breakdown flag is set; that and every later iteration leave x alone, x
+ *                                                                        keeps its last good value (in begin: the caller's x0).
+ *   gamma = 0                                                            A is singular on this Krylov space and the system incompatible: breakdown, handled the same way.
+ *   The iteration counter advances in every iteration whatever the guards did: a breakdown seen at the first check of solve(check_every = 8) reports 8 iterations.
+ * A tilespmv_minres and its plan run on ONE stream at a time.  d_b, d_x and d_minv are DEVICE vectors of `rows` elements, 16-byte aligned (hipErrorInvalidValue otherwise);
+ * nothing behind element rows - 1 is read or written.
+ *
+ *   tilespmv_minres_create      binds a workspace to `plan`, which must be square and whole (tilerow_begin = 0, tilerow_end = tilem; a square TILESPMV_CREATE_TRANSPOSE plan
+ *                               qualifies) and must outlive it; the plan is borrowed.  That A is symmetric is the caller's word: it is not checked.  d_minv: NULL, or a positive
+ *                               diagonal, borrowed until destroy — its VALUES may change between solves (tilespmv_plan_update_values, then tilespmv_csr_abs_diagonal_device into the
+ *                               same array).  One hipMalloc (synchronises).  Returns 0, hipErrorInvalidValue (a NULL argument: no HIP call made; a non-square or shard plan, a
+ *                               misaligned d_minv: nothing allocated), or the hipMalloc error.
+ *   tilespmv_minres_begin       as above, from the caller's x (pass zeros for none).
+ *   tilespmv_minres_iterate     `count` iterations back to back.  Like begin: asynchronous on `stream`, no allocation, no synchronisation, no host read, one linear chain of
+ *                               kernels — safe to capture into a hipGraph, for every kind of plan.  It stops at no tolerance.
+ *   tilespmv_minres_state_read  synchronises `stream` and fills the state (set out->size = sizeof(tilespmv_cg_state) first).  status: BREAKDOWN, else CONVERGED when rr is exactly
+ *                               0, else RUNNING.
+ *   tilespmv_minres_solve       begin, then iterate(check_every) + state_read until rr <= rtol^2 bb (CONVERGED), `maxiter` iterations are done (MAXITER; the last block is cut so
+ *                               that no more run) or a breakdown (BREAKDOWN).  bb = 0 -> x = 0, CONVERGED, 0 iterations.  check_every < 1 -> 1.  One host synchronisation per check.
+ * All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_minres tilespmv_minres;
+int tilespmv_minres_create(tilespmv_minres **s, tilespmv_plan *plan, const MAT_VAL_TYPE *d_minv /* may be NULL */);
+void tilespmv_minres_destroy(tilespmv_minres *s);
+int tilespmv_minres_begin(tilespmv_minres *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream);
+int tilespmv_minres_iterate(tilespmv_minres *s, MAT_VAL_TYPE *d_x, int count, void *stream);
+int tilespmv_minres_state_read(tilespmv_minres *s, void *stream, tilespmv_cg_state *out);
+int tilespmv_minres_solve(tilespmv_minres *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
+                          tilespmv_cg_state *out);
+/* tilespmv_csr_diagonal_device with one difference: d_out[i] = the ABSOLUTE VALUE of the sum of the stored entries (i, i); invert != 0: 1 / |d|, and 1 where d is 0 — a positive
+ * d_minv for tilespmv_minres_create whatever the signs on the diagonal (a KKT matrix with a negative or zero (2,2) block).  One thread per row, asynchronous on `stream`,
+ * capturable.  Returns a hipError_t value (hipErrorInvalidValue for a NULL array, hipErrorNoDevice without a device). */
+int tilespmv_csr_abs_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, MAT_VAL_TYPE *d_out, int invert,
+                                     void *stream);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

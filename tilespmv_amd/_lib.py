@@ -228,6 +228,20 @@ def load(dtype=np.float64):
     lib.tilespmv_bicgstab_state_read.restype = C.c_int
     lib.tilespmv_bicgstab_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
     lib.tilespmv_bicgstab_solve.restype = C.c_int
+    lib.tilespmv_minres_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.tilespmv_minres_create.restype = C.c_int
+    lib.tilespmv_minres_destroy.argtypes = [C.c_void_p]
+    lib.tilespmv_minres_destroy.restype = None
+    lib.tilespmv_minres_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_minres_begin.restype = C.c_int
+    lib.tilespmv_minres_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_minres_iterate.restype = C.c_int
+    lib.tilespmv_minres_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
+    lib.tilespmv_minres_state_read.restype = C.c_int
+    lib.tilespmv_minres_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
+    lib.tilespmv_minres_solve.restype = C.c_int
+    lib.tilespmv_csr_abs_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_csr_abs_diagonal_device.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -258,4 +272,6 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_cgls_create", "tilespmv_cgls_destroy", "tilespmv_cgls_begin", "tilespmv_cgls_iterate", "tilespmv_cgls_state_read", "tilespmv_cgls_solve",
                     "tilespmv_csr_row_sqnorms_device",
                     "tilespmv_bicgstab_create", "tilespmv_bicgstab_destroy", "tilespmv_bicgstab_begin", "tilespmv_bicgstab_iterate", "tilespmv_bicgstab_state_read",
-                    "tilespmv_bicgstab_solve"]
+                    "tilespmv_bicgstab_solve",
+                    "tilespmv_minres_create", "tilespmv_minres_destroy", "tilespmv_minres_begin", "tilespmv_minres_iterate", "tilespmv_minres_state_read", "tilespmv_minres_solve",
+                    "tilespmv_csr_abs_diagonal_device"]

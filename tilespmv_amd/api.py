@@ -656,6 +656,55 @@ class BiCGStab(_Solver):
         return CG._state(st)
 
 
+def csr_abs_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dtype=np.float64):
+    """``tilespmv_csr_abs_diagonal_device``: ``csr_diagonal_device`` with the absolute value of the summed entries (i, i); ``invert=True``: ``1 / |d|``, 1 where d is 0 — a positive
+    ``d_minv`` for ``MINRES`` whatever the signs on the diagonal (a KKT matrix with a negative or zero (2,2) block).  Asynchronous on ``stream``."""
+    lib = _lib.load(dtype)
+    rc = lib.tilespmv_csr_abs_diagonal_device(rows, C.c_void_p(d_rp), C.c_void_p(d_ci), C.c_void_p(d_v), C.c_void_p(d_out), 1 if invert else 0, C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("tilespmv_csr_abs_diagonal_device failed (hipError %d): bad argument, or no usable device" % rc)
+
+
+class MINRES(_Solver):
+    """``tilespmv_minres``: MINRES for a square, symmetric A that may be indefinite (saddle-point and KKT systems) around a resident plan, preconditioned by a positive diagonal,
+    every scalar on the device (include/tilespmv.h).  It mirrors ``CG``: the same state dict, the same statuses.  One product per iteration; ``rr`` never increases.
+
+    ``plan``: square and whole; it must stay open while the solver is.  ``d_minv``: device ADDRESS of a POSITIVE diagonal M^-1 (``csr_abs_diagonal_device(..., invert=True)``;
+    borrowed), or None.  With it ``rr`` is ``r.M^-1 r`` and ``bb`` is ``b.M^-1 b``.  ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its
+    plan run on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+
+    _destroy = "tilespmv_minres_destroy"
+    _hint = "the plan must be square and whole; vectors 16-byte aligned"
+
+    def __init__(self, plan, d_minv=None):
+        self.lib, self.plan = plan.lib, plan
+        h = C.c_void_p()
+        rc = self.lib.tilespmv_minres_create(C.byref(h), plan.h, C.c_void_p(d_minv or None))
+        self._check(rc, "tilespmv_minres_create")
+        self.h = h
+
+    def begin(self, d_b, d_x, stream=0):
+        """r2 = b - A x, z = minv o r2, beta = sqrt(r2.z); asynchronous."""
+        self._check(self.lib.tilespmv_minres_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)), "tilespmv_minres_begin")
+
+    def iterate(self, d_x, count=1, stream=0):
+        """``count`` iterations; asynchronous, capturable into a graph."""
+        self._check(self.lib.tilespmv_minres_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_minres_iterate")
+
+    def state(self, stream=0):
+        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
+        st = _lib.CGState()
+        self._check(self.lib.tilespmv_minres_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_minres_state_read")
+        return CG._state(st)
+
+    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
+        """``tilespmv_minres_solve``; returns the final state (as ``state``)."""
+        st = _lib.CGState()
+        self._check(self.lib.tilespmv_minres_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
+                    "tilespmv_minres_solve")
+        return CG._state(st)
+
+
 def algorithmic_bytes(nnz, rows, cols, itemsize):
     """B_alg = nnz*(s_v+4) + 4*(m+1) + s_v*(n+m)."""
     return nnz * (itemsize + 4) + 4 * (rows + 1) + itemsize * (cols + rows)

@@ -1,4 +1,4 @@
-// hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip, hip_solver_bi.hip): the launch shape, the number of
+// hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip, hip_solver_bi.hip, hip_solver_mr.hip): the launch shape, the number of
 // partial sums, the reduction tree, the walk over a vector, and the host-side handling of the one allocation and of the versioned state structs.
 //
 // No scalar ever visits the host: a reducing kernel writes one partial per workgroup and the CONSUMING kernel folds the partials itself — every workgroup the same additions in the

@@ -10,6 +10,8 @@
     X, infos = op.cg(B)                                              # B of shape (rows, k): k systems in lock-step around the multi-vector product
     x, info = op.bicgstab(b)                                         # A x = b, A square and not symmetric: the solver in the library
     x, info = bicgstab(op, b)                                        # ... the same as a loop of torch operations (the A/B baseline of scripts/bicgstab_time.py)
+    x, info = op.minres(b)                                           # A x = b, A symmetric and indefinite (saddle point, KKT): the solver in the library
+    x, info = minres(op, b)                                          # ... the same as a loop of torch operations (the A/B baseline of scripts/minres_time.py)
 
 The plan of A^T is a plan like any other (tuned kernels, form choice, ordered sums); there is no scatter form of A^T x.
 """
@@ -286,6 +288,36 @@ class SparseOperator:
                 "status": s["status_name"]}
         return x, info
 
+    def minres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, minv=None, stream=None):
+        """A x = b for a square SYMMETRIC A that may be indefinite (saddle-point, KKT), by MINRES in the library (``api.MINRES`` over the plan of A) — one product
+        and three fused kernels per iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations; the residual norm never increases.  ``b``: a
+        contiguous torch CUDA vector of ``rows`` elements; ``minv``: a POSITIVE diagonal M^-1 as a CUDA vector (``api.csr_abs_diagonal_device(..., invert=True)`` makes one),
+        None = unpreconditioned.  Stops at ``sqrt(rr / bb) <= rtol`` (with ``minv``: in the M^-1 norm), after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.
+        Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}`` (``residual``: the recurrence's ``sqrt(rr)``)."""
+        import torch
+        rows, cols = self.shape
+        if rows != cols:
+            raise ValueError("minres needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
+        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
+            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
+        if minv is not None and (not _is_tensor(minv) or minv.numel() != rows or not minv.is_contiguous() or minv.dtype != b.dtype):
+            raise ValueError("minv must be a contiguous vector of %d elements of b's type" % rows)
+        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != rows or x0.dtype != b.dtype):
+            raise ValueError("x0 must be a vector of %d elements of b's type" % rows)
+        maxiter = 2 * rows if maxiter is None else maxiter
+        x = torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+        if x0 is not None:
+            x.copy_(x0)
+        st = _stream(stream)
+        solver = api.MINRES(self.A, None if minv is None else minv.data_ptr())
+        try:
+            s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
+        finally:
+            solver.close()
+        info = {"iterations": s["iterations"], "residual": max(s["rr"], 0.0) ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
+                "status": s["status_name"]}
+        return x, info
+
     def close(self):
         for p in (getattr(self, "A", None), getattr(self, "AT", None)):
             if p is not None:
@@ -340,6 +372,62 @@ def bicgstab(op, b, x0=None, tol=1e-10, maxiter=None, dinv=None, check_every=1):
         if it % check_every == 0 or it == maxiter:
             converged = float(rr.sqrt()) <= tol * norm_b
     res = float(torch.linalg.vector_norm(b - op.matvec(x)))
+    info = {"iterations": it, "residual": res, "relative_residual": res / norm_b if norm_b > 0 else 0.0, "converged": bool(converged)}
+    return x, info
+
+
+def minres(op, b, x0=None, tol=1e-10, maxiter=None, minv=None, check_every=1):
+    """``A x = b`` for a square symmetric operator by preconditioned MINRES as a loop of torch operations: the recurrences of ``SparseOperator.minres``, without
+    its guards — the baseline of scripts/minres_time.py and a second opinion in tests.  ``b``: a torch CUDA vector of ``rows`` elements; ``minv``: None or a positive diagonal.
+    The scalars of the recurrence are 0-d tensors on the device: nothing is read on the host between checks.  Stops when ``phibar <= tol * sqrt(b.M^-1 b)`` (checked every
+    ``check_every`` iterations: each check is one host sync) or after ``maxiter`` iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations",
+    "residual", "relative_residual", "converged"}`` (``residual``: a recomputed ``|b - A x|``, relative to ``|b|``)."""
+    import torch
+    rows, cols = op.shape
+    if rows != cols:
+        raise ValueError("minres needs a square operator; this one is %d x %d" % (rows, cols))
+    if b.numel() != rows:
+        raise ValueError("b must have %d elements" % rows)
+    maxiter = 2 * rows if maxiter is None else maxiter
+
+    def vector():
+        return torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+
+    x = vector()
+    r1, r2, y, v, w, w2 = vector(), vector(), vector(), vector(), vector(), vector()
+    r2.copy_(b)
+    if x0 is not None:
+        x.copy_(x0)
+        r2 -= op.matvec(x)
+    z = r2 if minv is None else minv * r2
+    beta = torch.dot(r2, z).sqrt()
+    bnorm = float(torch.dot(b, b if minv is None else minv * b).sqrt())
+    zero = torch.zeros((), dtype=b.dtype, device=b.device)
+    oldb, dbar, epsln, phibar, cs, sn = zero, zero, zero, beta, zero - 1, zero
+    it, converged = 0, float(phibar) <= tol * bnorm
+    while not converged and it < maxiter:
+        torch.div(z, beta, out=v)
+        op.matvec(v, y)
+        if it > 0:
+            y.addcmul_(r1, -(beta / oldb))
+        alfa = torch.dot(v, y)
+        y.addcmul_(r2, -(alfa / beta))
+        r1, r2, y = r2, y, r1
+        z = r2 if minv is None else minv * r2
+        betan = torch.dot(r2, z).sqrt()
+        oldeps, delta, gbar = epsln, cs * dbar + sn * alfa, sn * dbar - cs * alfa
+        gamma = torch.hypot(gbar, betan)
+        oldb, beta = beta, betan
+        epsln, dbar = sn * beta, -cs * beta
+        cs, sn = gbar / gamma, beta / gamma
+        phi, phibar = cs * phibar, sn * phibar
+        w, w2 = w2, w                               # w' over the older of the two
+        w.mul_(-oldeps / gamma).addcmul_(w2, -delta / gamma).addcmul_(v, 1 / gamma)
+        x.addcmul_(w, phi)
+        it += 1
+        if it % check_every == 0 or it == maxiter:
+            converged = float(phibar) <= tol * bnorm
+    res, norm_b = float(torch.linalg.vector_norm(b - op.matvec(x))), float(torch.linalg.vector_norm(b))
     info = {"iterations": it, "residual": res, "relative_residual": res / norm_b if norm_b > 0 else 0.0, "converged": bool(converged)}
     return x, info
 
