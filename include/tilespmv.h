@@ -353,6 +353,11 @@ typedef struct {
                            0 = never; 1 = floats wherever eligible and narrowable (never halves); 2 = the narrowest width every value allows, wherever eligible: 2, else 4, else 8 bytes;
                            unset = the narrowest width whose launch still moves more than the 400 MB above which nt_stream is 1 by rule (smaller plans live in the caches and are bound by
                            latency, not bytes).  Ignored by the fp32 build.  TILESPMV_INFO_UNIT_VALUE_BYTES tells which form a plan has             TILESPMV_VALUE_NARROW */
+    int unit_lean;      /* classic unit plans with nontemporal streams, entry mode 0 or 2 and 16 strips per workgroup in which no unit is a row unit (no dense-row tiles) run lean forms of
+                           the unit kernel: what only a row unit needs — and, where the plan has no derived unit either (absorb), what only a derived unit needs — is compiled out,
+                           and the unit loop tests the task's end once per task instead of once per unit.  Same plan, same streams, same arithmetic in the same order: y keeps every
+                           bit.  0 = always the general kernels; unset / 1 = the lean form wherever the plan's facts allow.  TILESPMV_INFO_UNIT_LEAN tells which form a plan's launch takes.
+                           The environment variable is read once per process                                                                TILESPMV_UNIT_LEAN */
     int reserved[1];    /* must be TILESPMV_KNOB_DEFAULT or 0 */
 } tilespmv_plan_options;
 void tilespmv_plan_options_init(tilespmv_plan_options *opts);
@@ -513,7 +518,8 @@ enum {
     TILESPMV_INFO_DESC_BYTES = 20,        /* bytes per unit descriptor in HBM: 12, or 4 (column-pattern dictionary); pooled plans 20, or 8 (pattern dictionary); wide pooled plans 28 */
     TILESPMV_INFO_NT_STREAM = 21,         /* 1: the unit kernel reads the value / entry-record streams with nontemporal loads */
     TILESPMV_INFO_UNIT_VALUE_BYTES = 22,  /* bytes per stored unit value: 8, or 4 (floats) / 2 (halves) in a narrow plan (value_narrow); the fp32 build always reports 4 */
-    TILESPMV_INFO_RETIRED_23 = 23,        /* always 0 */
+    TILESPMV_INFO_UNIT_LEAN = 23,         /* form of the unit kernel the plan's launch takes: 0 = general, 1 = lean (no unit is a row unit), 2 = lean without derived units (tilespmv_plan_options.unit_lean;
+                                             the same for host- and device-built plans of one matrix).  (Until this fact: a retired slot that was always 0) */
     TILESPMV_INFO_PLACEMENT_TRIES = 24,   /* arena placements timed at plan creation (large plans; 0 / 1 = the first one was kept) */
     TILESPMV_INFO_RETIRED_25 = 25,        /* always 0 */
     TILESPMV_INFO_X_PANELS = 26,          /* column panels of the entry lists = launches of the entry part (1 = not panelled) */

@@ -18,14 +18,14 @@ _CACHE = {}
 
 INFO_NAMES = ["device_bytes", "stream_bytes", "nnz", "rows", "tiles", "coo_mode", "dense_mode", "kernel",
               "num_tasks", "num_split_rows", "fallback_nnz", "build_us", "upload_us", "entry_mode", "entry_ordered", "strip_cost",
-              "wg_strips", "list_entries", "derived_units", "brick_order", "desc_bytes", "nt_stream", "unit_value_bytes", "retired_23", "placement_tries", "retired_25", "x_panels", "x_panel_merge", "scattered_entries", "x_slice_passes", "csr_form", "timed_choices_us", "device_build", "tile_create_us",
+              "wg_strips", "list_entries", "derived_units", "brick_order", "desc_bytes", "nt_stream", "unit_value_bytes", "unit_lean", "placement_tries", "retired_25", "x_panels", "x_panel_merge", "scattered_entries", "x_slice_passes", "csr_form", "timed_choices_us", "device_build", "tile_create_us",
               "value_map_bytes"]
 
 
 KNOB_DEFAULT = -1
 # tuning knobs of tilespmv_plan_options (include/tilespmv.h), in struct order after `autotune`
 KNOB_NAMES = ["entry_mode", "entry_ordered", "strip_cost", "split_above", "split_cap", "xcd_remap", "xcd_chunk", "csr_split", "fix_inline",
-              "coo_cost", "coo_heavy_min", "coo_piece", "strip_even", "wg_strips", "x_window", "x_stride1", "x_stride2", "mv_native", "mv_xcd_chunk", "lds_pad", "y_store", "desc_dict", "nt_stream", "x_panel_kb", "x_panel_merge", "placement_tries", "x_slice_passes", "deterministic", "absorb", "value_narrow"]
+              "coo_cost", "coo_heavy_min", "coo_piece", "strip_even", "wg_strips", "x_window", "x_stride1", "x_stride2", "mv_native", "mv_xcd_chunk", "lds_pad", "y_store", "desc_dict", "nt_stream", "x_panel_kb", "x_panel_merge", "placement_tries", "x_slice_passes", "deterministic", "absorb", "value_narrow", "unit_lean"]
 
 
 class PlanOptions(C.Structure):

@@ -197,7 +197,20 @@ struct DevStream {
     // finishes last (fixed slot order): ifix[i] describes row i, ifix_count[i] counts finished pieces
     const FixRow *ifix;
     unsigned *ifix_count;
+    // what the plan's units provably do not contain (classic plans; computed at the end of the layout build by the host and the device builder alike): bit 0 = no unit is a
+    // row unit (UNIT_ROWUNIT), bit 1 = no unit is derived (UNIT_DERIVED_CODE).  The launch reads them through unit_lean_form below.
+    int unit_facts;
+    int unit_lean;                        // the knob (tilespmv_plan_options.unit_lean): 0 = general kernels whatever the facts say
 };
+constexpr int UNIT_FACT_NO_ROWUNIT = 1, UNIT_FACT_NO_DERIVED = 2;
+// The form of the unit kernel a launch takes (TILESPMV_INFO_UNIT_LEAN): 0 = the general kernel, 1 = lean (no row units), 2 = lean without derived units.  Lean forms exist for
+// classic plans with nontemporal streams, entry mode 0 / 2 and 16 strips per workgroup (hip_kernels_lean.hip).
+inline int unit_lean_form(const DevStream &S, int entry_mode, int wg_strips)
+{
+    if (!S.unit_lean || S.ntasks <= 0 || S.pooled || !S.nt_stream || !(entry_mode == 0 || entry_mode == 2) || wg_strips != 16) return 0;
+    if (!(S.unit_facts & UNIT_FACT_NO_ROWUNIT)) return 0;
+    return (S.unit_facts & UNIT_FACT_NO_DERIVED) ? 2 : 1;
+}
 
 // Dense tiles on the matrix cores (generation 2): one wavefront per tile-row that owns dense tiles.
 struct DenseRow { int row, tile_begin, tile_end, partial; };  // partial: -1 -> y += result, else slot in partial[]
@@ -233,5 +246,7 @@ inline void tile_stream_sizes(int fmt, int p1, int p2, int *nv, int *ni)
 // hip_kernels_half.hip: the k_units launch of a plan whose unit values are halves (DevStream::uval_narrow 2), called by launch_tiles_stream (hip_kernels.hip);
 // hipErrorInvalidValue for any other plan and in the fp32 build
 hipError_t launch_units_half(const DevPlan &P, const DevStream &S, int entry_mode, int wg_strips, int lds_pad_bytes, int xcd_chunk, const val_t *x, val_t *y, hipStream_t st);
+// hip_kernels_lean.hip: the k_units launch of a plan whose unit_lean_form is `form` > 0, called by launch_tiles_stream; hipErrorInvalidValue for any other plan
+hipError_t launch_units_lean(const DevPlan &P, const DevStream &S, int form, int entry_mode, int wg_strips, int lds_pad_bytes, int xcd_chunk, const val_t *x, val_t *y, hipStream_t st);
 
 }  // namespace tilespmv

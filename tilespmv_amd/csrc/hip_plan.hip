@@ -67,6 +67,8 @@ static Knobs resolve_knobs(const tilespmv_plan_options *opts)
     k.x_slice_passes = pick(o.x_slice_passes, "TILESPMV_X_SLICE_PASSES", -1);
     k.absorb = pick(o.absorb, "TILESPMV_ABSORB", -1); if (k.absorb < 0 || k.absorb > 2) k.absorb = 1;
     k.value_narrow = pick(o.value_narrow, "TILESPMV_VALUE_NARROW", -1);
+    static const int unit_lean_env = env_int("TILESPMV_UNIT_LEAN", 1);   // (read once)
+    k.unit_lean = (o.unit_lean != TILESPMV_KNOB_DEFAULT ? o.unit_lean : unit_lean_env) != 0 ? 1 : 0;
     k.deterministic = pick(o.deterministic, "TILESPMV_DETERMINISTIC", 0) > 0 ? 1 : 0;
     if (k.deterministic) {   // no stopwatch, no unordered sum: whatever the caller left unset among the timed choices is switched off
         if (k.placement_tries < 0) k.placement_tries = 1;
@@ -258,7 +260,7 @@ const char *tilespmv_plan_options_layout(void)
         TSPMV_F(entry_mode) TSPMV_F(entry_ordered) TSPMV_F(strip_cost) TSPMV_F(split_above) TSPMV_F(split_cap) TSPMV_F(xcd_remap) TSPMV_F(xcd_chunk)
         TSPMV_F(csr_split) TSPMV_F(fix_inline) TSPMV_F(coo_cost) TSPMV_F(coo_heavy_min) TSPMV_F(coo_piece) TSPMV_F(strip_even) TSPMV_F(wg_strips)
         TSPMV_F(x_window) TSPMV_F(x_stride1) TSPMV_F(x_stride2) TSPMV_F(mv_native) TSPMV_F(mv_xcd_chunk) TSPMV_F(lds_pad) TSPMV_F(y_store)
-        TSPMV_F(desc_dict) TSPMV_F(nt_stream) TSPMV_F(x_panel_kb) TSPMV_F(x_panel_merge) TSPMV_F(placement_tries) TSPMV_F(x_slice_passes) TSPMV_F(deterministic) TSPMV_F(absorb) TSPMV_F(value_narrow) TSPMV_F(reserved)
+        TSPMV_F(desc_dict) TSPMV_F(nt_stream) TSPMV_F(x_panel_kb) TSPMV_F(x_panel_merge) TSPMV_F(placement_tries) TSPMV_F(x_slice_passes) TSPMV_F(deterministic) TSPMV_F(absorb) TSPMV_F(value_narrow) TSPMV_F(unit_lean) TSPMV_F(reserved)
 #undef TSPMV_F
         return o;
     }();
@@ -421,6 +423,7 @@ static int plan_create_tuned(tilespmv_plan **out, const Tile_matrix *T, int rowA
         const bool flip = ms2[1] > 0 && ms2[1] < ms2[0] * 0.985;   // leave the rule unless clearly better
         best->st.nt_stream = flip ? 1 - rule : rule;
         best->info[TILESPMV_INFO_NT_STREAM] = best->st.nt_stream;
+        best->info[TILESPMV_INFO_UNIT_LEAN] = unit_lean_form(best->st, best->entry_mode, best->wg_strips);   // (the lean forms are nontemporal ones)
         if (ms2[flip ? 1 : 0] > 0) best_ms = std::min(best_ms, ms2[flip ? 1 : 0]);
     }
     if (best) {
@@ -794,6 +797,7 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
     I[TILESPMV_INFO_NUM_TASKS] = n_tasks; I[TILESPMV_INFO_NUM_SPLIT_ROWS] = (long long)fix.size();
     I[TILESPMV_INFO_FALLBACK_NNZ] = f_nnz;
     I[TILESPMV_INFO_UNIT_VALUE_BYTES] = plan->st.uval_narrow == 2 ? 2 : plan->st.uval_narrow ? 4 : sv;
+    I[TILESPMV_INFO_UNIT_LEAN] = plan->kernel == TILESPMV_KERNEL_STREAM ? unit_lean_form(plan->st, plan->entry_mode, plan->wg_strips) : 0;
     if (plan->kernel != TILESPMV_KERNEL_STREAM) { I[TILESPMV_INFO_ENTRY_ORDERED] = 1; I[TILESPMV_INFO_STRIP_COST] = target; }
     I[TILESPMV_INFO_BUILD_US] = (long long)(now_us() - t_create0) - I[TILESPMV_INFO_UPLOAD_US];
     // bytes one SpMV has to move at least: the three streams + tasks + x once + y once (+ fallback)

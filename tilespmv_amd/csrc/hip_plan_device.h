@@ -38,6 +38,7 @@ int dev_pack_desc(const uint4 *d_udesc, const uint2 *d_urow, const uint4 *d_ucol
 // the distinct (n0, n1) patterns of NUP packed descriptors, ascending, if there are at most `cap` of them (else `over` = true); then the 4-byte form
 int dev_all_narrowable(const val_t *d_uval, long long n, bool *all_float, bool *all_half);   // fp64 build, one pass: is every one of the n emitted unit values narrowable / halvable (plan_tile_ops.h)?  fp32 build: false
 int dev_shift_histogram(const UDesc *d_packed, long long NUP, unsigned long long hist[8]);   // units per shift code (word 0 >> UNIT_SHIFT_SHIFT)
+int dev_count_flag(const UDesc *d_packed, long long NUP, unsigned flag, long long *count);      // units whose flags (word 0 >> UNIT_FLAG_SHIFT) have a bit of `flag` set
 struct DictRanges { int off[9]; };   // dictionary entries of shift code c (word 0 >> UNIT_SHIFT_SHIFT): [off[c], off[c + 1])
 int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vector<uint4> &dict, DictRanges *ranges, bool *over);   // distinct (shift code, nibbles) patterns in ascending order, as dictionary entries
 int dev_compact_desc(const UDesc *d_packed, long long NUP, const uint4 *d_dict, DictRanges ranges, int cb_bits, unsigned *d_compact);

@@ -659,6 +659,26 @@ int dev_all_narrowable(const val_t *d_uval, long long n, bool *all_float, bool *
     return 0;
 }
 
+__global__ __launch_bounds__(256) void k_pd_count_flag(const UDesc *__restrict__ packed, long long n, unsigned flag, unsigned long long *__restrict__ count)
+{
+    unsigned c = 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) c += ((packed[i].w0 >> UNIT_FLAG_SHIFT) & flag) ? 1u : 0u;
+    if (c) atomicAdd(count, (unsigned long long)c);
+}
+int dev_count_flag(const UDesc *d_packed, long long NUP, unsigned flag, long long *count)
+{
+    *count = 0;
+    if (NUP <= 0) return 0;
+    Tmp<unsigned long long> c;
+    PD_TRY(c.alloc(1, true));
+    hipLaunchKernelGGL(k_pd_count_flag, dim3((unsigned)std::min<long long>(nblk(NUP, 256), 4096)), dim3(256), 0, 0, d_packed, NUP, flag, c.p);
+    PD_TRY(hipGetLastError());
+    unsigned long long h = 0;
+    PD_TRY(hipMemcpy(&h, c.p, sizeof(h), hipMemcpyDeviceToHost));
+    *count = (long long)h;
+    return 0;
+}
+
 int dev_shift_histogram(const UDesc *d_packed, long long NUP, unsigned long long hist[8])
 {
     for (int c = 0; c < 8; c++) hist[c] = 0;

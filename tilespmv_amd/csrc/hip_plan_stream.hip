@@ -136,7 +136,8 @@ struct StreamBuilder {
     long long value_bytes() const { return narrow == 2 ? 2 : narrow ? 4 : sv; }   // bytes per stored unit value
     long long value_group() const { return narrow ? UNIT_GROUP_NARROW : UNIT_GROUP; }
     void choose_value_width();
-    int reserve_values()      // arena space for the NUP * 16 stored values, in the plan's form
+    void set_unit_facts(long long nrowunit, long long nderived) { S.unit_facts = (nrowunit == 0 ? UNIT_FACT_NO_ROWUNIT : 0) | (nderived == 0 ? UNIT_FACT_NO_DERIVED : 0); }   // end of ENCODE, classic plans: what the lean unit kernels rest on
+    int reserve_values()     // arena space for the NUP * 16 stored values, in the plan's form
     {
         if (narrow == 2) return plan->reserve((size_t)NUP * 16, reinterpret_cast<const unsigned short **>(&S.uval));
         if (narrow) return plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
@@ -845,6 +846,11 @@ void StreamBuilder::encode_device()
     }
     plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
     if (rc == 0 && !pooled) { unsigned long long hist[8]; if (dev_shift_histogram(d_packed, NUP, hist) != 0) rc = -3; else plan->info[TILESPMV_INFO_DERIVED_UNITS] = (long long)hist[UNIT_DERIVED_CODE]; }
+    if (rc == 0 && !pooled) {   // the facts the lean unit kernels rest on (hip_plan.h DevStream::unit_facts): one more reduction over the packed descriptors' flags
+        long long nrowunit = 0;
+        if (dev_count_flag(d_packed, NUP, UNIT_ROWUNIT, &nrowunit) != 0) rc = -3;
+        else set_unit_facts(nrowunit, plan->info[TILESPMV_INFO_DERIVED_UNITS]);
+    }
     // the value pass (as in host mode: k_pair_values), its source already on the device
     rc |= reserve_values();
     if (rc == 0) {
@@ -870,6 +876,7 @@ void StreamBuilder::encode()
     choose_value_width();
     if (rc) return;
     S.uval_narrow = narrow;
+    S.unit_facts = 0; S.unit_lean = K.unit_lean;   // (pooled plans keep no facts: they have no lean form)
     // the estimate that sizes the arena blocks priced the values at sizeof(val_t); a plan of halves is up to four times smaller.  (The float form keeps the estimate — an upper
     // bound — it has always had, so that its plans are placed in memory as before.)
     if (narrow == 2) plan->size_hint -= std::min(plan->size_hint, (size_t)(NU * 16 * (sv - value_bytes())));
@@ -1045,7 +1052,12 @@ void StreamBuilder::encode()
             rc |= plan->upload(dict.data(), dict.size(), &S.udict);
         } else rc |= plan->upload(packed.data(), (size_t)NUP, &S.udesc);
         plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
-        if (!pooled) { long long nder = 0; for (long long u = 0; u < NUP; u++) nder += (packed[(size_t)u].w0 >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE; plan->info[TILESPMV_INFO_DERIVED_UNITS] = nder; }
+        if (!pooled) {
+            long long nder = 0, nrowunit = 0;
+            for (long long u = 0; u < NUP; u++) { nder += (packed[(size_t)u].w0 >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE; nrowunit += ((packed[(size_t)u].w0 >> UNIT_FLAG_SHIFT) & UNIT_ROWUNIT) != 0; }
+            plan->info[TILESPMV_INFO_DERIVED_UNITS] = nder;
+            set_unit_facts(nrowunit, nder);
+        }
         if (pooled && !wide && !pool_dict) rc |= plan->upload(packed_row.data(), (size_t)NUP, &S.urow);
         if (wide) rc |= plan->upload(packed_col.data(), (size_t)NUP, &S.ucol);
         if (on_device) {

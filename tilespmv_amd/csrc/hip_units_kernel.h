@@ -1,5 +1,6 @@
 // hip_units_kernel.h — the unit-stream kernel k_units (hip_plan.h "unit stream") and the device helpers it needs, shared by the translation units that
-// instantiate it: hip_kernels.hip (every form whose values are val_t or floats) and hip_kernels_half.hip (fp64 build: the four forms whose values are halves).
+// instantiate it: hip_kernels.hip (every form whose values are val_t or floats), hip_kernels_half.hip (fp64 build: the four forms whose values are halves) and
+// hip_kernels_lean.hip (the lean forms for plans without row units, every value form: UNITS_LEAN below).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -289,19 +290,35 @@ extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
 // Halves (DevStream::uval_narrow 2): one 8-byte lane load per batch, which waits as 2 VGPRs and is widened half -> float -> double, both exact, when the batch becomes the current
 // one.  The four kernels of that form are this template under another name in a translation unit of their own (hip_kernels_half.hip), which sets the two macros below before it
 // includes this header; the kernels of hip_kernels.hip do not change by a line for it.
-#if defined(UNITS_KERNEL) != defined(UNITS_NARROW_FORM)
-#error "hip_units_kernel.h: define UNITS_KERNEL and UNITS_NARROW_FORM together (or neither: k_units, floats)"
+#if defined(UNITS_LEAN) ? (!defined(UNITS_KERNEL) || defined(UNITS_NARROW_FORM)) : (defined(UNITS_KERNEL) != defined(UNITS_NARROW_FORM))
+#error "hip_units_kernel.h: define UNITS_KERNEL and UNITS_NARROW_FORM together (or neither: k_units, floats); UNITS_LEAN goes with UNITS_KERNEL alone (the value form is a template argument there)"
 #endif
-#ifndef UNITS_KERNEL
+#if !defined(UNITS_KERNEL) && !defined(UNITS_LEAN)
 #define UNITS_KERNEL k_units      // the kernel's name in the including translation unit
 #define UNITS_NARROW_FORM 1       // ... and what NARROW means there: DevStream::uval_narrow 1 (floats) or 2 (halves)
 #endif
 // (halves, workgroup entry mode: 8 waves per SIMD like the per-strip form — the unit prologue is issued behind the entry phase, see there)
+// UNITS_LEAN (hip_kernels_lean.hip): the lean forms, for classic plans in which NO unit is a row unit (DevStream::unit_facts).  The template then takes the value form
+// (VF = DevStream::uval_narrow) and DERIVED ("some unit is derived") as arguments in place of POOL / WIDE / NARROW, and what only a row unit needs (its identity nibbles in the
+// gather, the 16-lane all-reduce in `retire`) or, with DERIVED off, only a derived unit needs (unit_x_use, xprev, the test in front of the gather) is compiled out.  Their unit
+// loop is peeled (below).  Loads, waits and LDS accesses are where the general kernel has them and the arithmetic is its multiply-then-add in unit order: y is the general
+// kernel's bit for bit.  Every lean form asks for 8 waves per SIMD; in the workgroup entry mode they issue the unit prologue behind the entry phase, like the halves.
+#ifdef UNITS_LEAN
+template <int UB, int ECOO, int GPB, bool CD, bool NTS, int VF, bool DERIVED>
+__global__ __launch_bounds__(16 * GPB, UNITS_MIN_WAVES) void UNITS_KERNEL(DevStream S, int rowA, int colA, int xcd_chunk, val_t *__restrict__ partial,
+                                               const val_t *__restrict__ x, val_t *__restrict__ y)
+{
+    constexpr bool LEAN = true, POOL = false, WIDE = false, NARROW = VF != 0, ROWUNITS = false;
+    constexpr int VFORM = VF;
+    static_assert(ECOO != 1 && GPB == 16 && NTS && VF >= 0 && VF <= (sizeof(val_t) == 8 ? 2 : 0), "lean forms: entry mode 0 / 2, 16 strips, nontemporal streams, a value form of this build");
+#else
 template <int UB, int ECOO, int GPB, bool CD, bool NTS, bool POOL = false, bool WIDE = false, bool NARROW = false>
 __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_ECOO2_MIN_WAVES : NARROW && UNITS_NARROW_FORM == 2 ? UNITS_MIN_WAVES : ECOO2_MIN_WAVES) : POOL ? (WIDE ? 6 : POOL_MIN_WAVES) : UNITS_MIN_WAVES) void UNITS_KERNEL(DevStream S, int rowA, int colA, int xcd_chunk, val_t *__restrict__ partial,
                                                const val_t *__restrict__ x, val_t *__restrict__ y)
 {
+    constexpr bool LEAN = false, ROWUNITS = true, DERIVED = true;   // the general forms serve every plan
     constexpr int VFORM = NARROW ? UNITS_NARROW_FORM : 0;   // DevStream::uval_narrow of the plans this instantiation runs
+#endif
     static_assert(VFORM >= 0 && VFORM <= 2, "UNITS_NARROW_FORM: 1 or 2");
     static_assert(!NARROW || (sizeof(val_t) == 8 && !POOL && ECOO != 1 && GPB == 16 && NTS), "narrow values: fp64 classic plans, entry mode 0 / 2, 16 strips, nontemporal streams");
     constexpr int G = NARROW ? UNIT_GROUP_NARROW : UNIT_GROUP;   // units whose values share one 16-byte lane load
@@ -453,8 +470,8 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
 #pragma unroll
         for (int k = 0; k < UB; k++) {
             const unsigned fl = d[k].x >> 24;
-            const unsigned nib = (fl & UNIT_ROWUNIT) ? (unsigned)r : (d[k].y >> (28 - 4 * (r & 7))) & 15u;
-            if ((d[k].x >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE && r != 15) xv[k] = 0;   // derived unit: only lane 15 loads (unit_x_use gives the others the previous unit's x)
+            const unsigned nib = (ROWUNITS && (fl & UNIT_ROWUNIT)) ? (unsigned)r : (d[k].y >> (28 - 4 * (r & 7))) & 15u;
+            if (DERIVED && (d[k].x >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE && r != 15) { if constexpr (!LEAN) xv[k] = 0; }   // derived unit: only lane 15 loads (unit_x_use gives the others the previous unit's x and selects their xv[k] away: the lean forms leave it as it is)
             else if constexpr (UNIT_X32) xv[k] = x[x_index32(unit_x_base32(d[k].x), nib, xlast32)];
             else xv[k] = x[min(unit_x_base(d[k].x) + nib, xlast)];
         }
@@ -475,7 +492,7 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         // 6 waves — and changes nothing: power-law 8 M 0.1026-0.1034 ms either way, profiles/r03_entry_ablations.txt: bytes in flight are not the limit)
         // pipelined trips on top of that (78 VGPRs at 6 x 256, no spill): 0.1050-0.1062 against 0.1031-0.1046 — slightly worse
         // (halves: behind the entry phase — the 16 VGPRs this frees keep the form at 64 VGPRs without scratch)
-        constexpr bool LATE_PROLOGUE = VFORM == 2;
+        constexpr bool LATE_PROLOGUE = VFORM == 2 || LEAN;
         if constexpr (!LATE_PROLOGUE) unit_prologue();
         if (wr.y > wr.x) {
             int ge = wr.y;   // column-panelled launch: this kernel takes the first panel_merge panels of the list, k_entries_acc the rest
@@ -583,9 +600,11 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
             else atomicAdd(&s_y[g][0][0] + dest, (lacc_t)prod);
             return;
         }
-        if (flags & UNIT_ROWUNIT) {  // dense-row unit: lanes hold one row's products
-            prod = strip_allreduce(prod);
-            if (r != (int)(word1 & 15u)) prod = 0;
+        if constexpr (ROWUNITS) {
+            if (flags & UNIT_ROWUNIT) {  // dense-row unit: lanes hold one row's products
+                prod = strip_allreduce(prod);
+                if (r != (int)(word1 & 15u)) prod = 0;
+            }
         }
         acc += prod;
         if (flags & UNIT_EOR) {
@@ -612,6 +631,57 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         }
         int chunk_end = unit_begin + DCHUNK;  // first unit NOT described by the chunk in LDS
         val_t xprev = 0;   // classic plans: the x the previous unit used (derived units, unit_x_use)
+        if constexpr (LEAN) {
+            // The lean forms' loop.  One batch of UB units: TAIL = the task's last batch where its unit count is no multiple of UB — the only one whose units are tested
+            // against unit_end, and the only one with no batch behind it to prefetch values for; every other batch runs unguarded in the loop below.  The value prefetch
+            // keeps a carried pointer (the group of the batch behind the current one; it may pass the task's last group and is dereferenced only inside the task: groups
+            // start at multiples of G from unit_begin, so "u + UB + k <= last_grp" is "u + UB + k < unit_end").
+            const grp_t *vnext = ugrp + (long long)(unit_begin + UB) * (16 / G);
+            auto batch = [&](const int u, auto tail) {
+#pragma clang fp contract(off)   // the general loop's product and sum sit in different blocks (the tail guard, the row-unit test) and stay v_mul + v_add; without those branches the compiler would fuse them here, and y would differ in its last bit
+                constexpr bool TAIL = decltype(tail)::value;
+                if (u == chunk_end) {  // next descriptor chunk: already in registers, fetch the one after it (as in the general loop below; lean plans are classic ones)
+                    wave_lds_fence();
+                    if constexpr (CD) s_d[g][r] = udesc_expand(S, dnext.x, make_uint4(dnext.y, dnext.w, dnext.z, 0u));
+                    else s_d[g][r] = udesc_park_form(dnext);
+                    wave_lds_fence();
+                    chunk_end += DCHUNK;
+                    if constexpr (CD) {
+                        const uint4 p = udict_of(S, wnn);   // (its word was loaded a chunk ago)
+                        dnext = make_uint4(wnn, p.x, p.z, p.y);
+                        wnn = stream_load<NT_DESC>(udw + (min(chunk_end + DCHUNK + r + 1, unit_end) - 1));   // (= min(.., last) from unit_end, which the loop keeps anyway: one VGPR less across the loop)
+                    } else dnext = load_udesc_raw(S.udesc, min(chunk_end + r + 1, unit_end) - 1);
+                }
+                fetch_batch(u - (chunk_end - DCHUNK));
+                sval_t vn[UB];
+                if constexpr (!TAIL) {
+#pragma unroll
+                    for (int k = 0; k < UB; k += G) {  // unconditional: exact vmcnt
+                        const grp_t *pa = vnext + k * (16 / G);
+                        if constexpr (UNIT_TAIL_HOT) pa = (u + UB + k < unit_end) ? pa : reinterpret_cast<const grp_t *>(S.uval);   // behind the task's end: nobody uses what this loads (the plan's first 16 / 8 bytes)
+                        else pa = ugrp + (long long)min(u + UB + k, last_grp) * (16 / G);
+                        const grp_t pv = stream_load<NT>(pa);
+#pragma unroll
+                        for (int q = 0; q < G; q++) vn[k + q] = pv[q];
+                    }
+                    vnext += UB * (16 / G);
+                }
+                __builtin_amdgcn_sched_barrier(0);   // the batch's loads are issued before its first use, as in the general loop (whose tail guard keeps the scheduler from mixing the two)
+#pragma unroll
+                for (int k = 0; k < UB; k++) {
+                    val_t xu = xv[k];
+                    if constexpr (DERIVED) { xu = unit_x_use(xv[k], xprev, d[k].x, r); xprev = xu; }
+                    if (!TAIL || u + k < unit_end) retire(v[k] * xu, d[k].x >> 24, d[k].y);
+                }
+                if constexpr (!TAIL) {
+#pragma unroll
+                    for (int k = 0; k < UB; k++) v[k] = vn[k];
+                }
+            };
+            int u = unit_begin;
+            for (; u + UB <= unit_end; u += UB) batch(u, std::false_type());
+            if (u < unit_end) batch(u, std::true_type());
+        } else
         for (int u = unit_begin; u < unit_end; u += UB) {
             if (u == chunk_end) {  // next descriptor chunk: already in registers, fetch the one after it
                 wave_lds_fence();
