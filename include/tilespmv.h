@@ -835,6 +835,51 @@ int tilespmv_minres_solve(tilespmv_minres *s, const MAT_VAL_TYPE *d_b, MAT_VAL_T
 int tilespmv_csr_abs_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, MAT_VAL_TYPE *d_out, int invert,
                                      void *stream);
 
+/* ---- A block-Jacobi preconditioner for tilespmv_cg_* and tilespmv_bicgstab_* (new).  M is the block diagonal of A for CONSECUTIVE blocks of
+ * block_size rows: block k covers rows and columns [k bs, min((k + 1) bs, rows)), 1 <= bs <= 16, the last block short when rows % bs != 0 — one block per node of a structural FEM
+ * matrix with bs unknowns per node, where a point diagonal is the wrong tool.  The object holds M^-1 in device memory in the value type.
+ *
+ * Layout of M^-1, plane-major: plane j (j < bs) is a vector of `rows` elements padded to a multiple of 256 bytes; plane_j[i] = (M^-1)[i][blockstart(i) + j], 0 where the block is
+ * short — every plane is walked like a solver vector, with 16-byte lane accesses.  z = M^-1 r reads r once (a workgroup stages the slab of r its rows' blocks cover in LDS), every
+ * plane once, and writes z once: bs + 2 elements per row; z_i = sum_j plane_j[i] r[blockstart(i) + j] with j ascending, accumulated in double, rounded to the value type once.
+ *
+ *   tilespmv_block_jacobi_create   one hipMalloc (the bs planes and a device counter; synchronises).  hipErrorInvalidValue, without any HIP call, for a NULL bj, rows <= 0 or
+ *                                  block_size outside 1 .. 16.  Until the first update M^-1 is 0.
+ *   tilespmv_block_jacobi_update   extracts the blocks from a DEVICE CSR (the row pointer is used as it stands; duplicates are added in storage order, in double; columns may be
+ *                                  unsorted) and inverts them on the device: Gauss-Jordan with partial pivoting, in double in both builds, ties broken by the lowest row, the result
+ *                                  rounded to the value type once — a function of the block's values alone, so two updates from the same values give the same bytes.  A block whose
+ *                                  pivot is exactly 0 or not finite at any step gets the IDENTITY as its inverse and is counted (info).  Asynchronous on `stream`; no allocation,
+ *                                  no synchronisation, no host read: capturable into a hipGraph; after every tilespmv_plan_update_values it is the same call into the same object.
+ *   tilespmv_block_jacobi_apply    z = M^-1 r; d_r and d_z are distinct device vectors of `rows` elements, 16-byte aligned (hipErrorInvalidValue otherwise); nothing behind element
+ *                                  rows - 1 of either is touched.  Asynchronous, capturable.
+ *   tilespmv_block_jacobi_apply_dot  the same, and d_partials[w] = the sum over workgroup w's rows of r_i z_i (double; info's dot_partials of them, at most
+ *                                  TILESPMV_BJ_MAX_PARTIALS: their number and the order of every addition are fixed by `rows` alone) — what the CG below folds into r.z.
+ *   tilespmv_block_jacobi_info     synchronises `stream`; out[TILESPMV_BJ_INFO_*].
+ *
+ * Solvers that take the object: tilespmv_cg_create_block and tilespmv_bicgstab_create_block return the EXISTING solver types; begin, iterate, state_read, solve and destroy are the
+ * entry points above.  bj is borrowed until destroy and its values may change between solves; its rows must be the plan's (hipErrorInvalidValue otherwise, nothing allocated).
+ *   CG        z becomes a stored vector (4 work vectors).  One iteration: the product, k_cg_dot, k_cg_update (r.r partials), apply_dot r -> z (r.z partials), and p = z + beta p:
+ *             four launches beside the product, 13 + bs vector elements per row BY COUNT (13 with point Jacobi).
+ *   BiCGStab  phat = M^-1 p and shat = M^-1 s by two applies per iteration (7 work vectors): 18 + 2 (bs + 2) elements per row by count (23 with point Jacobi).
+ * Out of scope: MINRES (it needs a positive definite M, and the diagonal blocks of an indefinite matrix are not), multi-RHS CG (the apply would need the row-major [rows][nvec]
+ * layout) and CGLS.  All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_block_jacobi tilespmv_block_jacobi;
+enum {
+    TILESPMV_BJ_INFO_ROWS = 0, TILESPMV_BJ_INFO_BLOCK_SIZE = 1, TILESPMV_BJ_INFO_BLOCKS = 2,
+    TILESPMV_BJ_INFO_SINGULAR_BLOCKS = 3,   /* blocks the last update replaced by the identity */
+    TILESPMV_BJ_INFO_DEVICE_BYTES = 4, TILESPMV_BJ_INFO_DOT_PARTIALS = 5,
+    TILESPMV_BJ_INFO_COUNT = 6
+};
+#define TILESPMV_BJ_MAX_PARTIALS 1024
+int tilespmv_block_jacobi_create(tilespmv_block_jacobi **bj, int rows, int block_size);
+void tilespmv_block_jacobi_destroy(tilespmv_block_jacobi *bj);
+int tilespmv_block_jacobi_update(tilespmv_block_jacobi *bj, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, void *stream);
+int tilespmv_block_jacobi_apply(const tilespmv_block_jacobi *bj, const MAT_VAL_TYPE *d_r, MAT_VAL_TYPE *d_z, void *stream);   /* z = M^-1 r, z != r */
+int tilespmv_block_jacobi_apply_dot(const tilespmv_block_jacobi *bj, const MAT_VAL_TYPE *d_r, MAT_VAL_TYPE *d_z, double *d_partials, void *stream);
+int tilespmv_block_jacobi_info(const tilespmv_block_jacobi *bj, void *stream, long long *out /* [TILESPMV_BJ_INFO_COUNT] */);
+int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, const tilespmv_block_jacobi *bj);
+int tilespmv_bicgstab_create_block(tilespmv_bicgstab **s, tilespmv_plan *plan, const tilespmv_block_jacobi *bj);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

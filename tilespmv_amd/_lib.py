@@ -22,6 +22,8 @@ INFO_NAMES = ["device_bytes", "stream_bytes", "nnz", "rows", "tiles", "coo_mode"
               "value_map_bytes"]
 
 
+BJ_INFO_NAMES = ["rows", "block_size", "blocks", "singular_blocks", "device_bytes", "dot_partials"]   # TILESPMV_BJ_INFO_* of include/tilespmv.h
+
 KNOB_DEFAULT = -1
 # tuning knobs of tilespmv_plan_options (include/tilespmv.h), in struct order after `autotune`
 KNOB_NAMES = ["entry_mode", "entry_ordered", "strip_cost", "split_above", "split_cap", "xcd_remap", "xcd_chunk", "csr_split", "fix_inline",
@@ -242,6 +244,22 @@ def load(dtype=np.float64):
     lib.tilespmv_minres_solve.restype = C.c_int
     lib.tilespmv_csr_abs_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_csr_abs_diagonal_device.restype = C.c_int
+    lib.tilespmv_block_jacobi_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int]
+    lib.tilespmv_block_jacobi_create.restype = C.c_int
+    lib.tilespmv_block_jacobi_destroy.argtypes = [C.c_void_p]
+    lib.tilespmv_block_jacobi_destroy.restype = None
+    lib.tilespmv_block_jacobi_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_block_jacobi_update.restype = C.c_int
+    lib.tilespmv_block_jacobi_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_block_jacobi_apply.restype = C.c_int
+    lib.tilespmv_block_jacobi_apply_dot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_block_jacobi_apply_dot.restype = C.c_int
+    lib.tilespmv_block_jacobi_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.tilespmv_block_jacobi_info.restype = C.c_int
+    lib.tilespmv_cg_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.tilespmv_cg_create_block.restype = C.c_int
+    lib.tilespmv_bicgstab_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.tilespmv_bicgstab_create_block.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -274,4 +292,6 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_bicgstab_create", "tilespmv_bicgstab_destroy", "tilespmv_bicgstab_begin", "tilespmv_bicgstab_iterate", "tilespmv_bicgstab_state_read",
                     "tilespmv_bicgstab_solve",
                     "tilespmv_minres_create", "tilespmv_minres_destroy", "tilespmv_minres_begin", "tilespmv_minres_iterate", "tilespmv_minres_state_read", "tilespmv_minres_solve",
-                    "tilespmv_csr_abs_diagonal_device"]
+                    "tilespmv_csr_abs_diagonal_device",
+                    "tilespmv_block_jacobi_create", "tilespmv_block_jacobi_destroy", "tilespmv_block_jacobi_update", "tilespmv_block_jacobi_apply", "tilespmv_block_jacobi_apply_dot",
+                    "tilespmv_block_jacobi_info", "tilespmv_cg_create_block", "tilespmv_bicgstab_create_block"]

@@ -470,21 +470,72 @@ def csr_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dt
         raise RuntimeError("tilespmv_csr_diagonal_device failed (hipError %d): bad argument, or no usable device" % rc)
 
 
+class BlockJacobi(_Solver):
+    """``tilespmv_block_jacobi``: M^-1 for M = the block diagonal of A in consecutive blocks of ``block_size`` rows (1 .. 16; the last block may be short), held on the device and
+    applied by one streaming kernel (include/tilespmv.h) — the ``block`` of ``CG`` and ``BiCGStab``, one block per node of an FEM matrix with ``block_size``
+    unknowns per node.  All arguments of the methods are device ADDRESSES; vectors have ``rows`` elements and are 16-byte aligned.  Raises ``ValueError`` where the library returns
+    hipErrorInvalidValue."""
+
+    _destroy = "tilespmv_block_jacobi_destroy"
+    _hint = "rows > 0, 1 <= block_size <= 16; vectors distinct and 16-byte aligned"
+
+    def __init__(self, rows, block_size, dtype=np.float64):
+        self.lib = _lib.load(dtype)
+        self.rows, self.block_size, self.dtype = int(rows), int(block_size), np.dtype(dtype)
+        h = C.c_void_p()
+        self._check(self.lib.tilespmv_block_jacobi_create(C.byref(h), self.rows, self.block_size), "tilespmv_block_jacobi_create")
+        self.h = h
+
+    def update(self, d_rp, d_ci, d_v, stream=0):
+        """Extract the blocks from a device CSR and invert them; asynchronous, capturable.  After ``Plan.update_values``: the same call again."""
+        self._check(self.lib.tilespmv_block_jacobi_update(self.h, C.c_void_p(d_rp), C.c_void_p(d_ci), C.c_void_p(d_v), C.c_void_p(stream)), "tilespmv_block_jacobi_update")
+
+    def apply(self, d_r, d_z, stream=0, d_partials=None):
+        """z = M^-1 r (z and r distinct); asynchronous, capturable.  ``d_partials``: also the ``info()["dot_partials"]`` partial sums of r.z, doubles."""
+        if d_partials is None:
+            rc = self.lib.tilespmv_block_jacobi_apply(self.h, C.c_void_p(d_r), C.c_void_p(d_z), C.c_void_p(stream))
+        else:
+            rc = self.lib.tilespmv_block_jacobi_apply_dot(self.h, C.c_void_p(d_r), C.c_void_p(d_z), C.c_void_p(d_partials), C.c_void_p(stream))
+        self._check(rc, "tilespmv_block_jacobi_apply")
+
+    def info(self, stream=0):
+        """Synchronises ``stream``; ``{"rows", "block_size", "blocks", "singular_blocks", "device_bytes", "dot_partials"}`` (singular_blocks: blocks the last update replaced by
+        the identity)."""
+        out = (C.c_longlong * len(_lib.BJ_INFO_NAMES))()
+        self._check(self.lib.tilespmv_block_jacobi_info(self.h, C.c_void_p(stream), out), "tilespmv_block_jacobi_info")
+        return dict(zip(_lib.BJ_INFO_NAMES, [int(v) for v in out]))
+
+
+def _block_handle(block, d_dinv, lib):
+    """The handle of the ``block`` argument of ``CG`` / ``BiCGStab`` (None: none given)."""
+    if block is None:
+        return None
+    if d_dinv:
+        raise ValueError("block and d_dinv are mutually exclusive: one preconditioner")
+    if not isinstance(block, BlockJacobi) or not block.h or block.lib is not lib:
+        raise ValueError("block must be an open api.BlockJacobi of the plan's value type")
+    return block.h
+
+
 class CG(_Solver):
     """``tilespmv_cg``: conjugate gradients around a resident plan, every scalar on the device (include/tilespmv.h).
 
-    ``plan``: square and whole; it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal (Jacobi; borrowed), or None for plain CG.  ``b`` / ``x``
+    ``plan``: square and whole; it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal (Jacobi; borrowed), or None for plain CG.  ``block``: a
+    ``BlockJacobi`` of the plan's rows instead of ``d_dinv`` (borrowed: keep it open while the solver is).  ``b`` / ``x``
     are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library returns
-    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``."""
 
     _destroy = "tilespmv_cg_destroy"
-    _hint = "the plan must be square and whole; vectors 16-byte aligned"
+    _hint = "the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
 
-    def __init__(self, plan, d_dinv=None):
-        self.lib, self.plan = plan.lib, plan
+    def __init__(self, plan, d_dinv=None, block=None):
+        self.lib, self.plan, self.block = plan.lib, plan, block
         h = C.c_void_p()
-        rc = self.lib.tilespmv_cg_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None))
-        self._check(rc, "tilespmv_cg_create")
+        bh = _block_handle(block, d_dinv, plan.lib)
+        if bh is not None:
+            self._check(self.lib.tilespmv_cg_create_block(C.byref(h), plan.h, bh), "tilespmv_cg_create_block")
+        else:
+            self._check(self.lib.tilespmv_cg_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None)), "tilespmv_cg_create")
         self.h = h
 
     @staticmethod
@@ -621,17 +672,21 @@ class BiCGStab(_Solver):
     DESIGN.md §3.10).  It mirrors ``CG``: the same state dict, the same statuses.
 
     ``plan``: square and whole (a square ``transpose=True`` plan solves ``A^T x = b``); it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal
-    (Jacobi: ``csr_diagonal_device(..., invert=True)``; borrowed), or None.  ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run
-    on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+    (Jacobi: ``csr_diagonal_device(..., invert=True)``; borrowed), or None.  ``block``: a ``BlockJacobi`` of the plan's rows instead of ``d_dinv`` (borrowed).
+    ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library
+    returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``."""
 
     _destroy = "tilespmv_bicgstab_destroy"
-    _hint = "the plan must be square and whole; vectors 16-byte aligned"
+    _hint = "the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
 
-    def __init__(self, plan, d_dinv=None):
-        self.lib, self.plan = plan.lib, plan
+    def __init__(self, plan, d_dinv=None, block=None):
+        self.lib, self.plan, self.block = plan.lib, plan, block
         h = C.c_void_p()
-        rc = self.lib.tilespmv_bicgstab_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None))
-        self._check(rc, "tilespmv_bicgstab_create")
+        bh = _block_handle(block, d_dinv, plan.lib)
+        if bh is not None:
+            self._check(self.lib.tilespmv_bicgstab_create_block(C.byref(h), plan.h, bh), "tilespmv_bicgstab_create_block")
+        else:
+            self._check(self.lib.tilespmv_bicgstab_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None)), "tilespmv_bicgstab_create")
         self.h = h
 
     def begin(self, d_b, d_x, stream=0):

@@ -4,18 +4,21 @@
 //   k_cg_dot        reads p, Ap                     partial sums of p.Ap, one per workgroup
 //   k_cg_update     reads p, Ap, x, r (, dinv)      alpha = rho / p.Ap;  x += alpha p;  r -= alpha Ap;  partial sums of r.r and (Jacobi) r.z, z = dinv o r
 //   k_cg_direction  reads r, p (, dinv)             beta = rho_new / rho;  p = z + beta p  (z recomputed from r and dinv, never stored)
+// With a block-Jacobi object (tilespmv_cg_create_block; hip_precond.hip) z is a stored vector: k_cg_update runs with dinv = NULL (r.r partials only), k_bj_apply forms
+// z = M^-1 r and the r.z partials, and k_cg_zstep replaces k_cg_direction — four launches, (13 + bs) n elements.  The kernels above are the same code either way.
 // 11 n vector elements per iteration (13 n with Jacobi).  The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail
 // are those of hip_solver_common.h; the number of partials is solver_parts(n).  alpha and beta are rounded to the value type once, where they multiply.
 //
 // The scalar block (CgScal) has ONE writing kernel per field and no kernel reads a field it (or a concurrent workgroup of it) writes:
 //   rho         k_cg_dot, workgroup 0 (fold of the r.z partials the previous update left; 0 after a breakdown)      read by k_cg_update, k_cg_direction
 //   breakdown   k_cg_update, workgroup 0 (set, never cleared)                                                        read by k_cg_dot (workgroup 0), k_cg_direction
-//   rr, iterations   k_cg_direction, workgroup 0 (iterations: read and written by that workgroup alone)              read by the host (tilespmv_cg_state_read)
+//   rr, iterations   k_cg_direction (k_cg_zstep with a block preconditioner), workgroup 0 (iterations: read and written by that workgroup alone)              read by the host (tilespmv_cg_state_read)
 //   all of them      k_cg_begin_fold (one workgroup), at the start of a solve
 // Guards (data-dependent branches, no host round trip): rho = 0 -> alpha = beta = 0, x and r stay as they are; rho > 0 and not p.Ap > 0 (or rho < 0: a preconditioner that is not
 // positive definite) -> breakdown is set, alpha = beta = 0 in this and every later iteration, x keeps its last good value.
 #include <hip/hip_runtime.h>
 
+#include "hip_precond.h"
 #include "hip_solver_common.h"
 
 namespace tilespmv {
@@ -199,6 +202,36 @@ __global__ __launch_bounds__(SVB) void k_csr_diagonal(int rows, const int *__res
     out[i] = !invert ? d : SV_INVERSE_OR_ONE(d);
 }
 
+// the direction with a STORED z (block Jacobi: z = M^-1 r and the r.z partials come from k_bj_apply, hip_precond.hip): beta = rho_new / rho;  p = z + beta p.  The scalars are
+// k_cg_direction's, with rr folded from the r.r partials of k_cg_update (k_cg_direction with z in r's place would take rr = rho_new).
+__global__ __launch_bounds__(SVB) void k_cg_zstep(long long n, const val_t *__restrict__ z, val_t *__restrict__ p, const double *__restrict__ prr, const double *__restrict__ prz,
+                                                  int np, CgScal *__restrict__ S)
+{
+    __shared__ double s[SVB / 64];
+    const double rho_new = fold(prz, np, s), rho = S->rho;
+    const val_t beta = (val_t)((rho > 0.0 && !S->breakdown) ? rho_new / rho : 0.0);
+    if (blockIdx.x == 0) {   // what the host reads
+        const double rr = fold(prr, np, s);
+        if (threadIdx.x == 0) { S->rr = rr; S->iterations = S->iterations + 1; }
+    }
+    const long long nv = n / SV_VPL;
+    SV_FOR_TRIPS(base, nv, gridDim.x) {
+        svec_t vz[SV_U], vp[SV_U];
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) { vz[u] = lanes(z)[v]; vp[u] = lanes(p)[v]; }
+        }
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) lanes(p)[v] = vz[u] + beta * vp[u];
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long i = nv * SV_VPL; i < n; i++) p[i] = z[i] + beta * p[i];
+}
+
 }  // namespace
 }  // namespace tilespmv
 
@@ -209,36 +242,51 @@ struct tilespmv_cg {
     long long n = 0;
     int np = 0;
     const val_t *dinv = nullptr;   // borrowed
-    void *block = nullptr;         // the one allocation: r, p, Ap, the partial-sum arrays, the scalar block
-    val_t *r = nullptr, *p = nullptr, *Ap = nullptr;
+    const tilespmv_block_jacobi *bj = nullptr;   // borrowed (tilespmv_cg_create_block; then dinv is NULL and z is a vector)
+    void *block = nullptr;         // the one allocation: r, p, Ap (, z), the partial-sum arrays, the scalar block
+    val_t *r = nullptr, *p = nullptr, *Ap = nullptr, *z = nullptr;
     double *ppap = nullptr, *prr = nullptr, *prz = nullptr, *pbb = nullptr;
     CgScal *S = nullptr;
 };
+
+// the two creates: a diagonal (d_dinv, may be NULL) or a block-Jacobi object (bj), never both
+static int cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const val_t *d_dinv, const tilespmv_block_jacobi *bj)
+{
+    const long long n = plan->matrix_rows;
+    if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
+    if (misaligned(d_dinv) || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
+    const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    DeviceBlock blk;
+    const hipError_t e = blk.alloc((bj ? 4 : 3) * vec + 4 * parts + 256);
+    if (e != hipSuccess) return (int)e;
+    auto *c = new tilespmv_cg();
+    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->bj = bj; c->block = blk.base;
+    c->r = blk.take<val_t>(vec);
+    c->p = blk.take<val_t>(vec);
+    c->Ap = blk.take<val_t>(vec);
+    if (bj) c->z = blk.take<val_t>(vec);
+    c->ppap = blk.take<double>(parts);
+    c->prr = blk.take<double>(parts);
+    double *const rz = blk.take<double>(parts);
+    c->prz = (d_dinv || bj) ? rz : c->prr;
+    c->pbb = blk.take<double>(parts);
+    c->S = blk.take<CgScal>(256);
+    *cg = c;
+    return 0;
+}
 
 extern "C" int tilespmv_cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv)
 {
     if (cg) *cg = nullptr;
     if (!cg || !plan) return (int)hipErrorInvalidValue;
-    const long long n = plan->matrix_rows;
-    if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
-    if (misaligned(d_dinv)) return (int)hipErrorInvalidValue;
-    const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
-    DeviceBlock blk;
-    const hipError_t e = blk.alloc(3 * vec + 4 * parts + 256);
-    if (e != hipSuccess) return (int)e;
-    auto *c = new tilespmv_cg();
-    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->block = blk.base;
-    c->r = blk.take<val_t>(vec);
-    c->p = blk.take<val_t>(vec);
-    c->Ap = blk.take<val_t>(vec);
-    c->ppap = blk.take<double>(parts);
-    c->prr = blk.take<double>(parts);
-    double *const rz = blk.take<double>(parts);
-    c->prz = d_dinv ? rz : c->prr;
-    c->pbb = blk.take<double>(parts);
-    c->S = blk.take<CgScal>(256);
-    *cg = c;
-    return 0;
+    return cg_create(cg, plan, d_dinv, nullptr);
+}
+
+extern "C" int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, const tilespmv_block_jacobi *bj)
+{
+    if (cg) *cg = nullptr;
+    if (!cg || !plan || !bj) return (int)hipErrorInvalidValue;
+    return cg_create(cg, plan, nullptr, bj);
 }
 
 extern "C" void tilespmv_cg_destroy(tilespmv_cg *cg)
@@ -255,6 +303,7 @@ extern "C" int tilespmv_cg_begin(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_V
     const int rc = tilespmv_plan_spmv(cg->plan, d_x, cg->Ap, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_cg_begin, dim3(cg->np), dim3(SVB), 0, st, cg->n, d_b, cg->Ap, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->pbb);
+    if (cg->bj) block_jacobi_launch(cg->bj, cg->r, cg->p, cg->prz, st);   // p = z = M^-1 r, and the r.z partials
     hipLaunchKernelGGL(k_cg_begin_fold, dim3(1), dim3(SVB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->S);
     return (int)hipGetLastError();
 }
@@ -268,7 +317,11 @@ extern "C" int tilespmv_cg_iterate(tilespmv_cg *cg, MAT_VAL_TYPE *d_x, int count
         if (rc) return rc;
         hipLaunchKernelGGL(k_cg_dot, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->p, cg->Ap, cg->ppap, cg->prz, cg->np, cg->S);
         hipLaunchKernelGGL(k_cg_update, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->p, cg->Ap, d_x, cg->r, cg->dinv, cg->ppap, cg->prr, cg->prz, cg->np, cg->S);
-        hipLaunchKernelGGL(k_cg_direction, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->np, cg->S);
+        if (cg->bj) {   // (k_cg_update left the r.r partials only)
+            block_jacobi_launch(cg->bj, cg->r, cg->z, cg->prz, st);
+            hipLaunchKernelGGL(k_cg_zstep, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->z, cg->p, cg->prr, cg->prz, cg->np, cg->S);
+        } else
+            hipLaunchKernelGGL(k_cg_direction, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->np, cg->S);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }

@@ -10,6 +10,9 @@
 // Vector elements read or written per iteration beside the two products, BY COUNT: 18 n (rhat v | r v r | t s | x phat s t rhat x r | r p v p); Jacobi adds dinv and the store of
 // shat in the half step, the read of shat in the update, dinv and the store of phat in the direction: 23 n.  s lives in r; phat and shat are vectors only with a preconditioner:
 // 5 work vectors (r, rhat, p, v, t), 7 with Jacobi.
+// With a block-Jacobi object (tilespmv_bicgstab_create_block; hip_precond.hip) the kernels run with dinv = NULL and phat, shat are filled by k_bj_apply: phat = M^-1 p
+// at the end of begin and after k_bi_direction, shat = M^-1 s after k_bi_half — 7 work vectors, 18 n + 2 (bs + 2) n elements.  Under a guard that froze the vectors the applies write the
+// same bits again.
 // The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail are those of hip_solver_common.h; the number of partials
 // is solver_parts(n).  alpha, omega and beta are formed in double and rounded to the value type once, where they multiply.
 //
@@ -30,6 +33,7 @@
 // The iteration counter advances in every iteration whatever the guards did.
 #include <hip/hip_runtime.h>
 
+#include "hip_precond.h"
 #include "hip_solver_common.h"
 
 namespace tilespmv {
@@ -301,6 +305,7 @@ struct tilespmv_bicgstab {
     long long n = 0;
     int np = 0;
     const val_t *dinv = nullptr;     // borrowed
+    const tilespmv_block_jacobi *bj = nullptr;   // borrowed (tilespmv_bicgstab_create_block; then dinv is NULL, and phat and shat are filled by k_bj_apply, hip_precond.hip)
     void *block = nullptr;           // the one allocation: the work vectors, the partial-sum arrays, the scalar block
     val_t *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *t = nullptr;
     val_t *phat = nullptr, *shat = nullptr;   // vectors of their own with a preconditioner; without: phat is p, shat is NULL (s itself, in r)
@@ -308,26 +313,26 @@ struct tilespmv_bicgstab {
     BiScal *S = nullptr;
 };
 
-extern "C" int tilespmv_bicgstab_create(tilespmv_bicgstab **bs, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv)
+// the two creates: a diagonal (d_dinv, may be NULL) or a block-Jacobi object (bj), never both
+static int bi_create(tilespmv_bicgstab **bs, tilespmv_plan *plan, const val_t *d_dinv, const tilespmv_block_jacobi *bj)
 {
-    if (bs) *bs = nullptr;
-    if (!bs || !plan) return (int)hipErrorInvalidValue;
     const long long n = plan->matrix_rows;
     if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
-    if (misaligned(d_dinv)) return (int)hipErrorInvalidValue;
+    if (misaligned(d_dinv) || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
     const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    const bool hats = d_dinv || bj;
     DeviceBlock blk;
-    const hipError_t e = blk.alloc((d_dinv ? 7 : 5) * vec + 6 * parts + 256);
+    const hipError_t e = blk.alloc((hats ? 7 : 5) * vec + 6 * parts + 256);
     if (e != hipSuccess) return (int)e;
     auto *c = new tilespmv_bicgstab();
-    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->block = blk.base;
+    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->bj = bj; c->block = blk.base;
     c->r = blk.take<val_t>(vec);
     c->rhat = blk.take<val_t>(vec);
     c->p = blk.take<val_t>(vec);
     c->v = blk.take<val_t>(vec);
     c->t = blk.take<val_t>(vec);
-    c->phat = d_dinv ? blk.take<val_t>(vec) : c->p;
-    c->shat = d_dinv ? blk.take<val_t>(vec) : nullptr;
+    c->phat = hats ? blk.take<val_t>(vec) : c->p;
+    c->shat = hats ? blk.take<val_t>(vec) : nullptr;
     c->psig = blk.take<double>(parts);
     c->pts = blk.take<double>(parts);
     c->ptt = blk.take<double>(parts);
@@ -337,6 +342,20 @@ extern "C" int tilespmv_bicgstab_create(tilespmv_bicgstab **bs, tilespmv_plan *p
     c->S = blk.take<BiScal>(256);
     *bs = c;
     return 0;
+}
+
+extern "C" int tilespmv_bicgstab_create(tilespmv_bicgstab **bs, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv)
+{
+    if (bs) *bs = nullptr;
+    if (!bs || !plan) return (int)hipErrorInvalidValue;
+    return bi_create(bs, plan, d_dinv, nullptr);
+}
+
+extern "C" int tilespmv_bicgstab_create_block(tilespmv_bicgstab **bs, tilespmv_plan *plan, const tilespmv_block_jacobi *bj)
+{
+    if (bs) *bs = nullptr;
+    if (!bs || !plan || !bj) return (int)hipErrorInvalidValue;
+    return bi_create(bs, plan, nullptr, bj);
 }
 
 extern "C" void tilespmv_bicgstab_destroy(tilespmv_bicgstab *bs)
@@ -355,6 +374,7 @@ extern "C" int tilespmv_bicgstab_begin(tilespmv_bicgstab *bs, const MAT_VAL_TYPE
     hipLaunchKernelGGL(k_bi_begin, dim3(bs->np), dim3(SVB), 0, st, bs->n, d_b, bs->v, bs->r, bs->rhat, bs->p, bs->dinv, bs->dinv ? bs->phat : (val_t *)nullptr, bs->prr, bs->prho,
                        bs->pbb);
     hipLaunchKernelGGL(k_bi_begin_fold, dim3(1), dim3(SVB), 0, st, bs->prr, bs->pbb, bs->np, bs->S);
+    if (bs->bj) block_jacobi_launch(bs->bj, bs->p, bs->phat, nullptr, st);   // phat = M^-1 p
     return (int)hipGetLastError();
 }
 
@@ -369,11 +389,13 @@ extern "C" int tilespmv_bicgstab_iterate(tilespmv_bicgstab *bs, MAT_VAL_TYPE *d_
         if (rc) return rc;
         hipLaunchKernelGGL(k_bi_dot1, grid, wg, 0, st, bs->n, bs->rhat, bs->v, bs->psig, bs->prho, bs->prr, bs->np, bs->S);
         hipLaunchKernelGGL(k_bi_half, grid, wg, 0, st, bs->n, bs->r, bs->v, bs->dinv, bs->shat, bs->psig, bs->np, bs->S);
+        if (bs->bj) block_jacobi_launch(bs->bj, bs->r, bs->shat, nullptr, st);               // shat = M^-1 s (under a guard that froze the vectors: the same bits again)
         rc = tilespmv_plan_spmv(bs->plan, bs->shat ? bs->shat : bs->r, bs->t, stream);        // t = A shat
         if (rc) return rc;
         hipLaunchKernelGGL(k_bi_dot2, grid, wg, 0, st, bs->n, bs->t, bs->r, bs->pts, bs->ptt, bs->psig, bs->np, bs->S);
         hipLaunchKernelGGL(k_bi_update, grid, wg, 0, st, bs->n, d_x, bs->phat, bs->r, bs->shat, bs->t, bs->rhat, bs->pts, bs->ptt, bs->prr, bs->prho, bs->np, bs->S);
         hipLaunchKernelGGL(k_bi_direction, grid, wg, 0, st, bs->n, bs->r, bs->p, bs->v, bs->dinv, phat_out, bs->pts, bs->ptt, bs->prr, bs->prho, bs->np, bs->S);
+        if (bs->bj) block_jacobi_launch(bs->bj, bs->p, bs->phat, nullptr, st);               // phat = M^-1 p
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }

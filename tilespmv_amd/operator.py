@@ -150,17 +150,20 @@ class SparseOperator:
         self.A.update_values(d_vals, st)
         self.AT.update_values(d_vals, st)
 
-    def cg(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None):
+    def cg(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None, precond=None):
         """A x = b by conjugate gradients in the library (``api.CG`` over the plan of A: symmetric positive definite A) — the product and three fused kernels per
         iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: the inverse
         diagonal as a CUDA vector (Jacobi; ``api.csr_diagonal_device(..., invert=True)`` makes it), None = plain CG.  Stops at ``sqrt(rr / bb) <= rtol`` or after ``maxiter``
         iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}``.
-        A contiguous 2-D ``b`` of shape (rows, k) solves k systems at once (``_cg_multi``): ``(X, [info] * k)``."""
+        A contiguous 2-D ``b`` of shape (rows, k) solves k systems at once (``_cg_multi``): ``(X, [info] * k)``.
+        ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv`` (block Jacobi; a 1-D ``b`` only)."""
         import torch
         rows, cols = self.shape
         if rows != cols:
             raise ValueError("cg needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
         if b.dim() == 2:
+            if precond is not None:
+                raise ValueError("precond (block Jacobi) applies to a 1-D b only")
             return self._cg_multi(b, x0, rtol, maxiter, check_every, dinv, stream)
         if b.dim() != 1 or b.numel() != rows or not b.is_contiguous():
             raise ValueError("b must be a contiguous vector of %d elements" % rows)
@@ -171,7 +174,7 @@ class SparseOperator:
         if x0 is not None:
             x.copy_(x0)
         st = _stream(stream)
-        solver = api.CG(self.A, None if dinv is None else dinv.data_ptr())
+        solver = api.CG(self.A, None if dinv is None else dinv.data_ptr(), block=precond)
         try:
             s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
         finally:
@@ -258,16 +261,19 @@ class SparseOperator:
                 "converged": s["status"] == api.CG_CONVERGED, "status": s["status_name"]}
         return x, info
 
-    def bicgstab(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None):
+    def bicgstab(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None, precond=None):
         """A x = b for a square A that need not be symmetric, by BiCGStab in the library (``api.BiCGStab`` over the plan of A) — the two products and five fused
         kernels per iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a contiguous torch CUDA vector of ``rows`` elements;
         ``dinv``: the inverse diagonal as a CUDA vector (Jacobi, applied from the right; ``api.csr_diagonal_device(..., invert=True)`` makes it), None = unpreconditioned.  Stops at
         ``sqrt(rr / bb) <= rtol``, after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.  Returns ``(x, info)`` with ``info = {"iterations", "residual",
-        "relative_residual", "converged", "status"}`` (``residual``: the recurrence's ``|r|``)."""
+        "relative_residual", "converged", "status"}`` (``residual``: the recurrence's ``|r|``).  ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv``
+        (block Jacobi, applied from the right)."""
         import torch
         rows, cols = self.shape
         if rows != cols:
             raise ValueError("bicgstab needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
+        if precond is not None and _is_tensor(b) and b.dim() == 2:
+            raise ValueError("precond (block Jacobi) applies to a 1-D b only")
         if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
             raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
         if dinv is not None and (not _is_tensor(dinv) or dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
@@ -279,7 +285,7 @@ class SparseOperator:
         if x0 is not None:
             x.copy_(x0)
         st = _stream(stream)
-        solver = api.BiCGStab(self.A, None if dinv is None else dinv.data_ptr())
+        solver = api.BiCGStab(self.A, None if dinv is None else dinv.data_ptr(), block=precond)
         try:
             s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
         finally:
