@@ -178,70 +178,22 @@ def load(dtype=np.float64):
     lib.tilespmv_csr_transpose.restype = C.c_int
     lib.tilespmv_csr_transpose_device.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tilespmv_csr_transpose_device.restype = C.c_int
-    lib.tilespmv_cg_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
-    lib.tilespmv_cg_create.restype = C.c_int
-    lib.tilespmv_cg_destroy.argtypes = [C.c_void_p]
-    lib.tilespmv_cg_destroy.restype = None
-    lib.tilespmv_cg_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.tilespmv_cg_begin.restype = C.c_int
-    lib.tilespmv_cg_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.tilespmv_cg_iterate.restype = C.c_int
-    lib.tilespmv_cg_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_cg_state_read.restype = C.c_int
-    lib.tilespmv_cg_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_cg_solve.restype = C.c_int
-    lib.tilespmv_cg_multi_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
-    lib.tilespmv_cg_multi_create.restype = C.c_int
-    lib.tilespmv_cg_multi_destroy.argtypes = [C.c_void_p]
-    lib.tilespmv_cg_multi_destroy.restype = None
-    lib.tilespmv_cg_multi_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.tilespmv_cg_multi_begin.restype = C.c_int
-    lib.tilespmv_cg_multi_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.tilespmv_cg_multi_iterate.restype = C.c_int
-    lib.tilespmv_cg_multi_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_cg_multi_state_read.restype = C.c_int
-    lib.tilespmv_cg_multi_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_cg_multi_solve.restype = C.c_int
+    # the device-resident solvers: (prefix, state struct, what create takes behind the plan, what begin and solve take behind d_x)
+    for prefix, state, create_args, solve_args in (("cg", CGState, [C.c_void_p], []), ("cg_multi", CGState, [C.c_int, C.c_void_p], []),
+                                                   ("cgls", CGLSState, [C.c_void_p, C.c_void_p], [C.c_double]), ("bicgstab", CGState, [C.c_void_p], []),
+                                                   ("minres", CGState, [C.c_void_p], [])):
+        for what, restype, argtypes in (("create", C.c_int, [C.POINTER(C.c_void_p), C.c_void_p] + create_args),
+                                        ("destroy", None, [C.c_void_p]),
+                                        ("begin", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + solve_args + [C.c_void_p]),
+                                        ("iterate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+                                        ("state_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(state)]),
+                                        ("solve", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + solve_args + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(state)])):
+            fn = getattr(lib, "tilespmv_%s_%s" % (prefix, what))
+            fn.argtypes, fn.restype = argtypes, restype
     lib.tilespmv_csr_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_csr_diagonal_device.restype = C.c_int
-    lib.tilespmv_cgls_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.tilespmv_cgls_create.restype = C.c_int
-    lib.tilespmv_cgls_destroy.argtypes = [C.c_void_p]
-    lib.tilespmv_cgls_destroy.restype = None
-    lib.tilespmv_cgls_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
-    lib.tilespmv_cgls_begin.restype = C.c_int
-    lib.tilespmv_cgls_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.tilespmv_cgls_iterate.restype = C.c_int
-    lib.tilespmv_cgls_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGLSState)]
-    lib.tilespmv_cgls_state_read.restype = C.c_int
-    lib.tilespmv_cgls_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGLSState)]
-    lib.tilespmv_cgls_solve.restype = C.c_int
     lib.tilespmv_csr_row_sqnorms_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_csr_row_sqnorms_device.restype = C.c_int
-    lib.tilespmv_bicgstab_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
-    lib.tilespmv_bicgstab_create.restype = C.c_int
-    lib.tilespmv_bicgstab_destroy.argtypes = [C.c_void_p]
-    lib.tilespmv_bicgstab_destroy.restype = None
-    lib.tilespmv_bicgstab_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.tilespmv_bicgstab_begin.restype = C.c_int
-    lib.tilespmv_bicgstab_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.tilespmv_bicgstab_iterate.restype = C.c_int
-    lib.tilespmv_bicgstab_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_bicgstab_state_read.restype = C.c_int
-    lib.tilespmv_bicgstab_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_bicgstab_solve.restype = C.c_int
-    lib.tilespmv_minres_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
-    lib.tilespmv_minres_create.restype = C.c_int
-    lib.tilespmv_minres_destroy.argtypes = [C.c_void_p]
-    lib.tilespmv_minres_destroy.restype = None
-    lib.tilespmv_minres_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.tilespmv_minres_begin.restype = C.c_int
-    lib.tilespmv_minres_iterate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.tilespmv_minres_iterate.restype = C.c_int
-    lib.tilespmv_minres_state_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_minres_state_read.restype = C.c_int
-    lib.tilespmv_minres_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(CGState)]
-    lib.tilespmv_minres_solve.restype = C.c_int
     lib.tilespmv_csr_abs_diagonal_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_csr_abs_diagonal_device.restype = C.c_int
     lib.tilespmv_block_jacobi_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int]

@@ -517,15 +517,70 @@ def _block_handle(block, d_dinv, lib):
     return block.h
 
 
-class CG(_Solver):
+class _IterativeSolver(_Solver):
+    """``begin`` / ``iterate`` / ``state`` / ``solve`` of a device-resident solver over the entry points ``<_prefix>_{begin,iterate,state_read,solve,destroy}``.  A subclass names
+    the prefix, where it differs the state struct (``_State``) with its dict form (``_state``), and creates the handle; ``_begin`` and ``_solve`` take the arguments an entry point
+    has between ``d_x`` and the common ones (``extra``: the ``damp`` of ``CGLS``)."""
+
+    _State = _lib.CGState
+
+    @property
+    def _destroy(self):
+        return self._prefix + "_destroy"
+
+    @staticmethod
+    def _state(st):
+        rel = (st.rr / st.bb) ** 0.5 if st.bb > 0 else 0.0
+        return {"iterations": st.iterations, "status": st.status, "status_name": CG_STATUS_NAMES[st.status], "rr": st.rr, "bb": st.bb, "relative_residual": rel}
+
+    def _buffer(self):
+        """What ``state_read`` and ``solve`` fill."""
+        return self._State()
+
+    def _result(self, buf):
+        return self._state(buf)
+
+    def _call(self, what, *args):
+        name = "%s_%s" % (self._prefix, what)
+        self._check(getattr(self.lib, name)(self.h, *args), name)
+
+    def _begin(self, d_b, d_x, extra, stream):
+        self._call("begin", C.c_void_p(d_b), C.c_void_p(d_x), *extra, C.c_void_p(stream))
+
+    def _solve(self, d_b, d_x, extra, rtol, maxiter, check_every, stream):
+        buf = self._buffer()
+        self._call("solve", C.c_void_p(d_b), C.c_void_p(d_x), *extra, rtol, maxiter, check_every, C.c_void_p(stream), buf)
+        return self._result(buf)
+
+    def begin(self, d_b, d_x, stream=0):
+        """The start of a solve from the x that ``d_x`` holds: the residual and what the recurrence keeps beside it; asynchronous."""
+        self._begin(d_b, d_x, (), stream)
+
+    def iterate(self, d_x, count=1, stream=0):
+        """``count`` iterations; asynchronous, capturable into a graph."""
+        self._call("iterate", C.c_void_p(d_x), count, C.c_void_p(stream))
+
+    def state(self, stream=0):
+        """Synchronises ``stream``; the state as a dict (the class says which keys)."""
+        buf = self._buffer()
+        self._call("state_read", C.c_void_p(stream), buf)
+        return self._result(buf)
+
+    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
+        """``<prefix>_solve``; returns the final state (as ``state``)."""
+        return self._solve(d_b, d_x, (), rtol, maxiter, check_every, stream)
+
+
+class CG(_IterativeSolver):
     """``tilespmv_cg``: conjugate gradients around a resident plan, every scalar on the device (include/tilespmv.h).
 
     ``plan``: square and whole; it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal (Jacobi; borrowed), or None for plain CG.  ``block``: a
     ``BlockJacobi`` of the plan's rows instead of ``d_dinv`` (borrowed: keep it open while the solver is).  ``b`` / ``x``
     are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library returns
-    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``."""
+    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``.
+    ``begin``: r = b - A x, p = z.  ``state``: ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
 
-    _destroy = "tilespmv_cg_destroy"
+    _prefix = "tilespmv_cg"
     _hint = "the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
 
     def __init__(self, plan, d_dinv=None, block=None):
@@ -538,41 +593,17 @@ class CG(_Solver):
             self._check(self.lib.tilespmv_cg_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None)), "tilespmv_cg_create")
         self.h = h
 
-    @staticmethod
-    def _state(st):
-        rel = (st.rr / st.bb) ** 0.5 if st.bb > 0 else 0.0
-        return {"iterations": st.iterations, "status": st.status, "status_name": CG_STATUS_NAMES[st.status], "rr": st.rr, "bb": st.bb, "relative_residual": rel}
 
-    def begin(self, d_b, d_x, stream=0):
-        """r = b - A x, p = z; asynchronous."""
-        self._check(self.lib.tilespmv_cg_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)), "tilespmv_cg_begin")
-
-    def iterate(self, d_x, count=1, stream=0):
-        """``count`` iterations; asynchronous, capturable into a graph."""
-        self._check(self.lib.tilespmv_cg_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_cg_iterate")
-
-    def state(self, stream=0):
-        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
-        st = _lib.CGState()
-        self._check(self.lib.tilespmv_cg_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_cg_state_read")
-        return self._state(st)
-
-    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
-        """``tilespmv_cg_solve``; returns the final state (as ``state``)."""
-        st = _lib.CGState()
-        self._check(self.lib.tilespmv_cg_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)), "tilespmv_cg_solve")
-        return self._state(st)
-
-
-class CGMulti(_Solver):
+class CGMulti(_IterativeSolver):
     """``tilespmv_cg_multi``: conjugate gradients on ``nvec`` systems in lock-step around the multi-vector product, one set of device scalars per column (include/tilespmv.h,
     DESIGN.md §3.8).
 
     ``plan``: square and whole; it must stay open while the solver is.  ``nvec``: 1, 2, 4 or 8.  ``d_dinv``: device ADDRESS of the inverse diagonal (``rows`` elements, shared by
     the columns; borrowed), or None.  ``B`` / ``X`` are device addresses of row-major ``(rows, nvec)`` arrays, 16-byte aligned.  ``state`` and ``solve`` return a list of ``nvec``
-    dicts in the shape of ``CG.state``.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (another nvec, a shard, a non-square plan, a misaligned array)."""
+    dicts in the shape of ``CG.state``.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (another nvec, a shard, a non-square plan, a misaligned array).
+    ``begin``: R = B - A X, P = Z; ``iterate`` advances every column."""
 
-    _destroy = "tilespmv_cg_multi_destroy"
+    _prefix = "tilespmv_cg_multi"
     _hint = "nvec in {1, 2, 4, 8}; the plan must be square and whole; arrays 16-byte aligned"
 
     def __init__(self, plan, nvec, d_dinv=None):
@@ -582,30 +613,13 @@ class CGMulti(_Solver):
         self._check(rc, "tilespmv_cg_multi_create")
         self.h = h
 
-    def _states(self):
+    def _buffer(self):
         arr = (_lib.CGState * self.nvec)()
         arr[0].size = C.sizeof(_lib.CGState)
         return arr
 
-    def begin(self, d_B, d_X, stream=0):
-        """R = B - A X, P = Z; asynchronous."""
-        self._check(self.lib.tilespmv_cg_multi_begin(self.h, C.c_void_p(d_B), C.c_void_p(d_X), C.c_void_p(stream)), "tilespmv_cg_multi_begin")
-
-    def iterate(self, d_X, count=1, stream=0):
-        """``count`` iterations of every column; asynchronous, capturable into a graph."""
-        self._check(self.lib.tilespmv_cg_multi_iterate(self.h, C.c_void_p(d_X), count, C.c_void_p(stream)), "tilespmv_cg_multi_iterate")
-
-    def state(self, stream=0):
-        """Synchronises ``stream``; one dict per column."""
-        arr = self._states()
-        self._check(self.lib.tilespmv_cg_multi_state_read(self.h, C.c_void_p(stream), arr), "tilespmv_cg_multi_state_read")
-        return [CG._state(st) for st in arr]
-
-    def solve(self, d_B, d_X, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
-        """``tilespmv_cg_multi_solve``; returns the final state of every column."""
-        arr = self._states()
-        self._check(self.lib.tilespmv_cg_multi_solve(self.h, C.c_void_p(d_B), C.c_void_p(d_X), rtol, maxiter, check_every, C.c_void_p(stream), arr), "tilespmv_cg_multi_solve")
-        return [CG._state(st) for st in arr]
+    def _result(self, buf):
+        return [self._state(st) for st in buf]
 
 
 def csr_row_sqnorms_device(rows, d_rp, d_src, d_v, d_out, invert=False, stream=0, dtype=np.float64):
@@ -618,16 +632,18 @@ def csr_row_sqnorms_device(rows, d_rp, d_src, d_v, d_out, invert=False, stream=0
         raise RuntimeError("tilespmv_csr_row_sqnorms_device failed (hipError %d): bad argument, or no usable device" % rc)
 
 
-class CGLS(_Solver):
+class CGLS(_IterativeSolver):
     """``tilespmv_cgls``: least squares ``min |A x - b|^2 + damp^2 |x|^2`` by CGLS around the resident plans of A and A^T, every scalar on the device (include/tilespmv.h,
     DESIGN.md §3.9).  It mirrors ``CG``.
 
     ``plan_A`` (rows x cols) and ``plan_AT`` (cols x rows; ``transpose=True``, or any plan of the transposed CSR): whole plans; they must stay open while the solver is.
     ``d_cinv``: device ADDRESS of a positive diagonal of ``cols`` elements (column scaling: ``csr_row_sqnorms_device(..., invert=True)``; borrowed), or None.  ``b`` (rows) / ``x``
     (cols) are device addresses, 16-byte aligned.  The solver and its plans run on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue
-    (swapped or mismatched plans, a shard, a misaligned vector)."""
+    (swapped or mismatched plans, a shard, a misaligned vector).
+    ``state``: ``{"iterations", "status", "status_name", "nn", "nn0", "rr", "bb", "relative_normal_residual"}``."""
 
-    _destroy = "tilespmv_cgls_destroy"
+    _prefix = "tilespmv_cgls"
+    _State = _lib.CGLSState
     _hint = "whole plans of a rows x cols matrix and of its transpose; vectors 16-byte aligned"
 
     def __init__(self, plan_A, plan_AT, d_cinv=None):
@@ -647,36 +663,24 @@ class CGLS(_Solver):
 
     def begin(self, d_b, d_x, damp=0.0, stream=0):
         """r = b - A x, s = A^T r - damp^2 x, p = z; asynchronous.  ``damp`` holds for the ``iterate`` calls that follow."""
-        self._check(self.lib.tilespmv_cgls_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), damp, C.c_void_p(stream)), "tilespmv_cgls_begin")
-
-    def iterate(self, d_x, count=1, stream=0):
-        """``count`` iterations; asynchronous, capturable into a graph."""
-        self._check(self.lib.tilespmv_cgls_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_cgls_iterate")
-
-    def state(self, stream=0):
-        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "nn", "nn0", "rr", "bb", "relative_normal_residual"}``."""
-        st = _lib.CGLSState()
-        self._check(self.lib.tilespmv_cgls_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_cgls_state_read")
-        return self._state(st)
+        self._begin(d_b, d_x, (damp,), stream)
 
     def solve(self, d_b, d_x, damp=0.0, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
         """``tilespmv_cgls_solve``; returns the final state (as ``state``)."""
-        st = _lib.CGLSState()
-        self._check(self.lib.tilespmv_cgls_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), damp, rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
-                    "tilespmv_cgls_solve")
-        return self._state(st)
+        return self._solve(d_b, d_x, (damp,), rtol, maxiter, check_every, stream)
 
 
-class BiCGStab(_Solver):
+class BiCGStab(_IterativeSolver):
     """``tilespmv_bicgstab``: BiCGStab for a square, nonsymmetric A around a resident plan, right-preconditioned by a diagonal, every scalar on the device (include/tilespmv.h,
     DESIGN.md §3.10).  It mirrors ``CG``: the same state dict, the same statuses.
 
     ``plan``: square and whole (a square ``transpose=True`` plan solves ``A^T x = b``); it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal
     (Jacobi: ``csr_diagonal_device(..., invert=True)``; borrowed), or None.  ``block``: a ``BlockJacobi`` of the plan's rows instead of ``d_dinv`` (borrowed).
     ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library
-    returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``."""
+    returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``.
+    ``begin``: r = b - A x, rhat = p = r."""
 
-    _destroy = "tilespmv_bicgstab_destroy"
+    _prefix = "tilespmv_bicgstab"
     _hint = "the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
 
     def __init__(self, plan, d_dinv=None, block=None):
@@ -689,27 +693,6 @@ class BiCGStab(_Solver):
             self._check(self.lib.tilespmv_bicgstab_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None)), "tilespmv_bicgstab_create")
         self.h = h
 
-    def begin(self, d_b, d_x, stream=0):
-        """r = b - A x, rhat = p = r; asynchronous."""
-        self._check(self.lib.tilespmv_bicgstab_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)), "tilespmv_bicgstab_begin")
-
-    def iterate(self, d_x, count=1, stream=0):
-        """``count`` iterations; asynchronous, capturable into a graph."""
-        self._check(self.lib.tilespmv_bicgstab_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_bicgstab_iterate")
-
-    def state(self, stream=0):
-        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
-        st = _lib.CGState()
-        self._check(self.lib.tilespmv_bicgstab_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_bicgstab_state_read")
-        return CG._state(st)
-
-    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
-        """``tilespmv_bicgstab_solve``; returns the final state (as ``state``)."""
-        st = _lib.CGState()
-        self._check(self.lib.tilespmv_bicgstab_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
-                    "tilespmv_bicgstab_solve")
-        return CG._state(st)
-
 
 def csr_abs_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dtype=np.float64):
     """``tilespmv_csr_abs_diagonal_device``: ``csr_diagonal_device`` with the absolute value of the summed entries (i, i); ``invert=True``: ``1 / |d|``, 1 where d is 0 — a positive
@@ -720,15 +703,16 @@ def csr_abs_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0
         raise RuntimeError("tilespmv_csr_abs_diagonal_device failed (hipError %d): bad argument, or no usable device" % rc)
 
 
-class MINRES(_Solver):
+class MINRES(_IterativeSolver):
     """``tilespmv_minres``: MINRES for a square, symmetric A that may be indefinite (saddle-point and KKT systems) around a resident plan, preconditioned by a positive diagonal,
     every scalar on the device (include/tilespmv.h).  It mirrors ``CG``: the same state dict, the same statuses.  One product per iteration; ``rr`` never increases.
 
     ``plan``: square and whole; it must stay open while the solver is.  ``d_minv``: device ADDRESS of a POSITIVE diagonal M^-1 (``csr_abs_diagonal_device(..., invert=True)``;
     borrowed), or None.  With it ``rr`` is ``r.M^-1 r`` and ``bb`` is ``b.M^-1 b``.  ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its
-    plan run on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector)."""
+    plan run on one stream at a time.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector).
+    ``begin``: r2 = b - A x, z = minv o r2, beta = sqrt(r2.z)."""
 
-    _destroy = "tilespmv_minres_destroy"
+    _prefix = "tilespmv_minres"
     _hint = "the plan must be square and whole; vectors 16-byte aligned"
 
     def __init__(self, plan, d_minv=None):
@@ -737,27 +721,6 @@ class MINRES(_Solver):
         rc = self.lib.tilespmv_minres_create(C.byref(h), plan.h, C.c_void_p(d_minv or None))
         self._check(rc, "tilespmv_minres_create")
         self.h = h
-
-    def begin(self, d_b, d_x, stream=0):
-        """r2 = b - A x, z = minv o r2, beta = sqrt(r2.z); asynchronous."""
-        self._check(self.lib.tilespmv_minres_begin(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(stream)), "tilespmv_minres_begin")
-
-    def iterate(self, d_x, count=1, stream=0):
-        """``count`` iterations; asynchronous, capturable into a graph."""
-        self._check(self.lib.tilespmv_minres_iterate(self.h, C.c_void_p(d_x), count, C.c_void_p(stream)), "tilespmv_minres_iterate")
-
-    def state(self, stream=0):
-        """Synchronises ``stream``; ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
-        st = _lib.CGState()
-        self._check(self.lib.tilespmv_minres_state_read(self.h, C.c_void_p(stream), C.byref(st)), "tilespmv_minres_state_read")
-        return CG._state(st)
-
-    def solve(self, d_b, d_x, rtol=1e-10, maxiter=1000, check_every=8, stream=0):
-        """``tilespmv_minres_solve``; returns the final state (as ``state``)."""
-        st = _lib.CGState()
-        self._check(self.lib.tilespmv_minres_solve(self.h, C.c_void_p(d_b), C.c_void_p(d_x), rtol, maxiter, check_every, C.c_void_p(stream), C.byref(st)),
-                    "tilespmv_minres_solve")
-        return CG._state(st)
 
 
 def algorithmic_bytes(nnz, rows, cols, itemsize):

@@ -252,10 +252,9 @@ struct tilespmv_cg {
 // the two creates: a diagonal (d_dinv, may be NULL) or a block-Jacobi object (bj), never both
 static int cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const val_t *d_dinv, const tilespmv_block_jacobi *bj)
 {
-    const long long n = plan->matrix_rows;
-    if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
-    if (misaligned(d_dinv) || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
-    const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    const long long n = square_system(cg, plan, d_dinv);
+    if (!n || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
+    const size_t vec = vec_bytes(n), parts = SV_PARTS_BYTES;
     DeviceBlock blk;
     const hipError_t e = blk.alloc((bj ? 4 : 3) * vec + 4 * parts + 256);
     if (e != hipSuccess) return (int)e;
@@ -277,24 +276,19 @@ static int cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const val_t *d_dinv,
 
 extern "C" int tilespmv_cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv)
 {
-    if (cg) *cg = nullptr;
-    if (!cg || !plan) return (int)hipErrorInvalidValue;
     return cg_create(cg, plan, d_dinv, nullptr);
 }
 
 extern "C" int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, const tilespmv_block_jacobi *bj)
 {
-    if (cg) *cg = nullptr;
-    if (!cg || !plan || !bj) return (int)hipErrorInvalidValue;
+    if (!bj) {
+        if (cg) *cg = nullptr;
+        return (int)hipErrorInvalidValue;
+    }
     return cg_create(cg, plan, nullptr, bj);
 }
 
-extern "C" void tilespmv_cg_destroy(tilespmv_cg *cg)
-{
-    if (!cg) return;
-    (void)hipFree(cg->block);
-    delete cg;
-}
+extern "C" void tilespmv_cg_destroy(tilespmv_cg *cg) { destroy_solver(cg); }
 
 extern "C" int tilespmv_cg_begin(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream)
 {
@@ -330,48 +324,21 @@ extern "C" int tilespmv_cg_iterate(tilespmv_cg *cg, MAT_VAL_TYPE *d_x, int count
 
 extern "C" int tilespmv_cg_state_read(tilespmv_cg *cg, void *stream, tilespmv_cg_state *out)
 {
-    if (!cg || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
-    CgScal h;
-    const hipError_t e = read_scalars(&h, cg->S, sizeof(h), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    tilespmv_cg_state s;
-    s.iterations = h.iterations;
-    s.status = h.breakdown ? TILESPMV_CG_BREAKDOWN : h.rr == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
-    s.rr = h.rr; s.bb = h.bb;
-    put_versioned(out, out->size, 0, s);
-    return 0;
+    if (!cg) return (int)hipErrorInvalidValue;
+    return state_read(cg->S, (hipStream_t)stream, out, cg_state_of<CgScal>);
 }
 
 extern "C" int tilespmv_cg_solve(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
                                  tilespmv_cg_state *out)
 {
-    if (!cg || !out || out->size < sizeof(tilespmv_cg_state) || maxiter < 0) return (int)hipErrorInvalidValue;
-    if (check_every < 1) check_every = 1;
-    int rc = tilespmv_cg_begin(cg, d_b, d_x, stream);
-    if (rc) return rc;
-    for (;;) {
-        rc = tilespmv_cg_state_read(cg, stream, out);
-        if (rc) return rc;
-        if (out->status == TILESPMV_CG_BREAKDOWN) return 0;
-        if (out->bb == 0.0) {   // b = 0: the solution is 0
-            const hipError_t e = hipMemsetAsync(d_x, 0, (size_t)cg->n * sizeof(val_t), (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-            out->rr = 0.0; out->status = TILESPMV_CG_CONVERGED;
-            return (int)hipStreamSynchronize((hipStream_t)stream);
-        }
-        if (out->rr <= rtol * rtol * out->bb) { out->status = TILESPMV_CG_CONVERGED; return 0; }
-        if (out->iterations >= maxiter) { out->status = TILESPMV_CG_MAXITER; return 0; }
-        rc = tilespmv_cg_iterate(cg, d_x, std::min(check_every, maxiter - out->iterations), stream);
-        if (rc) return rc;
-    }
+    if (!cg) return (int)hipErrorInvalidValue;
+    return solve_loop<RrBbTest>(
+        out, d_x, cg->n, rtol, maxiter, check_every, (hipStream_t)stream, [&] { return tilespmv_cg_begin(cg, d_b, d_x, stream); },
+        [&] { return tilespmv_cg_state_read(cg, stream, out); }, [&](int count) { return tilespmv_cg_iterate(cg, d_x, count, stream); });
 }
 
 extern "C" int tilespmv_csr_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, MAT_VAL_TYPE *d_out, int invert,
                                             void *stream)
 {
-    if (rows < 0 || (rows > 0 && (!d_csrRowPtr || !d_csrColIdx || !d_csrVal || !d_out))) return (int)hipErrorInvalidValue;
-    if (tilespmv_device_count() <= 0) return (int)hipErrorNoDevice;
-    if (rows > 0)
-        hipLaunchKernelGGL(k_csr_diagonal, dim3((unsigned)((rows + SVB - 1) / SVB)), dim3(SVB), 0, (hipStream_t)stream, rows, d_csrRowPtr, d_csrColIdx, d_csrVal, d_out, invert);
-    return (int)hipGetLastError();
+    return launch_per_row(k_csr_diagonal, rows, d_csrRowPtr, d_csrColIdx, false, d_csrVal, d_out, invert, stream);
 }

@@ -316,10 +316,9 @@ struct tilespmv_bicgstab {
 // the two creates: a diagonal (d_dinv, may be NULL) or a block-Jacobi object (bj), never both
 static int bi_create(tilespmv_bicgstab **bs, tilespmv_plan *plan, const val_t *d_dinv, const tilespmv_block_jacobi *bj)
 {
-    const long long n = plan->matrix_rows;
-    if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
-    if (misaligned(d_dinv) || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
-    const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    const long long n = square_system(bs, plan, d_dinv);
+    if (!n || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
+    const size_t vec = vec_bytes(n), parts = SV_PARTS_BYTES;
     const bool hats = d_dinv || bj;
     DeviceBlock blk;
     const hipError_t e = blk.alloc((hats ? 7 : 5) * vec + 6 * parts + 256);
@@ -346,24 +345,19 @@ static int bi_create(tilespmv_bicgstab **bs, tilespmv_plan *plan, const val_t *d
 
 extern "C" int tilespmv_bicgstab_create(tilespmv_bicgstab **bs, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv)
 {
-    if (bs) *bs = nullptr;
-    if (!bs || !plan) return (int)hipErrorInvalidValue;
     return bi_create(bs, plan, d_dinv, nullptr);
 }
 
 extern "C" int tilespmv_bicgstab_create_block(tilespmv_bicgstab **bs, tilespmv_plan *plan, const tilespmv_block_jacobi *bj)
 {
-    if (bs) *bs = nullptr;
-    if (!bs || !plan || !bj) return (int)hipErrorInvalidValue;
+    if (!bj) {
+        if (bs) *bs = nullptr;
+        return (int)hipErrorInvalidValue;
+    }
     return bi_create(bs, plan, nullptr, bj);
 }
 
-extern "C" void tilespmv_bicgstab_destroy(tilespmv_bicgstab *bs)
-{
-    if (!bs) return;
-    (void)hipFree(bs->block);
-    delete bs;
-}
+extern "C" void tilespmv_bicgstab_destroy(tilespmv_bicgstab *bs) { destroy_solver(bs); }
 
 extern "C" int tilespmv_bicgstab_begin(tilespmv_bicgstab *bs, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream)
 {
@@ -404,38 +398,15 @@ extern "C" int tilespmv_bicgstab_iterate(tilespmv_bicgstab *bs, MAT_VAL_TYPE *d_
 
 extern "C" int tilespmv_bicgstab_state_read(tilespmv_bicgstab *bs, void *stream, tilespmv_cg_state *out)
 {
-    if (!bs || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
-    BiScal h;
-    const hipError_t e = read_scalars(&h, bs->S, sizeof(h), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    tilespmv_cg_state s;
-    s.iterations = h.iterations;
-    s.status = h.breakdown ? TILESPMV_CG_BREAKDOWN : h.rr == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
-    s.rr = h.rr; s.bb = h.bb;
-    put_versioned(out, out->size, 0, s);
-    return 0;
+    if (!bs) return (int)hipErrorInvalidValue;
+    return state_read(bs->S, (hipStream_t)stream, out, cg_state_of<BiScal>);
 }
 
 extern "C" int tilespmv_bicgstab_solve(tilespmv_bicgstab *bs, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
                                        tilespmv_cg_state *out)
 {
-    if (!bs || !out || out->size < sizeof(tilespmv_cg_state) || maxiter < 0) return (int)hipErrorInvalidValue;
-    if (check_every < 1) check_every = 1;
-    int rc = tilespmv_bicgstab_begin(bs, d_b, d_x, stream);
-    if (rc) return rc;
-    for (;;) {
-        rc = tilespmv_bicgstab_state_read(bs, stream, out);
-        if (rc) return rc;
-        if (out->status == TILESPMV_CG_BREAKDOWN) return 0;
-        if (out->bb == 0.0) {   // b = 0: the solution is 0
-            const hipError_t e = hipMemsetAsync(d_x, 0, (size_t)bs->n * sizeof(val_t), (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-            out->rr = 0.0; out->status = TILESPMV_CG_CONVERGED;
-            return (int)hipStreamSynchronize((hipStream_t)stream);
-        }
-        if (out->rr <= rtol * rtol * out->bb) { out->status = TILESPMV_CG_CONVERGED; return 0; }
-        if (out->iterations >= maxiter) { out->status = TILESPMV_CG_MAXITER; return 0; }
-        rc = tilespmv_bicgstab_iterate(bs, d_x, std::min(check_every, maxiter - out->iterations), stream);
-        if (rc) return rc;
-    }
+    if (!bs) return (int)hipErrorInvalidValue;
+    return solve_loop<RrBbTest>(
+        out, d_x, bs->n, rtol, maxiter, check_every, (hipStream_t)stream, [&] { return tilespmv_bicgstab_begin(bs, d_b, d_x, stream); },
+        [&] { return tilespmv_bicgstab_state_read(bs, stream, out); }, [&](int count) { return tilespmv_bicgstab_iterate(bs, d_x, count, stream); });
 }

@@ -1,5 +1,7 @@
 // hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip, hip_solver_bi.hip, hip_solver_mr.hip): the launch shape, the number of
-// partial sums, the reduction tree, the walk over a vector, and the host-side handling of the one allocation and of the versioned state structs.
+// partial sums, the reduction tree, the walk over a vector, and the host-side driver around the kernels: the one allocation (DeviceBlock), the versioned state structs (cg_state_of,
+// state_read, put_versioned), the loop of *_solve with its convergence test (solve_loop, RrBbTest), the start of a create and the end of a solver (square_system, destroy_solver),
+// and the one-thread-per-row launch of tilespmv_csr_*_device (launch_per_row).
 //
 // No scalar ever visits the host: a reducing kernel writes one partial per workgroup and the CONSUMING kernel folds the partials itself — every workgroup the same additions in the
 // same order, so all of them hold the same bits of the scalar; no finishing launch, no atomics.  The number of partials (solver_parts) and which elements a thread adds depend on the
@@ -108,6 +110,95 @@ template <class State> void put_versioned(State *out, unsigned stride, int j, St
 {
     s.size = stride;
     memcpy((char *)out + (size_t)j * stride, &s, std::min<size_t>(stride, sizeof(s)));
+}
+
+// ---- the host-side driver: what the extern "C" entry points of every solver do around their kernels (DESIGN.md §3.7 "The driver")
+
+constexpr size_t SV_PARTS_BYTES = (size_t)SV_MAX_PARTS * sizeof(double);   // one array of partial sums inside a solver's allocation
+
+// the status the device's scalars stand for (MAXITER is the solve loop's alone): `residual` is the squared norm whose exact zero means converged
+inline int device_status(int breakdown, double residual)
+{
+    return breakdown ? TILESPMV_CG_BREAKDOWN : residual == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
+}
+// a scalar block with iterations, breakdown, rr, bb as a whole tilespmv_cg_state
+template <class Scal> tilespmv_cg_state cg_state_of(const Scal &h)
+{
+    tilespmv_cg_state s;
+    s.size = sizeof(s);
+    s.iterations = h.iterations;
+    s.status = device_status(h.breakdown, h.rr);
+    s.rr = h.rr; s.bb = h.bb;
+    return s;
+}
+// *_state_read behind the handle's null check: the device's scalar block d_S, converted by `convert`, in the caller's struct of out->size bytes
+template <class Scal, class State> int state_read(const Scal *d_S, hipStream_t st, State *out, State (*convert)(const Scal &))
+{
+    if (!out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
+    Scal h;
+    const hipError_t e = read_scalars(&h, d_S, sizeof(h), st);
+    if (e != hipSuccess) return (int)e;
+    put_versioned(out, out->size, 0, convert(h));
+    return 0;
+}
+
+// The convergence test of a solve on tilespmv_cg_state: rr <= rtol^2 bb, and b = 0 has the solution 0.  (CGLS has its own on nn and nn0: hip_solver_ls.hip.)
+struct RrBbTest {
+    static double residual(const tilespmv_cg_state &s) { return s.rr; }
+    static double scale(const tilespmv_cg_state &s) { return s.bb; }
+    static void at_zero_scale(tilespmv_cg_state &s) { s.rr = 0.0; }
+};
+// *_solve of a single system behind the handle's null check.  begin(), read() (the solver's state_read into `out`) and iterate(count) are the solver's own entry points; d_x has
+// x_len elements.  Refusals come before any launch; one read, hence one synchronisation, per check_every iterations; the last batch is clipped to maxiter.
+template <class Test, class State, class Begin, class Read, class Iterate>
+int solve_loop(State *out, val_t *d_x, long long x_len, double rtol, int maxiter, int check_every, hipStream_t st, Begin begin, Read read, Iterate iterate)
+{
+    if (!out || out->size < sizeof(State) || maxiter < 0) return (int)hipErrorInvalidValue;
+    if (check_every < 1) check_every = 1;
+    int rc = begin();
+    if (rc) return rc;
+    for (;;) {
+        rc = read();
+        if (rc) return rc;
+        if (out->status == TILESPMV_CG_BREAKDOWN) return 0;
+        if (Test::scale(*out) == 0.0) {   // the solution is 0
+            const hipError_t e = hipMemsetAsync(d_x, 0, (size_t)x_len * sizeof(val_t), st);
+            if (e != hipSuccess) return (int)e;
+            Test::at_zero_scale(*out);
+            out->status = TILESPMV_CG_CONVERGED;
+            return (int)hipStreamSynchronize(st);
+        }
+        if (Test::residual(*out) <= rtol * rtol * Test::scale(*out)) { out->status = TILESPMV_CG_CONVERGED; return 0; }
+        if (out->iterations >= maxiter) { out->status = TILESPMV_CG_MAXITER; return 0; }
+        rc = iterate(std::min(check_every, maxiter - out->iterations));
+        if (rc) return rc;
+    }
+}
+
+// The start of a create for a square system: *out is NULL from here on unless the create succeeds; the plan is the whole of a square matrix, the borrowed diagonal (may be NULL)
+// is aligned.  Returns the number of rows, or 0: refuse with hipErrorInvalidValue.
+template <class Solver> long long square_system(Solver **out, const tilespmv_plan *plan, const void *d_diag)
+{
+    if (out) *out = nullptr;
+    if (!out || !plan) return 0;
+    const long long n = plan->matrix_rows;
+    return (n <= 0 || !whole_plan(plan, n, n) || misaligned(d_diag)) ? 0 : n;
+}
+// the end of a solver whose one allocation is `block`
+template <class Solver> void destroy_solver(Solver *s)
+{
+    if (!s) return;
+    (void)hipFree(s->block);
+    delete s;
+}
+
+// The tilespmv_csr_*_device entry points: kernel `k`, one thread per row of a device CSR.  idx (column indices, or positions in the value array) may be NULL where idx_optional.
+template <class Kernel> int launch_per_row(Kernel k, int rows, const int *d_rowPtr, const int *d_idx, bool idx_optional, const val_t *d_val, val_t *d_out, int invert, void *stream)
+{
+    if (rows < 0 || (rows > 0 && (!d_rowPtr || (!d_idx && !idx_optional) || !d_val || !d_out))) return (int)hipErrorInvalidValue;
+    if (tilespmv_device_count() <= 0) return (int)hipErrorNoDevice;
+    if (rows > 0) hipLaunchKernelGGL(k, dim3((unsigned)((rows + SVB - 1) / SVB)), dim3(SVB), 0, (hipStream_t)stream, rows, d_rowPtr, d_idx, d_val, d_out, invert);
+    return (int)hipGetLastError();
 }
 
 }  // namespace

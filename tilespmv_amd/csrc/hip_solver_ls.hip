@@ -302,7 +302,7 @@ extern "C" int tilespmv_cgls_create(tilespmv_cgls **ls, tilespmv_plan *plan_A, t
     const long long rows = plan_A->matrix_rows, cols = plan_A->dev.colA;
     if (rows <= 0 || cols <= 0 || !whole_plan(plan_A, rows, cols) || !whole_plan(plan_AT, cols, rows)) return (int)hipErrorInvalidValue;   // whole plans of a rows x cols matrix and its transpose
     if (misaligned(d_cinv)) return (int)hipErrorInvalidValue;
-    const size_t vr = vec_bytes(rows), vc = vec_bytes(cols), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    const size_t vr = vec_bytes(rows), vc = vec_bytes(cols), parts = SV_PARTS_BYTES;
     DeviceBlock blk;
     const hipError_t e = blk.alloc(2 * vr + 2 * vc + 7 * parts + 256);
     if (e != hipSuccess) return (int)e;
@@ -326,12 +326,7 @@ extern "C" int tilespmv_cgls_create(tilespmv_cgls **ls, tilespmv_plan *plan_A, t
     return 0;
 }
 
-extern "C" void tilespmv_cgls_destroy(tilespmv_cgls *ls)
-{
-    if (!ls) return;
-    (void)hipFree(ls->block);
-    delete ls;
-}
+extern "C" void tilespmv_cgls_destroy(tilespmv_cgls *ls) { destroy_solver(ls); }
 
 extern "C" int tilespmv_cgls_begin(tilespmv_cgls *ls, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double damp, void *stream)
 {
@@ -369,50 +364,40 @@ extern "C" int tilespmv_cgls_iterate(tilespmv_cgls *ls, MAT_VAL_TYPE *d_x, int c
     return 0;
 }
 
-extern "C" int tilespmv_cgls_state_read(tilespmv_cgls *ls, void *stream, tilespmv_cgls_state *out)
+// the scalar block as a whole tilespmv_cgls_state: converged is nn = 0, the normal residual
+static tilespmv_cgls_state cgls_state_of(const LsScal &h)
 {
-    if (!ls || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
-    LsScal h;
-    const hipError_t e = read_scalars(&h, ls->S, sizeof(h), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
     tilespmv_cgls_state s;
     memset(&s, 0, sizeof(s));
+    s.size = sizeof(s);
     s.iterations = h.iterations;
-    s.status = h.breakdown ? TILESPMV_CG_BREAKDOWN : h.nn == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
+    s.status = device_status(h.breakdown, h.nn);
     s.nn = h.nn; s.nn0 = h.nn0; s.rr = h.rr; s.bb = h.bb;
-    put_versioned(out, out->size, 0, s);
-    return 0;
+    return s;
+}
+// the convergence test of tilespmv_cgls_solve: nn <= rtol^2 nn0, and A^T b = 0 (b = 0, or b orthogonal to the range of A) has the solution 0, whose residual is b
+struct NormalTest {
+    static double residual(const tilespmv_cgls_state &s) { return s.nn; }
+    static double scale(const tilespmv_cgls_state &s) { return s.nn0; }
+    static void at_zero_scale(tilespmv_cgls_state &s) { s.nn = 0.0; s.rr = s.bb; }
+};
+
+extern "C" int tilespmv_cgls_state_read(tilespmv_cgls *ls, void *stream, tilespmv_cgls_state *out)
+{
+    if (!ls) return (int)hipErrorInvalidValue;
+    return state_read(ls->S, (hipStream_t)stream, out, cgls_state_of);
 }
 
 extern "C" int tilespmv_cgls_solve(tilespmv_cgls *ls, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double damp, double rtol, int maxiter, int check_every, void *stream,
                                    tilespmv_cgls_state *out)
 {
-    if (!ls || !out || out->size < sizeof(tilespmv_cgls_state) || maxiter < 0) return (int)hipErrorInvalidValue;
-    if (check_every < 1) check_every = 1;
-    int rc = tilespmv_cgls_begin(ls, d_b, d_x, damp, stream);
-    if (rc) return rc;
-    for (;;) {
-        rc = tilespmv_cgls_state_read(ls, stream, out);
-        if (rc) return rc;
-        if (out->status == TILESPMV_CG_BREAKDOWN) return 0;
-        if (out->nn0 == 0.0) {   // A^T b = 0 (b = 0, or b orthogonal to the range of A): the solution is 0
-            const hipError_t e = hipMemsetAsync(d_x, 0, (size_t)ls->cols * sizeof(val_t), (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-            out->nn = 0.0; out->rr = out->bb; out->status = TILESPMV_CG_CONVERGED;
-            return (int)hipStreamSynchronize((hipStream_t)stream);
-        }
-        if (out->nn <= rtol * rtol * out->nn0) { out->status = TILESPMV_CG_CONVERGED; return 0; }
-        if (out->iterations >= maxiter) { out->status = TILESPMV_CG_MAXITER; return 0; }
-        rc = tilespmv_cgls_iterate(ls, d_x, std::min(check_every, maxiter - out->iterations), stream);
-        if (rc) return rc;
-    }
+    if (!ls) return (int)hipErrorInvalidValue;
+    return solve_loop<NormalTest>(
+        out, d_x, ls->cols, rtol, maxiter, check_every, (hipStream_t)stream, [&] { return tilespmv_cgls_begin(ls, d_b, d_x, damp, stream); },
+        [&] { return tilespmv_cgls_state_read(ls, stream, out); }, [&](int count) { return tilespmv_cgls_iterate(ls, d_x, count, stream); });
 }
 
 extern "C" int tilespmv_csr_row_sqnorms_device(int rows, const MAT_PTR_TYPE *d_rowPtr, const int *d_src, const MAT_VAL_TYPE *d_val, MAT_VAL_TYPE *d_out, int invert, void *stream)
 {
-    if (rows < 0 || (rows > 0 && (!d_rowPtr || !d_val || !d_out))) return (int)hipErrorInvalidValue;
-    if (tilespmv_device_count() <= 0) return (int)hipErrorNoDevice;
-    if (rows > 0)
-        hipLaunchKernelGGL(k_csr_row_sqnorms, dim3((unsigned)((rows + SVB - 1) / SVB)), dim3(SVB), 0, (hipStream_t)stream, rows, d_rowPtr, d_src, d_val, d_out, invert);
-    return (int)hipGetLastError();
+    return launch_per_row(k_csr_row_sqnorms, rows, d_rowPtr, d_src, true, d_val, d_out, invert, stream);
 }

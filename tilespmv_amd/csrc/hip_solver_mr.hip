@@ -271,12 +271,9 @@ struct tilespmv_minres {
 
 extern "C" int tilespmv_minres_create(tilespmv_minres **ms, tilespmv_plan *plan, const MAT_VAL_TYPE *d_minv)
 {
-    if (ms) *ms = nullptr;
-    if (!ms || !plan) return (int)hipErrorInvalidValue;
-    const long long n = plan->matrix_rows;
-    if (n <= 0 || !whole_plan(plan, n, n)) return (int)hipErrorInvalidValue;   // square, whole matrix
-    if (misaligned(d_minv)) return (int)hipErrorInvalidValue;
-    const size_t vec = vec_bytes(n), parts = (size_t)SV_MAX_PARTS * sizeof(double);
+    const long long n = square_system(ms, plan, d_minv);
+    if (!n) return (int)hipErrorInvalidValue;
+    const size_t vec = vec_bytes(n), parts = SV_PARTS_BYTES;
     static_assert(sizeof(MrScal) <= 256, "the scalar block has 256 bytes");
     DeviceBlock blk;
     const hipError_t e = blk.alloc(6 * vec + 2 * parts + 256);
@@ -296,12 +293,7 @@ extern "C" int tilespmv_minres_create(tilespmv_minres **ms, tilespmv_plan *plan,
     return 0;
 }
 
-extern "C" void tilespmv_minres_destroy(tilespmv_minres *ms)
-{
-    if (!ms) return;
-    (void)hipFree(ms->block);
-    delete ms;
-}
+extern "C" void tilespmv_minres_destroy(tilespmv_minres *ms) { destroy_solver(ms); }
 
 extern "C" int tilespmv_minres_begin(tilespmv_minres *ms, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream)
 {
@@ -333,49 +325,21 @@ extern "C" int tilespmv_minres_iterate(tilespmv_minres *ms, MAT_VAL_TYPE *d_x, i
 
 extern "C" int tilespmv_minres_state_read(tilespmv_minres *ms, void *stream, tilespmv_cg_state *out)
 {
-    if (!ms || !out || out->size < 3 * sizeof(int)) return (int)hipErrorInvalidValue;
-    MrScal h;
-    const hipError_t e = read_scalars(&h, ms->S, sizeof(h), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    tilespmv_cg_state s;
-    s.iterations = h.iterations;
-    s.status = h.breakdown ? TILESPMV_CG_BREAKDOWN : h.rr == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
-    s.rr = h.rr; s.bb = h.bb;
-    put_versioned(out, out->size, 0, s);
-    return 0;
+    if (!ms) return (int)hipErrorInvalidValue;
+    return state_read(ms->S, (hipStream_t)stream, out, cg_state_of<MrScal>);
 }
 
 extern "C" int tilespmv_minres_solve(tilespmv_minres *ms, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
                                      tilespmv_cg_state *out)
 {
-    if (!ms || !out || out->size < sizeof(tilespmv_cg_state) || maxiter < 0) return (int)hipErrorInvalidValue;
-    if (check_every < 1) check_every = 1;
-    int rc = tilespmv_minres_begin(ms, d_b, d_x, stream);
-    if (rc) return rc;
-    for (;;) {
-        rc = tilespmv_minres_state_read(ms, stream, out);
-        if (rc) return rc;
-        if (out->status == TILESPMV_CG_BREAKDOWN) return 0;
-        if (out->bb == 0.0) {   // b = 0: the solution is 0
-            const hipError_t e = hipMemsetAsync(d_x, 0, (size_t)ms->n * sizeof(val_t), (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-            out->rr = 0.0; out->status = TILESPMV_CG_CONVERGED;
-            return (int)hipStreamSynchronize((hipStream_t)stream);
-        }
-        if (out->rr <= rtol * rtol * out->bb) { out->status = TILESPMV_CG_CONVERGED; return 0; }
-        if (out->iterations >= maxiter) { out->status = TILESPMV_CG_MAXITER; return 0; }
-        rc = tilespmv_minres_iterate(ms, d_x, std::min(check_every, maxiter - out->iterations), stream);
-        if (rc) return rc;
-    }
+    if (!ms) return (int)hipErrorInvalidValue;
+    return solve_loop<RrBbTest>(
+        out, d_x, ms->n, rtol, maxiter, check_every, (hipStream_t)stream, [&] { return tilespmv_minres_begin(ms, d_b, d_x, stream); },
+        [&] { return tilespmv_minres_state_read(ms, stream, out); }, [&](int count) { return tilespmv_minres_iterate(ms, d_x, count, stream); });
 }
 
 extern "C" int tilespmv_csr_abs_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, MAT_VAL_TYPE *d_out, int invert,
                                                 void *stream)
 {
-    if (rows < 0 || (rows > 0 && (!d_csrRowPtr || !d_csrColIdx || !d_csrVal || !d_out))) return (int)hipErrorInvalidValue;
-    if (tilespmv_device_count() <= 0) return (int)hipErrorNoDevice;
-    if (rows > 0)
-        hipLaunchKernelGGL(k_csr_abs_diagonal, dim3((unsigned)((rows + SVB - 1) / SVB)), dim3(SVB), 0, (hipStream_t)stream, rows, d_csrRowPtr, d_csrColIdx, d_csrVal, d_out,
-                           invert);
-    return (int)hipGetLastError();
+    return launch_per_row(k_csr_abs_diagonal, rows, d_csrRowPtr, d_csrColIdx, false, d_csrVal, d_out, invert, stream);
 }

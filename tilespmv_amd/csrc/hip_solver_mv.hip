@@ -389,12 +389,7 @@ int read_columns(const tilespmv_cg_multi *c, hipStream_t st, tilespmv_cg_state *
     CgmScal h[MAX_NVEC];
     const hipError_t e = read_scalars(h, c->S, sizeof(CgmScal) * c->nvec, st);
     if (e != hipSuccess) return (int)e;
-    for (int j = 0; j < c->nvec; j++) {
-        cols[j].size = sizeof(tilespmv_cg_state);
-        cols[j].iterations = h[j].iterations;
-        cols[j].status = h[j].breakdown ? TILESPMV_CG_BREAKDOWN : h[j].rr == 0.0 ? TILESPMV_CG_CONVERGED : TILESPMV_CG_RUNNING;
-        cols[j].rr = h[j].rr; cols[j].bb = h[j].bb;
-    }
+    for (int j = 0; j < c->nvec; j++) cols[j] = cg_state_of(h[j]);
     return 0;
 }
 
@@ -403,11 +398,9 @@ int read_columns(const tilespmv_cg_multi *c, hipStream_t st, tilespmv_cg_state *
 extern "C" int tilespmv_cg_multi_create(tilespmv_cg_multi **cg, tilespmv_plan *plan, int nvec, const MAT_VAL_TYPE *d_dinv)
 {
     if (cg) *cg = nullptr;
-    if (!cg || !plan) return (int)hipErrorInvalidValue;
     if (nvec != 1 && nvec != 2 && nvec != 4 && nvec != 8) return (int)hipErrorInvalidValue;   // (before the plan is touched)
-    const long long rows = plan->matrix_rows;
-    if (rows <= 0 || !whole_plan(plan, rows, rows)) return (int)hipErrorInvalidValue;   // square, whole matrix
-    if (misaligned(d_dinv)) return (int)hipErrorInvalidValue;
+    const long long rows = square_system(cg, plan, d_dinv);
+    if (!rows) return (int)hipErrorInvalidValue;
     if (nvec == 1) {
         tilespmv_cg *one = nullptr;
         const int rc = tilespmv_cg_create(&one, plan, d_dinv);
@@ -419,7 +412,7 @@ extern "C" int tilespmv_cg_multi_create(tilespmv_cg_multi **cg, tilespmv_plan *p
     }
     int rc = tilespmv_plan_reserve_spmm(plan, nvec);   // plans that multiply one right-hand side at a time: their scratch now, so that iterate never allocates
     if (rc) return rc;
-    const size_t vec = vec_bytes(rows, nvec), parts = (size_t)SV_MAX_PARTS * nvec * sizeof(double), scal = ((size_t)nvec * sizeof(CgmScal) + 255) / 256 * 256;
+    const size_t vec = vec_bytes(rows, nvec), parts = SV_PARTS_BYTES * nvec, scal = ((size_t)nvec * sizeof(CgmScal) + 255) / 256 * 256;
     DeviceBlock blk;
     const hipError_t e = blk.alloc(3 * vec + 4 * parts + scal);
     if (e != hipSuccess) return (int)e;

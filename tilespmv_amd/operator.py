@@ -35,6 +35,12 @@ def _stream(stream):
     return torch.cuda.current_stream().cuda_stream
 
 
+def _info(s):
+    """The info dict of ``cg``, ``bicgstab`` and ``minres`` from the solver's state dict (the rr of MINRES is r.M^-1 r, below 0 at a breakdown under a ``minv`` that is not positive: the residual is 0 then)."""
+    return {"iterations": s["iterations"], "residual": max(s["rr"], 0.0) ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
+            "status": s["status_name"]}
+
+
 class SparseOperator:
     """The plans of A (``rows x cols``) and of A^T from one CSR.
 
@@ -150,6 +156,34 @@ class SparseOperator:
         self.A.update_values(d_vals, st)
         self.AT.update_values(d_vals, st)
 
+    def _square(self, what):
+        rows, cols = self.shape
+        if rows != cols:
+            raise ValueError("%s needs a square operator; this one is %d x %d (least squares: cgls)" % (what, rows, cols))
+
+    def _solve(self, make, b, x0, n, scaling_name, scaling, stream, maxiter=None, **solve_args):
+        """What ``cg`` (1-D ``b``), ``bicgstab``, ``minres`` and ``cgls`` share: ``b`` is a contiguous CUDA vector of ``rows`` elements of the operator's type; the diagonal
+        ``scaling`` (or None) and ``x0`` (or None: zeros) have the ``n`` elements of x and b's type; ``maxiter`` defaults to ``2 * n``.  ``make(address of the diagonal or None)``
+        creates the ``api`` solver, which lives for the one ``solve``.  Returns ``(x, the solver's final state dict)``."""
+        import torch
+        rows = self.shape[0]
+        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
+            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
+        if scaling is not None and (not _is_tensor(scaling) or scaling.numel() != n or not scaling.is_contiguous() or scaling.dtype != b.dtype):
+            raise ValueError("%s must be a contiguous vector of %d elements of b's type" % (scaling_name, n))
+        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != n or x0.dtype != b.dtype):
+            raise ValueError("x0 must be a vector of %d elements of b's type" % n)
+        x = torch.zeros(n + 16, dtype=b.dtype, device=b.device)[:n]
+        if x0 is not None:
+            x.copy_(x0)
+        st = _stream(stream)
+        solver = make(None if scaling is None else scaling.data_ptr())
+        try:
+            s = solver.solve(b.data_ptr(), x.data_ptr(), maxiter=2 * n if maxiter is None else maxiter, stream=st, **solve_args)
+        finally:
+            solver.close()
+        return x, s
+
     def cg(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, dinv=None, stream=None, precond=None):
         """A x = b by conjugate gradients in the library (``api.CG`` over the plan of A: symmetric positive definite A) — the product and three fused kernels per
         iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: the inverse
@@ -157,31 +191,13 @@ class SparseOperator:
         iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}``.
         A contiguous 2-D ``b`` of shape (rows, k) solves k systems at once (``_cg_multi``): ``(X, [info] * k)``.
         ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv`` (block Jacobi; a 1-D ``b`` only)."""
-        import torch
-        rows, cols = self.shape
-        if rows != cols:
-            raise ValueError("cg needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
-        if b.dim() == 2:
+        self._square("cg")
+        if _is_tensor(b) and b.dim() == 2:
             if precond is not None:
                 raise ValueError("precond (block Jacobi) applies to a 1-D b only")
             return self._cg_multi(b, x0, rtol, maxiter, check_every, dinv, stream)
-        if b.dim() != 1 or b.numel() != rows or not b.is_contiguous():
-            raise ValueError("b must be a contiguous vector of %d elements" % rows)
-        if dinv is not None and (dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
-            raise ValueError("dinv must be a contiguous vector of %d elements of b's type" % rows)
-        maxiter = 2 * rows if maxiter is None else maxiter
-        x = torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
-        if x0 is not None:
-            x.copy_(x0)
-        st = _stream(stream)
-        solver = api.CG(self.A, None if dinv is None else dinv.data_ptr(), block=precond)
-        try:
-            s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
-        finally:
-            solver.close()
-        info = {"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
-                "status": s["status_name"]}
-        return x, info
+        x, s = self._solve(lambda d: api.CG(self.A, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
+        return x, _info(s)
 
     @staticmethod
     def cg_groups(k):
@@ -239,24 +255,7 @@ class SparseOperator:
         positive diagonal of ``cols`` elements as a CUDA vector (column scaling; ``api.csr_row_sqnorms_device(..., invert=True)`` makes it), None = unpreconditioned.  Stops at
         ``|A^T r - damp^2 x| <= rtol |A^T b|`` or after ``maxiter`` iterations (default ``2 * cols``).  Returns ``(x, info)`` with ``info = {"iterations", "normal_residual",
         "relative_normal_residual", "residual", "converged", "status"}`` (``residual``: the recurrence's ``|r|``)."""
-        import torch
-        rows, cols = self.shape
-        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
-            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
-        if cinv is not None and (not _is_tensor(cinv) or cinv.numel() != cols or not cinv.is_contiguous() or cinv.dtype != b.dtype):
-            raise ValueError("cinv must be a contiguous vector of %d elements of b's type" % cols)
-        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != cols or x0.dtype != b.dtype):
-            raise ValueError("x0 must be a vector of %d elements of b's type" % cols)
-        maxiter = 2 * cols if maxiter is None else maxiter
-        x = torch.zeros(cols + 16, dtype=b.dtype, device=b.device)[:cols]
-        if x0 is not None:
-            x.copy_(x0)
-        st = _stream(stream)
-        solver = api.CGLS(self.A, self.AT, None if cinv is None else cinv.data_ptr())
-        try:
-            s = solver.solve(b.data_ptr(), x.data_ptr(), damp=damp, rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
-        finally:
-            solver.close()
+        x, s = self._solve(lambda d: api.CGLS(self.A, self.AT, d), b, x0, self.shape[1], "cinv", cinv, stream, damp=damp, rtol=rtol, maxiter=maxiter, check_every=check_every)
         info = {"iterations": s["iterations"], "normal_residual": s["nn"] ** 0.5, "relative_normal_residual": s["relative_normal_residual"], "residual": s["rr"] ** 0.5,
                 "converged": s["status"] == api.CG_CONVERGED, "status": s["status_name"]}
         return x, info
@@ -268,31 +267,11 @@ class SparseOperator:
         ``sqrt(rr / bb) <= rtol``, after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.  Returns ``(x, info)`` with ``info = {"iterations", "residual",
         "relative_residual", "converged", "status"}`` (``residual``: the recurrence's ``|r|``).  ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv``
         (block Jacobi, applied from the right)."""
-        import torch
-        rows, cols = self.shape
-        if rows != cols:
-            raise ValueError("bicgstab needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
+        self._square("bicgstab")
         if precond is not None and _is_tensor(b) and b.dim() == 2:
             raise ValueError("precond (block Jacobi) applies to a 1-D b only")
-        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
-            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
-        if dinv is not None and (not _is_tensor(dinv) or dinv.numel() != rows or not dinv.is_contiguous() or dinv.dtype != b.dtype):
-            raise ValueError("dinv must be a contiguous vector of %d elements of b's type" % rows)
-        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != rows or x0.dtype != b.dtype):
-            raise ValueError("x0 must be a vector of %d elements of b's type" % rows)
-        maxiter = 2 * rows if maxiter is None else maxiter
-        x = torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
-        if x0 is not None:
-            x.copy_(x0)
-        st = _stream(stream)
-        solver = api.BiCGStab(self.A, None if dinv is None else dinv.data_ptr(), block=precond)
-        try:
-            s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
-        finally:
-            solver.close()
-        info = {"iterations": s["iterations"], "residual": s["rr"] ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
-                "status": s["status_name"]}
-        return x, info
+        x, s = self._solve(lambda d: api.BiCGStab(self.A, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
+        return x, _info(s)
 
     def minres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, minv=None, stream=None):
         """A x = b for a square SYMMETRIC A that may be indefinite (saddle-point, KKT), by MINRES in the library (``api.MINRES`` over the plan of A) — one product
@@ -300,29 +279,9 @@ class SparseOperator:
         contiguous torch CUDA vector of ``rows`` elements; ``minv``: a POSITIVE diagonal M^-1 as a CUDA vector (``api.csr_abs_diagonal_device(..., invert=True)`` makes one),
         None = unpreconditioned.  Stops at ``sqrt(rr / bb) <= rtol`` (with ``minv``: in the M^-1 norm), after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.
         Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}`` (``residual``: the recurrence's ``sqrt(rr)``)."""
-        import torch
-        rows, cols = self.shape
-        if rows != cols:
-            raise ValueError("minres needs a square operator; this one is %d x %d (least squares: cgls)" % (rows, cols))
-        if not _is_tensor(b) or b.dim() != 1 or b.numel() != rows or not b.is_contiguous() or np.dtype(str(b.dtype).replace("torch.", "")) != self.dtype:
-            raise ValueError("b must be a contiguous %s vector of %d elements" % (self.dtype, rows))
-        if minv is not None and (not _is_tensor(minv) or minv.numel() != rows or not minv.is_contiguous() or minv.dtype != b.dtype):
-            raise ValueError("minv must be a contiguous vector of %d elements of b's type" % rows)
-        if x0 is not None and (not _is_tensor(x0) or x0.dim() != 1 or x0.numel() != rows or x0.dtype != b.dtype):
-            raise ValueError("x0 must be a vector of %d elements of b's type" % rows)
-        maxiter = 2 * rows if maxiter is None else maxiter
-        x = torch.zeros(rows + 16, dtype=b.dtype, device=b.device)[:rows]
-        if x0 is not None:
-            x.copy_(x0)
-        st = _stream(stream)
-        solver = api.MINRES(self.A, None if minv is None else minv.data_ptr())
-        try:
-            s = solver.solve(b.data_ptr(), x.data_ptr(), rtol=rtol, maxiter=maxiter, check_every=check_every, stream=st)
-        finally:
-            solver.close()
-        info = {"iterations": s["iterations"], "residual": max(s["rr"], 0.0) ** 0.5, "relative_residual": s["relative_residual"], "converged": s["status"] == api.CG_CONVERGED,
-                "status": s["status_name"]}
-        return x, info
+        self._square("minres")
+        x, s = self._solve(lambda d: api.MINRES(self.A, d), b, x0, self.shape[0], "minv", minv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
+        return x, _info(s)
 
     def close(self):
         for p in (getattr(self, "A", None), getattr(self, "AT", None)):
