@@ -386,13 +386,14 @@ void tilespmv_plan_destroy(tilespmv_plan *plan);
  * Tile_create_device: the host Tile_create computed by kernels — the CSR arrays go up, every member array of the Tile_matrix comes back, byte for byte what Tile_create /
  * Tile_create_ex builds (flags: TILESPMV_CREATE_QUIET, TILESPMV_CREATE_CDNA4, and since round 6 TILESPMV_CREATE_HYB — width search src/csr2tile.h:279-306, pack :505-548, index bytes
  * :984-1008 as per-tile device code).  Returns 0, -1 no HIP device (there is no CPU fallback behind this entry point: call Tile_create), -2 an offset leaves the int32 range
- * of Tile_matrix, -3 HIP error / out of device memory.
+ * of Tile_matrix, or a tile with a repeated position holds more than 255 entries ("Repeated entries" above tilespmv_plan_spmv: decided by the selection kernel, nothing is
+ * packed, *matrix is not written), -3 HIP error / out of device memory.
  *
  * tilespmv_plan_create_from_csr: CSR in, resident plan out, nothing but the CSR arrays crossing the bus — the tiled matrix is built on the device and stays there, the stages of the
  * plan builder that touch every nonzero run as kernels calling the same per-tile functions as the host builder, so the plan is the one tilespmv_plan_create makes from
  * Tile_create's output (same streams, same y).  Not every option has a device path: returns -4 (and builds nothing) for the first-generation kernel, the CSR fallback
  * mode and whole CSR tiles (csr_split = 0) — use Tile_create + tilespmv_plan_create for those (HYB tiles, TILESPMV_CREATE_HYB in `create_flags`, are served since round 6).  autotune = 1 is served: every candidate plan is built from the one device-resident tiled
- * matrix (the CSR-fallback candidate, which has no device path, is not among them).  Other return codes as above.
+ * matrix (the CSR-fallback candidate, which has no device path, is not among them).  Other return codes as above (-2 also for the refused tile: *plan stays NULL).
  * Peak device memory during the call: the CSR arrays + the tiled matrix + the sort's key buffers (about 40 bytes per nonzero in fp64) beside the plan.  With TILESPMV_CREATE_VALUE_MAP add
  * the value map (4 bytes per value slot of the plan — about 4.5 to 6 bytes per nonzero; it stays with the plan) and, for tilespmv_plan_create_from_device_csr, one more value array
  * (sizeof(MAT_VAL_TYPE) bytes per nonzero, freed before the call returns).  With TILESPMV_CREATE_TRANSPOSE add the transposed CSR (about 4 + sizeof(MAT_VAL_TYPE) bytes per
@@ -432,6 +433,16 @@ int tilespmv_plan_update_values(tilespmv_plan *plan, const MAT_VAL_TYPE *d_csrVa
  * lists (wavefront / workgroup entry modes, CSR fallback) pad a 64-record chunk that had to be closed early — its columns span 2^(32 - dest_bits)
  * (2^20 ... 2^23) or more, or, in slab-paced plans, the local part of a list ends — with null records (value 0, destination = the group's first
  * row, column = the chunk's first column): they add 0 * x[that column] to that row (tests/test_gpu_configs.py::test_non_finite_x_reaches_only_what_the_header_says).
+ *
+ * Repeated entries: a CSR may store the same (i, j) more than once (element contributions not yet summed, an uncoalesced framework CSR, a symmetric .mtx that lists an
+ * entry twice).  Nothing is summed at creation: every stored entry keeps a slot of its own, and y is the sum over ALL stored entries — tilespmv_cpu, every plan form, SpMV
+ * and SpMM, transposed plans, value-mapped plans before and after tilespmv_plan_update_values.  (1) A 16 x 16 tile without a repeated position is built exactly as before,
+ * byte for byte, also beside tiles that have one.  (2) A tile with a repeated position is never stored as DNS, DNSROW or DNSCOL (one value per position): it gets the
+ * format the selection rule gives with those three branches skipped — COO, ELL, HYB or CSR (an ELL / HYB width beyond 127, what tilewidth holds, becomes CSR).  (3) A tile
+ * with a repeated position and more than 255 entries is REFUSED: its in-tile row pointer and blknnznnz are bytes.  That covers a local row of 256 entries, where 8-bit row
+ * counters wrap (16 columns: it has repeats and at least 256 entries).  Entry points with a status return -2 and build nothing; Tile_create / Tile_create_ex are void and
+ * exit(2), as for an int32 offset overflow; both print "tilespmv: tile-row R, column block C: N entries with a repeated position ..." on stderr.  Sum duplicates first for
+ * such a matrix.  Not part of this: dense-row / dense-column tiles still assume ascending columns inside a row, as in the reference.
  *
  * y[16*tilerow_begin .. 16*tilerow_end) = A_shard * x.  d_x has colA elements, d_y points at
  * element 0 of the FULL-length y (the shard writes only its own rows).  Asynchronous on

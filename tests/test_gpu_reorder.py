@@ -21,7 +21,7 @@ def _square(gen):
     rows = (m // 16) * 16
     A = sp.csr_matrix((np.ones(int(rp[rows])), ci[:int(rp[rows])], rp[:rows + 1]), shape=(rows, n))[:, :rows].tocsr()
     A.sum_duplicates()   # a simple graph: with repeated (i, j) entries a renumbering that packs hub rows and popular columns into one 16 x 16 tile can put more than 255 entries
-    return rows, A.indptr.astype(np.int32), A.indices.astype(np.int32)   # there, which the reference's unsigned-char tile counters do not hold (SURVEY S8c "input hazards")
+    return rows, A.indptr.astype(np.int32), A.indices.astype(np.int32)   # there, which a tile with repeated positions does not serve (include/tilespmv.h "Repeated entries": refused with -2; tests/test_gpu_dup_cases.py)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -112,20 +112,23 @@ struct TileArrays {   // the per-tile arrays of Tile_matrix (device)
 
 // ---- 4. selection: one thread per tile
 __global__ __launch_bounds__(256) void k_tc_select(int tilenum, int tilem, int tilen, int rowA, int colA, bool allow_hyb, bool cdna4, const int *__restrict__ tile_nnz, const int *__restrict__ tile_bi,
-                                                     const int *__restrict__ tile_columnidx, const u64 *__restrict__ key, TileArrays A)
+                                                     const int *__restrict__ tile_columnidx, const u64 *__restrict__ key, TileArrays A, unsigned long long *__restrict__ refused)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= tilenum) return;
     const int e0 = tile_nnz[t], n = tile_nnz[t + 1] - e0;
     const int rowlen = tile_rowlen(tile_bi[t], tilem, rowA), collen = tile_collen(tile_columnidx[t], tilen, colA);
     u64 c0 = 0, c1 = 0;   // sixteen 8-bit row counters
+    Occupancy occ;        // ... and, in the same walk, which positions the tile stores (tile_select.h "repeated positions")
     for (int k = 0; k < n; k++) {
         const int r = (int)(key[e0 + k] >> 4) & 15;
+        occ.add((int)(key[e0 + k] & 255ull));
         const u64 one = 1ull << (8 * (r & 7)), m = 255ull << (8 * (r & 7));
         if (r < 8) c0 = (c0 & ~m) | ((c0 + one) & m); else c1 = (c1 & ~m) | ((c1 + one) & m);
     }
     const u64 *kp = key + e0;
-    const Choice c = select_format(n, rowlen, collen, [c0, c1](int r) { return (int)(((r < 8 ? c0 : c1) >> (8 * (r & 7))) & 255ull); }, [kp](int k) { return (int)(kp[k] & 255ull); }, allow_hyb, cdna4);
+    const Choice c = select_format(n, rowlen, collen, [c0, c1](int r) { return (int)(((r < 8 ? c0 : c1) >> (8 * (r & 7))) & 255ull); }, [kp](int k) { return (int)(kp[k] & 255ull); }, allow_hyb, cdna4, occ.repeat);
+    if (c.refused) atomicMax(refused, (unsigned long long)(tilenum - t));   // the FIRST refused tile wins (0: none); read back with the scans' totals
     A.Format[t] = (char)c.fmt;
     A.blknnz[t] = c.stored;
     A.blknnznnz[t] = (unsigned char)c.stored;
@@ -384,7 +387,7 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     // ---- pool of the arrays of tilenum (+ 1) elements: the table's (tile_ptr exists already), and beside them every tile's tile-row, the HYB tiles' byte counts and the scans' totals
     constexpr int NS = 14;
     TileExtents X; X.rowA = rowA;
-    if (pool_begin(D, fields_need(D, X, TF_LIST | TF_TILE) + pool_need((size_t)tilenum, 4) + pool_need(np1, 4) + pool_need(NS, 8))) return -3;
+    if (pool_begin(D, fields_need(D, X, TF_LIST | TF_TILE) + pool_need((size_t)tilenum, 4) + pool_need(np1, 4) + pool_need(NS + 1, 8))) return -3;
     int *d_tile_bi = nullptr, *d_hyb_bytes = nullptr;
     if (dalloc_fields(D, X, TF_LIST | TF_TILE) || dalloc(D, &d_tile_bi, (size_t)tilenum, true) || dalloc(D, &d_hyb_bytes, np1, true)) return -3;
     D->tile_bi = d_tile_bi;
@@ -407,20 +410,29 @@ int create_impl(DevTile *D, int rowA, int colA, const MAT_PTR_TYPE *h_rowptr, co
     // ---- per-tile metadata + format selection + scans
     const TileArrays A{T.Format, T.blknnz, T.blknnznnz, T.dnsrowptr, T.dnscolptr, T.tilewidth, T.csrptr_offset, T.hyb_coocount, T.new_coocount,
                        {T.csr_offset, T.coo_offset, T.ell_offset, T.hyb_offset, T.dns_offset, T.dnsrow_offset, T.dnscol_offset}, d_hyb_bytes};
+    unsigned long long *d_totals = nullptr, h_totals[NS + 1] = {0};   // the scans' totals, and behind them the selection kernel's refusal (tilenum - the first refused tile; 0: none)
+    if (dalloc(D, &d_totals, NS + 1, true)) return -3;
     if (tilenum > 0) {
-        hipLaunchKernelGGL(k_tc_select, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, tilen, rowA, colA, allow_hyb, cdna4, T.tile_nnz, d_tile_bi, T.tile_columnidx, D->key, A);
+        hipLaunchKernelGGL(k_tc_select, dim3(blocks_for(tilenum, 256)), dim3(256), 0, 0, tilenum, tilem, tilen, rowA, colA, allow_hyb, cdna4, T.tile_nnz, d_tile_bi, T.tile_columnidx, D->key, A, d_totals + NS);
         TC_TRY(hipGetLastError());
     }
     ScanSet S{};
     int *scans[] = {T.csr_offset, T.csrptr_offset, T.coo_offset, T.ell_offset, T.hyb_offset, T.dns_offset, T.dnsrow_offset, T.dnscol_offset, T.dnsrowptr, T.dnscolptr, T.hyb_coocount, T.new_coocount, T.blknnz, d_hyb_bytes};
     static const char *names[] = {"csr_offset", "csrptr_offset", "coo_offset", "ell_offset", "hyb_offset", "dns_offset", "dnsrow_offset", "dnscol_offset", "dnsrowptr", "dnscolptr", "hyb_coocount", "new_coocount", "blknnz", "hybIdx bytes"};
     for (int k = 0; k < NS; k++) S.a[k] = scans[k];
-    unsigned long long *d_totals = nullptr, h_totals[NS] = {0};
-    if (dalloc(D, &d_totals, NS, true)) return -3;
     hipLaunchKernelGGL(k_tc_totals, dim3((unsigned)std::min<long long>(2048, blocks_for((long long)np1, 256))), dim3(256), 0, 0, S, NS, (long long)np1, d_totals);
     TC_TRY(hipGetLastError());
     TC_TRY(hipMemcpy(h_totals, d_totals, sizeof(h_totals), hipMemcpyDeviceToHost));
     dfree(D, d_totals);
+    if (h_totals[NS] != 0) {   // a tile with a repeated position and more entries than a tile serves (tile_select.h): nothing is packed
+        const long long t = (long long)tilenum - (long long)h_totals[NS];
+        int bi = 0, cb = 0, e01[2] = {0, 0};
+        TC_TRY(hipMemcpy(&bi, d_tile_bi + t, sizeof(int), hipMemcpyDeviceToHost));
+        TC_TRY(hipMemcpy(&cb, T.tile_columnidx + t, sizeof(int), hipMemcpyDeviceToHost));
+        TC_TRY(hipMemcpy(e01, T.tile_nnz + t, 2 * sizeof(int), hipMemcpyDeviceToHost));
+        fprintf(stderr, TILESPMV_TILE_REFUSAL_FMT, bi, cb, e01[1] - e01[0], TILE_REPEAT_MAX);
+        return -2;
+    }
     for (int k = 0; k < NS; k++)
         if (h_totals[k] > (unsigned long long)INT32_MAX) { fprintf(stderr, "tilespmv: %s exceeds the int32 offsets of Tile_matrix\n", names[k]); return -2; }
     {

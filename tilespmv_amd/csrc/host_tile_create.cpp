@@ -146,6 +146,7 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
     // ---- per-tile metadata + format selection
     for_each_tile_field(*T, X, TF_TILE, zalloc_tile_field);
     int *hyb_bytes = zalloc<int>(np1);   // HYB tiles: bytes of the tile in hybIdx (scanned into the tile's byte offset)
+    std::atomic<int64_t> refused((int64_t)tilenum);   // the first tile that cannot be served (tile_select.h "repeated positions")
 
     parallel_chunks(tilem, 256, [&](int64_t b, int64_t e, int) {
         for (int bi = (int)b; bi < (int)e; bi++) {
@@ -154,7 +155,9 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
                 const int collen = tile_collen(T->tile_columnidx[t], tilen, colA);
                 const int n = T->tile_nnz[t + 1] - T->tile_nnz[t];
                 const uint8_t *cr = cnt_row + (size_t)t * BS, *lr = lrc + T->tile_nnz[t];
-                const Choice c = select_format(n, rowlen, collen, [cr](int r) { return (int)cr[r]; }, [lr](int k) { return (int)lr[k]; }, allow_hyb, cdna4);   // (tile_select.h: shared with the device builder)
+                const bool repeat = tile_has_repeat(n, [lr](int k) { return (int)lr[k]; });
+                const Choice c = select_format(n, rowlen, collen, [cr](int r) { return (int)cr[r]; }, [lr](int k) { return (int)lr[k]; }, allow_hyb, cdna4, repeat);   // (tile_select.h: shared with the device builder)
+                if (c.refused) { int64_t seen = refused.load(); while (t < seen && !refused.compare_exchange_weak(seen, (int64_t)t)) {} }
                 T->Format[t] = (char)c.fmt;
                 T->blknnz[t] = c.stored;
                 T->blknnznnz[t] = (unsigned char)c.stored;
@@ -170,6 +173,12 @@ void tile_create_impl(Tile_matrix *T, int rowA, int colA, const MAT_PTR_TYPE *ro
         }
     });
     lap("format selection");
+    if (refused.load() < tilenum) {   // (void entry point: as for an int32 offset overflow)
+        const int64_t t = refused.load();
+        const int bi = (int)(std::upper_bound(T->tile_ptr, T->tile_ptr + tilem + 1, (int)t) - T->tile_ptr) - 1;
+        fprintf(stderr, TILESPMV_TILE_REFUSAL_FMT, bi, T->tile_columnidx[t], T->tile_nnz[t + 1] - T->tile_nnz[t], TILE_REPEAT_MAX);
+        exit(2);
+    }
     int *scans[] = { T->csr_offset, T->csrptr_offset, T->coo_offset, T->ell_offset, T->hyb_offset, T->dns_offset,
                      T->dnsrow_offset, T->dnscol_offset, T->dnsrowptr, T->dnscolptr, T->hyb_coocount,
                      T->new_coocount, T->blknnz, hyb_bytes };

@@ -2,6 +2,7 @@
 // builder (host_tile_create.cpp) and the device builder (hip_tile_create.hip): both call THIS function, as both call select_format (tile_select.h).
 // PRECONDITION: the tile's entries arrive in row order, and within a row in CSR order (the host's gather goes row by row; the device's sort is stable).  The walk below
 // relies on it: it keeps the row it is in (rcur) and where that row started (rstart), and needs no per-row counts.
+// DNS, DNSROW and DNSCOL have one slot per position: selection never gives them to a tile that stores a position twice (tile_select.h "repeated positions").
 #pragma once
 #include "host_util.h"
 

@@ -10,22 +10,59 @@
 
 namespace tilespmv {
 
-struct Choice { int fmt = 0, stored = 0, width = 0, ndr = 0, ndc = 0, hybcoo = 0, extracted = 0, csrptr = 0; };
+struct Choice { int fmt = 0, stored = 0, width = 0, ndr = 0, ndc = 0, hybcoo = 0, extracted = 0, csrptr = 0, refused = 0; };
+
+// REPEATED POSITIONS.  A CSR may store the same (i, j) more than once (element contributions not yet summed, an uncoalesced framework CSR); y is then the sum over all stored
+// entries.  DNS, DNSROW and DNSCOL hold one value per POSITION of the tile, so a tile that stores a position twice must not get them: counted by entries it looks denser than it
+// is (100 positions stored twice "fill" 200 of 256 slots) and the packer would overwrite values or write past the tile's slots.  Such a tile gets the format the rule gives with
+// those three branches skipped — COO, ELL, HYB and CSR keep entries apart.  Occupancy is the 256-bit map of the (row << 4 | column) bytes seen so far; the device builder feeds
+// it in the loop over the tile's keys that counts its rows, the host builder (whose row counts come from its gather) in tile_has_repeat below: no pass over the matrix is added.
+struct Occupancy {
+    unsigned long long w0 = 0ull, w1 = 0ull, w2 = 0ull, w3 = 0ull;
+    bool repeat = false;
+    TILESPMV_HD inline void add(int b)   // (four selects instead of an indexed word: the words stay in registers on the device)
+    {
+        const unsigned long long bit = 1ull << (b & 63);
+        const int q = (b >> 6) & 3;
+        const unsigned long long m0 = q == 0 ? bit : 0ull, m1 = q == 1 ? bit : 0ull, m2 = q == 2 ? bit : 0ull, m3 = q == 3 ? bit : 0ull;
+        repeat = repeat || ((w0 & m0) | (w1 & m1) | (w2 & m2) | (w3 & m3)) != 0ull;
+        w0 |= m0; w1 |= m1; w2 |= m2; w3 |= m3;
+    }
+};
+template <class LrcAt>
+TILESPMV_HD inline bool tile_has_repeat(int nnz, LrcAt lrc)
+{
+    // entries arrive row by row, so where every row's columns ascend (sorted CSR input) the bytes ascend strictly: no position occurs twice, and the map is not needed
+    // (one compare per entry, which the host compiler vectorises: Tile_create of the 5-point 4096^2 grid lost 15 % to the map without this)
+    int ascending = 1;
+    for (int k = 1; k < nnz; k++) ascending &= lrc(k) > lrc(k - 1);
+    if (ascending) return false;
+    Occupancy o;
+    for (int k = 0; k < nnz; k++) o.add(lrc(k));
+    return o.repeat;
+}
+// A tile with a repeated position is served up to TILE_REPEAT_MAX entries: its in-tile row pointer (Blockcsr_Ptr) and blknnznnz are bytes.  Beyond that it is REFUSED
+// (Choice::refused; the builders print the line below and build nothing).  A local row of 256 entries — where the builders' 8-bit row counters wrap — has repeats
+// (16 columns) and more than 255 entries, so this one test covers it, and it is made BEFORE any row count is looked at.
+constexpr int TILE_REPEAT_MAX = 255;
+constexpr int TILE_WIDTH_MAX = 127;   // Tile_matrix::tilewidth is a (signed) char: a wider ELL / HYB candidate — only a tile with repeats can be one — is stored as CSR
+#define TILESPMV_TILE_REFUSAL_FMT "tilespmv: tile-row %d, column block %d: %d entries with a repeated position in one 16 x 16 tile (at most %d are served: the tile's row pointer is bytes) - sum duplicates first\n"
 
 // One tile of rowlen x collen.  cnt(r): entries in local row r (0 .. 15).  lrc(k): (row << 4 | column) byte of entry k, k = 0 .. nnz - 1 (read only by the
-// whole-column test).  The reference's rule (src/csr2tile.h:150-323).
+// whole-column test).  The reference's rule (src/csr2tile.h:150-323); repeat: the tile stores a position twice (above) — the three positional formats are skipped.
 template <class CntRow, class LrcAt>
-TILESPMV_HD inline Choice select_format_reference(int nnz, int rowlen, int collen, CntRow cnt, LrcAt lrc, bool allow_hyb)
+TILESPMV_HD inline Choice select_format_reference(int nnz, int rowlen, int collen, CntRow cnt, LrcAt lrc, bool allow_hyb, bool repeat)
 {
 #pragma clang fp contract(off)
     Choice c;
-    if (nnz >= (int)(rowlen * collen * 0.75)) {  // near-dense tile stored dense (src/csr2tile.h:150-158)
+    if (repeat && nnz > TILE_REPEAT_MAX) { c.refused = 1; c.fmt = TILESPMV_FMT_COO; return c; }   // (nothing is stored: the build ends with the refusal)
+    if (!repeat && nnz >= (int)(rowlen * collen * 0.75)) {  // near-dense tile stored dense (src/csr2tile.h:150-158)
         c.fmt = TILESPMV_FMT_DNS; c.stored = rowlen * collen; return c;
     }
     if (nnz <= TILESPMV_COO_NNZ_TH) {  // very sparse tile: COO + copy into the extracted matrix (:159-168)
         c.fmt = TILESPMV_FMT_COO; c.stored = nnz; c.extracted = nnz; return c;
     }
-    if (nnz % collen == 0 || nnz % rowlen == 0) {  // candidates for whole-row / whole-column storage (:169-242)
+    if (!repeat && (nnz % collen == 0 || nnz % rowlen == 0)) {  // candidates for whole-row / whole-column storage (:169-242)
         bool usable = false; int full = 0;
         for (int r = 0; r < rowlen; r++) {
             if (cnt(r) % collen) { usable = false; break; }
@@ -49,10 +86,10 @@ TILESPMV_HD inline Choice select_format_reference(int nnz, int rowlen, int colle
     for (int r = 0; r < rowlen; r++) { double d = (double)(cnt(r) - mean); var += d * d; }
     var /= rowlen;
     const double variation = sqrt(var) / mean;  // (:251-265)
-    if (variation <= 0.2) {  // regular rows: ELL padded to the widest row (:270-276)
+    if (variation <= 0.2 && widest <= TILE_WIDTH_MAX) {  // regular rows: ELL padded to the widest row (:270-276)
         c.fmt = TILESPMV_FMT_ELL; c.width = widest; c.stored = widest * rowlen; return c;
     }
-    if (allow_hyb && variation >= 1.0) {  // dormant in the shipped reference (:279-316)
+    if (allow_hyb && variation >= 1.0 && widest <= TILE_WIDTH_MAX) {  // dormant in the shipped reference (:279-316)
         const int sv = (int)sizeof(MAT_VAL_TYPE);
         int hw = widest, best = widest * rowlen * sv + (widest * rowlen + 1) / 2, best_spill = 0;
         for (int w = widest - 1; w > 0; w--) {
@@ -77,10 +114,11 @@ TILESPMV_HD inline Choice select_format_reference(int nnz, int rowlen, int colle
 // the reference's COO tile), w = widest row -> ELL, in between CSR (which the plan splits at that very w); dense when 16 whole columns are cheaper than that.
 // Whole-row / whole-column tiles keep the reference rule (exact patterns only).
 template <class CntRow, class LrcAt>
-TILESPMV_HD inline Choice select_format(int nnz, int rowlen, int collen, CntRow cnt, LrcAt lrc, bool allow_hyb, bool cdna4)
+TILESPMV_HD inline Choice select_format(int nnz, int rowlen, int collen, CntRow cnt, LrcAt lrc, bool allow_hyb, bool cdna4, bool repeat)
 {
-    if (!cdna4) return select_format_reference(nnz, rowlen, collen, cnt, lrc, allow_hyb);
+    if (!cdna4) return select_format_reference(nnz, rowlen, collen, cnt, lrc, allow_hyb, repeat);
     Choice c;
+    if (repeat && nnz > TILE_REPEAT_MAX) { c.refused = 1; c.fmt = TILESPMV_FMT_COO; return c; }
     const int sv = (int)sizeof(MAT_VAL_TYPE);
     const long long unit_b = 12 + 16LL * sv, entry_b = sv + 5;
     int widest = 0;
@@ -92,13 +130,13 @@ TILESPMV_HD inline Choice select_format(int nnz, int rowlen, int collen, CntRow 
         const long long b = unit_b * w + entry_b * rem;
         if (b < best) { best = b; best_w = w; }
     }
-    if ((long long)collen * unit_b <= best) { c.fmt = TILESPMV_FMT_DNS; c.stored = rowlen * collen; return c; }
-    if (nnz % collen == 0 || nnz % rowlen == 0) {
-        const Choice r = select_format_reference(nnz, rowlen, collen, cnt, lrc, false);
+    if (!repeat && (long long)collen * unit_b <= best) { c.fmt = TILESPMV_FMT_DNS; c.stored = rowlen * collen; return c; }
+    if (!repeat && (nnz % collen == 0 || nnz % rowlen == 0)) {
+        const Choice r = select_format_reference(nnz, rowlen, collen, cnt, lrc, false, false);
         if (r.fmt == TILESPMV_FMT_DNSROW || r.fmt == TILESPMV_FMT_DNSCOL) return r;
     }
     if (best_w == 0 && nnz <= TILESPMV_COO_NNZ_TH) { c.fmt = TILESPMV_FMT_COO; c.stored = nnz; c.extracted = nnz; return c; }
-    if (best_w == widest && widest > 0) { c.fmt = TILESPMV_FMT_ELL; c.width = widest; c.stored = widest * rowlen; return c; }
+    if (best_w == widest && widest > 0 && widest <= TILE_WIDTH_MAX) { c.fmt = TILESPMV_FMT_ELL; c.width = widest; c.stored = widest * rowlen; return c; }
     c.fmt = TILESPMV_FMT_CSR; c.stored = nnz; c.csrptr = rowlen;
     return c;
 }
