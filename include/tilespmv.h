@@ -872,6 +872,7 @@ int tilespmv_csr_abs_diagonal_device(int rows, const MAT_PTR_TYPE *d_csrRowPtr, 
  *   CG        z becomes a stored vector (4 work vectors).  One iteration: the product, k_cg_dot, k_cg_update (r.r partials), apply_dot r -> z (r.z partials), and p = z + beta p:
  *             four launches beside the product, 13 + bs vector elements per row BY COUNT (13 with point Jacobi).
  *   BiCGStab  phat = M^-1 p and shat = M^-1 s by two applies per iteration (7 work vectors): 18 + 2 (bs + 2) elements per row by count (23 with point Jacobi).
+ *   GMRES     tilespmv_gmres_create_block, below: one apply per inner iteration and one in every close.
  * Out of scope: MINRES (it needs a positive definite M, and the diagonal blocks of an indefinite matrix are not), multi-RHS CG (the apply would need the row-major [rows][nvec]
  * layout) and CGLS.  All but destroy return a hipError_t value (0 = success). */
 typedef struct tilespmv_block_jacobi tilespmv_block_jacobi;
@@ -890,6 +891,82 @@ int tilespmv_block_jacobi_apply_dot(const tilespmv_block_jacobi *bj, const MAT_V
 int tilespmv_block_jacobi_info(const tilespmv_block_jacobi *bj, void *stream, long long *out /* [TILESPMV_BJ_INFO_COUNT] */);
 int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, const tilespmv_block_jacobi *bj);
 int tilespmv_bicgstab_create_block(tilespmv_bicgstab **s, tilespmv_plan *plan, const tilespmv_block_jacobi *bj);
+
+/* ---- Nonsymmetric systems that BiCGStab does not solve: restarted GMRES around a resident plan (new).  A x = b for a square A that need be
+ * neither symmetric nor definite, by GMRES(m), m = restart <= TILESPMV_GMRES_MAX_RESTART, right-preconditioned by M^-1 = diag(d_dinv) (tilespmv_csr_diagonal_device(..., invert = 1)
+ * makes it; d_dinv = NULL: M = I) or by a block-Jacobi object.  One product per iteration, a residual norm that never increases inside a cycle, no breakdown but the lucky one and
+ * the singular one.  The contract is that of tilespmv_bicgstab_*, word for word, wherever it can be; the state is tilespmv_cg_state and the statuses are TILESPMV_CG_*.
+ *   begin     the solver's copy of b (every restart needs it: d_b is not read after begin's work is done);  bb = b.b;  iteration count and breakdown flag cleared;  open a cycle
+ *   open      r = b - A x (one plan product);  rr = r.r;  beta = sqrt(rr);  V_0 = r / beta;  g = beta e_0;  j = 0.  rr = 0 exactly: nothing is formed, the cycle is dead
+ *   iterate   w = A (M^-1 V_j);  h1 = V_{0..j}^T w;  w' = w - V h1;  h2 = V^T w';  w'' = w' - V h2;  h_{j+1,j} = |w''|;  column j of H = (h1 + h2, h_{j+1,j});  the j stored Givens
+ *             rotations applied to it;  gamma = hypot(h_jj, h_{j+1,j}), cs = h_jj / gamma, sn = h_{j+1,j} / gamma;  g_{j+1} = -sn g_j, g_j = cs g_j;  rr = g_{j+1}^2;
+ *             V_{j+1} = w'' / h_{j+1,j};  j += 1.  After `restart` iterations in a cycle: close it and open the next
+ *   close     after k columns: R y = g by back substitution (k x k, in double);  x += M^-1 (V_{0..k-1} y)
+ * Classical Gram-Schmidt applied twice is deliberate: a pass needs all its dot products before it subtracts, so a pass is two streaming kernels whatever j is, where modified
+ * Gram-Schmidt needs j + 1 dependent reductions; the second pass keeps the float library orthogonal.
+ * All vectors live in the value type; every dot product, H, the rotations, g, y and every scalar is double in both libraries; h1_i, h2_i, 1 / h_{j+1,j}, 1 / beta and y_i are
+ * rounded to the value type once, where they multiply a vector (the rule of tilespmv_cg_*).
+ * WHAT rr IS, AND WHEN d_x IS CURRENT: D_X HOLDS THE ITERATE ONLY AFTER A CLOSE (the end of a cycle inside iterate, or flush); between closes it is the x of the last close.  Inside
+ * a cycle rr is the recurrence's g_{j+1}^2, which with right preconditioning estimates the TRUE |b - A x|^2.  After an open (begin, a full cycle, flush) rr IS A RECOMPUTED
+ * |b - A x|^2 of the x in d_x — this solver is the one place in the library where that holds.  bb is |b|^2.  `iterations` counts inner iterations; an open's product is not counted.
+ * One inner iteration with k = j + 1 basis vectors = the plan product and FOUR streaming kernels (the k dot products h1;  w' with the k dot products h2 from the same walk;  w''
+ * with |w''|^2;  V_{j+1} with the column, the rotations, g and rr).  A close is a one-workgroup back substitution and one kernel for x; an open is the product, the residual with
+ * its norm, and the fourth kernel in its open role.  Every scalar lives in device memory with one writing kernel per field; a reducing kernel leaves one partial per sum and
+ * workgroup and the consuming kernel folds them itself, every workgroup in the same order: no atomics, no finishing launch, no host read.  The number of partials (at most 256 per
+ * sum for vectors below 32 MiB, 512 below 128 MiB, 1024 beyond) depends on `rows` alone and the order of every addition on `rows` and j: on a plan whose y is bit-reproducible (TILESPMV_INFO_ENTRY_ORDERED = 1, e.g. deterministic = 1) the
+ * iterates and the state are too, run after run and plan after plan.
+ * Vector elements read or written per inner iteration beside the product, by count, each basis vector counted once per kernel: 3 k + 7 per row (k + 1, k + 2, k + 2, 2 over the
+ * four kernels), 3 k + 9 with d_dinv (its read and the store of M^-1 V_{j+1}); the mean over a full cycle is 1.5 (restart + 1) + 7.  A block object adds its apply (bs + 2).  A close
+ * moves k + 2 (+ 1 with d_dinv), an open 5 beside its product.  The dot products are accumulated for 8 basis vectors at a time (what a thread's registers hold), so w is read again
+ * once per further group of 8, and the second kernel reads the basis a second time for h2 once w' is complete: 4 k + 2 ceil(k / 8) + 6 with those re-reads.  Folding k sums of P
+ * partials in every workgroup reads 8 k P^2 bytes per kernel out of the cache: at most 1/16 of the vector traffic for vectors of 8 MiB and more.
+ * Workspace: restart + 3 vectors of rows + 16 elements (the basis V_0..V_restart, w, the copy of b), one more with d_dinv or a block object, (restart + 1) 4 KB of partial sums (16 KB on the largest systems) and
+ * 39 KB of R, rotations, g, y and scalars, in one hipMalloc.
+ * Guards, taken on the device, exact tests only, uniform branches, in the style of the CG guards:
+ *   rr = 0 at an open, or the breakdown flag set   the cycle is dead: inner iterations and closes write no vector, x does not change by a bit — a captured graph may overrun convergence.
+ *   h_{j+1,j} = 0 with gamma != 0                  the lucky termination: the rotation is applied (rr = 0), V_{j+1} is not formed, the cycle is closed early: its remaining inner
+ *                                                  iterations write nothing and the close uses the columns done so far.
+ *   gamma = 0                                      A is singular on this Krylov space and the system incompatible: the breakdown flag is set, never cleared until begin; this iteration,
+ *                                                  every later one and every close write nothing, x keeps its last good value.
+ *   j = restart without a close in between         the iteration writes nothing: the device's column index never passes `restart` (a replayed graph, misused: below).
+ *   The iteration counter advances in every inner iteration whatever the guards did: a breakdown seen at the first check of solve(check_every = 8) reports 8 iterations.
+ * WHERE THE CYCLE POSITION LIVES: on the host, in the solver object — the close + open sequence contains a product, so the host must know when to launch it.  begin and flush reset
+ * it, iterate advances it.  For graphs: a captured iterate(count) replays correctly when it was captured at a cycle boundary (after begin, flush or a whole number of cycles) and
+ * count is a multiple of `restart`.
+ * A tilespmv_gmres and its plan run on ONE stream at a time.  d_b, d_x and d_dinv are DEVICE vectors of `rows` elements, 16-byte aligned (hipErrorInvalidValue otherwise);
+ * nothing behind element rows - 1 is read or written.
+ *
+ *   tilespmv_gmres_create        binds a workspace to `plan`, which must be square and whole (tilerow_begin = 0, tilerow_end = tilem; a square TILESPMV_CREATE_TRANSPOSE plan
+ *                                qualifies: it solves A^T x = b) and must outlive it; the plan is borrowed.  d_dinv: NULL, or the inverse diagonal, borrowed until destroy — its VALUES
+ *                                may change between solves (tilespmv_plan_update_values, then tilespmv_csr_diagonal_device into the same array).  One hipMalloc (synchronises).
+ *                                Returns 0, hipErrorInvalidValue (a NULL argument, or restart outside 1 .. TILESPMV_GMRES_MAX_RESTART, which is looked at first: no HIP call made; a non-square or shard plan, a
+ *                                misaligned d_dinv: nothing allocated), or the hipMalloc error.
+ *   tilespmv_gmres_create_block  the same with a block-Jacobi object for M^-1 (borrowed; its values may change between solves; its rows must be the plan's: hipErrorInvalidValue
+ *                                otherwise, nothing allocated): M^-1 V_{j+1} by one apply after the fourth kernel; a close forms u = V y, applies M^-1 and adds.
+ *   tilespmv_gmres_begin         as above, from the caller's x (pass zeros for none).
+ *   tilespmv_gmres_iterate       `count` inner iterations back to back, with a close and an open after every `restart`-th of a cycle.  Like begin: asynchronous on `stream`, no
+ *                                allocation, no synchronisation, no host read, one linear chain of kernels — safe to capture into a hipGraph, for every kind of plan.  It stops at
+ *                                no tolerance.
+ *   tilespmv_gmres_flush         closes the cycle early (with no column done it writes nothing) and opens the next: d_x is the current iterate and rr its recomputed residual.
+ *                                Asynchronous and capturable like iterate.
+ *   tilespmv_gmres_state_read    synchronises `stream` and fills the state (set out->size = sizeof(tilespmv_cg_state) first).  status: BREAKDOWN, else CONVERGED when rr is exactly
+ *                                0, else RUNNING.
+ *   tilespmv_gmres_solve         begin, then iterate(check_every) + state_read until rr <= rtol^2 bb (CONVERGED), `maxiter` inner iterations are done (MAXITER; the last block is
+ *                                cut so that no more run) or a breakdown (BREAKDOWN); then flush, so that d_x is the iterate the decision was taken on, and one more read: out->rr
+ *                                is the recomputed |b - A x|^2 of the returned x, status and iterations stay those of the decision.  bb = 0 -> x = 0, CONVERGED, 0 iterations.
+ *                                check_every < 1 -> 1.  One host synchronisation per check.
+ * All but destroy return a hipError_t value (0 = success). */
+typedef struct tilespmv_gmres tilespmv_gmres;
+#define TILESPMV_GMRES_MAX_RESTART 64
+int tilespmv_gmres_create(tilespmv_gmres **s, tilespmv_plan *plan, int restart, const MAT_VAL_TYPE *d_dinv /* may be NULL */);
+int tilespmv_gmres_create_block(tilespmv_gmres **s, tilespmv_plan *plan, int restart, const tilespmv_block_jacobi *bj);
+void tilespmv_gmres_destroy(tilespmv_gmres *s);
+int tilespmv_gmres_begin(tilespmv_gmres *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, void *stream);
+int tilespmv_gmres_iterate(tilespmv_gmres *s, MAT_VAL_TYPE *d_x, int count, void *stream);
+int tilespmv_gmres_flush(tilespmv_gmres *s, MAT_VAL_TYPE *d_x, void *stream);
+int tilespmv_gmres_state_read(tilespmv_gmres *s, void *stream, tilespmv_cg_state *out);
+int tilespmv_gmres_solve(tilespmv_gmres *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
+                         tilespmv_cg_state *out);
 
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */

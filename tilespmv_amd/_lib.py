@@ -181,7 +181,7 @@ def load(dtype=np.float64):
     # the device-resident solvers: (prefix, state struct, what create takes behind the plan, what begin and solve take behind d_x)
     for prefix, state, create_args, solve_args in (("cg", CGState, [C.c_void_p], []), ("cg_multi", CGState, [C.c_int, C.c_void_p], []),
                                                    ("cgls", CGLSState, [C.c_void_p, C.c_void_p], [C.c_double]), ("bicgstab", CGState, [C.c_void_p], []),
-                                                   ("minres", CGState, [C.c_void_p], [])):
+                                                   ("minres", CGState, [C.c_void_p], []), ("gmres", CGState, [C.c_int, C.c_void_p], [])):
         for what, restype, argtypes in (("create", C.c_int, [C.POINTER(C.c_void_p), C.c_void_p] + create_args),
                                         ("destroy", None, [C.c_void_p]),
                                         ("begin", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + solve_args + [C.c_void_p]),
@@ -212,6 +212,10 @@ def load(dtype=np.float64):
     lib.tilespmv_cg_create_block.restype = C.c_int
     lib.tilespmv_bicgstab_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
     lib.tilespmv_bicgstab_create_block.restype = C.c_int
+    lib.tilespmv_gmres_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
+    lib.tilespmv_gmres_create_block.restype = C.c_int
+    lib.tilespmv_gmres_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_gmres_flush.restype = C.c_int
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -246,4 +250,6 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_minres_create", "tilespmv_minres_destroy", "tilespmv_minres_begin", "tilespmv_minres_iterate", "tilespmv_minres_state_read", "tilespmv_minres_solve",
                     "tilespmv_csr_abs_diagonal_device",
                     "tilespmv_block_jacobi_create", "tilespmv_block_jacobi_destroy", "tilespmv_block_jacobi_update", "tilespmv_block_jacobi_apply", "tilespmv_block_jacobi_apply_dot",
-                    "tilespmv_block_jacobi_info", "tilespmv_cg_create_block", "tilespmv_bicgstab_create_block"]
+                    "tilespmv_block_jacobi_info", "tilespmv_cg_create_block", "tilespmv_bicgstab_create_block",
+                    "tilespmv_gmres_create", "tilespmv_gmres_create_block", "tilespmv_gmres_destroy", "tilespmv_gmres_begin", "tilespmv_gmres_iterate", "tilespmv_gmres_flush",
+                    "tilespmv_gmres_state_read", "tilespmv_gmres_solve"]

@@ -694,6 +694,36 @@ class BiCGStab(_IterativeSolver):
         self.h = h
 
 
+class GMRES(_IterativeSolver):
+    """``tilespmv_gmres``: restarted GMRES(``restart``) for a square, nonsymmetric A around a resident plan, right-preconditioned by a diagonal or a block-Jacobi object, every
+    scalar on the device (include/tilespmv.h) — the solver for the systems ``BiCGStab`` breaks down or stagnates on.  It mirrors ``BiCGStab``: the same state
+    dict, the same statuses.  One product per iteration.
+
+    ``plan``: square and whole (a square ``transpose=True`` plan solves ``A^T x = b``); it must stay open while the solver is.  ``restart``: 1 .. 64 inner iterations per cycle
+    (the workspace holds ``restart + 1`` basis vectors).  ``d_dinv`` / ``block``: as for ``BiCGStab``.  ``b`` / ``x`` are device addresses of ``rows`` elements, 16-byte aligned.
+    ``x`` HOLDS THE ITERATE ONLY AFTER A CLOSE: at the end of every ``restart``-th iteration of a cycle, after ``flush`` and after ``solve``; ``rr`` is then a recomputed
+    ``|b - A x|^2``, inside a cycle the recurrence's estimate of it.  A captured ``iterate(count)`` replays correctly when captured at a cycle boundary with ``count`` a multiple of
+    ``restart``.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (``restart`` out of range, a shard, a non-square plan, a misaligned vector, a block
+    preconditioner of another row count) and for ``block`` together with ``d_dinv``."""
+
+    _prefix = "tilespmv_gmres"
+    _hint = "1 <= restart <= 64; the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
+
+    def __init__(self, plan, restart=30, d_dinv=None, block=None):
+        self.lib, self.plan, self.block, self.restart = plan.lib, plan, block, int(restart)
+        h = C.c_void_p()
+        bh = _block_handle(block, d_dinv, plan.lib)
+        if bh is not None:
+            self._check(self.lib.tilespmv_gmres_create_block(C.byref(h), plan.h, self.restart, bh), "tilespmv_gmres_create_block")
+        else:
+            self._check(self.lib.tilespmv_gmres_create(C.byref(h), plan.h, self.restart, C.c_void_p(d_dinv or None)), "tilespmv_gmres_create")
+        self.h = h
+
+    def flush(self, d_x, stream=0):
+        """Close the cycle early and open the next: ``d_x`` is the current iterate and ``rr`` its recomputed residual; asynchronous, capturable."""
+        self._call("flush", C.c_void_p(d_x), C.c_void_p(stream))
+
+
 def csr_abs_diagonal_device(rows, d_rp, d_ci, d_v, d_out, invert=False, stream=0, dtype=np.float64):
     """``tilespmv_csr_abs_diagonal_device``: ``csr_diagonal_device`` with the absolute value of the summed entries (i, i); ``invert=True``: ``1 / |d|``, 1 where d is 0 — a positive
     ``d_minv`` for ``MINRES`` whatever the signs on the diagonal (a KKT matrix with a negative or zero (2,2) block).  Asynchronous on ``stream``."""

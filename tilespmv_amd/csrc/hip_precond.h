@@ -1,4 +1,4 @@
-// hip_precond.h — the block-Jacobi object (hip_precond.hip) as the solvers that take one see it (hip_solver.hip, hip_solver_bi.hip).
+// hip_precond.h — the block-Jacobi object (hip_precond.hip) as the solvers that take one see it (hip_solver.hip, hip_solver_bi.hip, hip_solver_gm.hip).
 #pragma once
 
 #include "hip_solver_common.h"

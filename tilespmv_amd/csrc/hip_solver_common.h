@@ -1,4 +1,4 @@
-// hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip, hip_solver_bi.hip, hip_solver_mr.hip): the launch shape, the number of
+// hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip, hip_solver_bi.hip, hip_solver_mr.hip, hip_solver_gm.hip): the launch shape, the number of
 // partial sums, the reduction tree, the walk over a vector, and the host-side driver around the kernels: the one allocation (DeviceBlock), the versioned state structs (cg_state_of,
 // state_read, put_versioned), the loop of *_solve with its convergence test (solve_loop, RrBbTest), the start of a create and the end of a solver (square_system, destroy_solver),
 // and the one-thread-per-row launch of tilespmv_csr_*_device (launch_per_row).

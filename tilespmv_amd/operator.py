@@ -10,7 +10,9 @@
     X, infos = op.cg(B)                                              # B of shape (rows, k): k systems in lock-step around the multi-vector product
     x, info = op.bicgstab(b)                                         # A x = b, A square and not symmetric: the solver in the library
     x, info = bicgstab(op, b)                                        # ... the same as a loop of torch operations (the A/B baseline of scripts/bicgstab_time.py)
-    x, info = op.minres(b)                                           # A x = b, A symmetric and indefinite (saddle point, KKT): the solver in the library
+    x, info = op.gmres(b)                                            # A x = b where BiCGStab breaks down or stagnates: restarted GMRES in the library
+    x, info = gmres(op, b)                                           # ... the same as a loop of torch operations
+    x, info = op.minres(b)                                 # A x = b, A symmetric and indefinite (saddle point, KKT): the solver in the library
     x, info = minres(op, b)                                          # ... the same as a loop of torch operations (the A/B baseline of scripts/minres_time.py)
 
 The plan of A^T is a plan like any other (tuned kernels, form choice, ordered sums); there is no scatter form of A^T x.
@@ -273,6 +275,19 @@ class SparseOperator:
         x, s = self._solve(lambda d: api.BiCGStab(self.A, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
         return x, _info(s)
 
+    def gmres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, restart=30, dinv=None, stream=None, precond=None):
+        """A x = b for a square A that need not be symmetric, by restarted GMRES in the library (``api.GMRES`` over the plan of A) — one product and four fused
+        kernels per iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations; the solver for what ``bicgstab`` breaks down or stagnates on
+        (convection-dominated, nearly skew-symmetric).  ``b``: a contiguous torch CUDA vector of ``rows`` elements; ``restart``: 1 .. 64 iterations per cycle; ``dinv``: the inverse
+        diagonal as a CUDA vector (Jacobi, applied from the right), None = unpreconditioned; ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv``.
+        Stops at ``sqrt(rr / bb) <= rtol``, after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.  Returns ``(x, info)`` with ``info = {"iterations", "residual",
+        "relative_residual", "converged", "status"}`` (``residual``: ``|b - A x|`` recomputed for the returned x)."""
+        self._square("gmres")
+        if precond is not None and _is_tensor(b) and b.dim() == 2:
+            raise ValueError("precond (block Jacobi) applies to a 1-D b only")
+        x, s = self._solve(lambda d: api.GMRES(self.A, restart, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
+        return x, _info(s)
+
     def minres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, minv=None, stream=None):
         """A x = b for a square SYMMETRIC A that may be indefinite (saddle-point, KKT), by MINRES in the library (``api.MINRES`` over the plan of A) — one product
         and three fused kernels per iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations; the residual norm never increases.  ``b``: a
@@ -337,6 +352,68 @@ def bicgstab(op, b, x0=None, tol=1e-10, maxiter=None, dinv=None, check_every=1):
         if it % check_every == 0 or it == maxiter:
             converged = float(rr.sqrt()) <= tol * norm_b
     res = float(torch.linalg.vector_norm(b - op.matvec(x)))
+    info = {"iterations": it, "residual": res, "relative_residual": res / norm_b if norm_b > 0 else 0.0, "converged": bool(converged)}
+    return x, info
+
+
+def gmres(op, b, x0=None, tol=1e-10, maxiter=None, restart=30, dinv=None, check_every=1):
+    """``A x = b`` for a square operator by right-preconditioned restarted GMRES as a loop of torch operations: the recurrences of ``SparseOperator.gmres`` (DESIGN.md §3.13:
+    classical Gram-Schmidt applied twice, the basis a 2-D tensor, ``V @ w`` for the dot products, Givens rotations on the host), without its guards — what the fused solver is
+    measured against and a second opinion in tests.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: None or the inverse diagonal.  Stops when the recurrence's residual
+    estimate is ``<= tol * |b|`` (checked every ``check_every`` iterations and at the end of a cycle) or after ``maxiter`` iterations (default ``2 * rows``).  Returns ``(x, info)``
+    with ``info = {"iterations", "residual", "relative_residual", "converged"}`` (``residual``: a recomputed ``|b - A x|``)."""
+    import torch
+    rows, cols = op.shape
+    if rows != cols:
+        raise ValueError("gmres needs a square operator; this one is %d x %d" % (rows, cols))
+    if b.numel() != rows:
+        raise ValueError("b must have %d elements" % rows)
+    maxiter = 2 * rows if maxiter is None else maxiter
+    m = int(restart)
+    x = torch.zeros(rows, dtype=b.dtype, device=b.device) if x0 is None else x0.clone()
+    norm_b = float(torch.linalg.vector_norm(b))
+    V = torch.zeros((m + 1, rows), dtype=b.dtype, device=b.device)
+    w = torch.empty(rows + 16, dtype=b.dtype, device=b.device)[:rows]
+    it, converged = 0, norm_b == 0.0
+    if converged:
+        x.zero_()
+    while not converged and it < maxiter:
+        r = b - op.matvec(x)
+        beta = float(torch.linalg.vector_norm(r))
+        if beta <= tol * norm_b:
+            converged = True
+            break
+        V[0] = r / beta
+        R = np.zeros((m, m))
+        cs, sn, g = np.zeros(m), np.zeros(m), np.zeros(m + 1)
+        g[0] = beta
+        k = 0
+        while k < m and it < maxiter:
+            op.matvec(V[k] if dinv is None else dinv * V[k], w)
+            h1 = V[:k + 1] @ w
+            w -= h1 @ V[:k + 1]
+            h2 = V[:k + 1] @ w
+            w -= h2 @ V[:k + 1]
+            hh = float(torch.linalg.vector_norm(w))
+            col = (h1 + h2).double().cpu().numpy()
+            for i in range(k):
+                col[i], col[i + 1] = cs[i] * col[i] + sn[i] * col[i + 1], -sn[i] * col[i] + cs[i] * col[i + 1]
+            gamma = float(np.hypot(col[k], hh))
+            cs[k], sn[k] = col[k] / gamma, hh / gamma
+            R[:k, k], R[k, k] = col[:k], gamma
+            g[k + 1], g[k] = -sn[k] * g[k], cs[k] * g[k]
+            k += 1
+            it += 1
+            if hh == 0.0:
+                break
+            V[k] = w / hh
+            if (it % check_every == 0 or it == maxiter) and abs(g[k]) <= tol * norm_b:
+                break
+        y = np.linalg.solve(np.triu(R[:k, :k]), g[:k])
+        u = torch.from_numpy(y).to(device=b.device, dtype=b.dtype) @ V[:k]
+        x += u if dinv is None else dinv * u
+    res = float(torch.linalg.vector_norm(b - op.matvec(x)))
+    converged = converged or res <= tol * norm_b
     info = {"iterations": it, "residual": res, "relative_residual": res / norm_b if norm_b > 0 else 0.0, "converged": bool(converged)}
     return x, info
 
