@@ -6,8 +6,9 @@
 //   k_cg_direction  reads r, p (, dinv)             beta = rho_new / rho;  p = z + beta p  (z recomputed from r and dinv, never stored)
 // With a block-Jacobi object (tilespmv_cg_create_block; hip_precond.hip) z is a stored vector: k_cg_update runs with dinv = NULL (r.r partials only), k_bj_apply forms
 // z = M^-1 r and the r.z partials, and k_cg_zstep replaces k_cg_direction — four launches, (13 + bs) n elements.  The kernels above are the same code either way.
-// 11 n vector elements per iteration (13 n with Jacobi).  The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail
-// are those of hip_solver_common.h; the number of partials is solver_parts(n).  alpha and beta are rounded to the value type once, where they multiply.
+// 11 n vector elements per iteration (13 n with Jacobi).  The launch shape and the partial sums with their fixed order of additions are those of hip_solver_common.h, and so is the
+// walk over a vector: every kernel here hands its body, written once for lane vectors and tail elements alike, to sv_dot, sv_walk_loaded (the kernels of the iteration: a trip's loads
+// before its arithmetic) or sv_walk.  The number of partials is solver_parts(n).  alpha and beta are rounded to the value type once, where they multiply.
 //
 // The scalar block (CgScal) has ONE writing kernel per field and no kernel reads a field it (or a concurrent workgroup of it) writes:
 //   rho         k_cg_dot, workgroup 0 (fold of the r.z partials the previous update left; 0 after a breakdown)      read by k_cg_update, k_cg_direction
@@ -33,23 +34,8 @@ __global__ __launch_bounds__(SVB) void k_cg_dot(long long n, const val_t *__rest
                                                 int np, CgScal *__restrict__ S)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t a[SV_U], b[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) { a[u] = lanes(p)[v]; b[u] = lanes(Ap)[v]; }
-            else { a[u] = (val_t)0; b[u] = (val_t)0; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++)
-#pragma unroll
-            for (int q = 0; q < SV_VPL; q++) acc += (double)a[u][q] * (double)b[u][q];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) acc += (double)p[i] * (double)Ap[i];
+    sv_dot(n, gridDim.x, p, Ap, [&](auto a, auto b) { sv_mac(acc, a, b); });
     const double t = block_sum(acc, s);
     if (threadIdx.x == 0) ppap[blockIdx.x] = t;
     if (blockIdx.x == 0) {   // rho of this iteration, for the two kernels that follow
@@ -58,6 +44,7 @@ __global__ __launch_bounds__(SVB) void k_cg_dot(long long n, const val_t *__rest
     }
 }
 
+template <class T> struct CgUpdate { T p, Ap, x, r, d; };
 __global__ __launch_bounds__(SVB) void k_cg_update(long long n, const val_t *__restrict__ p, const val_t *__restrict__ Ap, val_t *__restrict__ x, val_t *__restrict__ r,
                                                    const val_t *__restrict__ dinv, const double *__restrict__ ppap, double *__restrict__ prr, double *__restrict__ prz, int np,
                                                    CgScal *__restrict__ S)
@@ -67,42 +54,20 @@ __global__ __launch_bounds__(SVB) void k_cg_update(long long n, const val_t *__r
     const bool broke = rho < 0.0 || (rho > 0.0 && !(pap > 0.0));
     const val_t alpha = (val_t)((rho > 0.0 && pap > 0.0) ? rho / pap : 0.0);
     if (broke && blockIdx.x == 0 && threadIdx.x == 0) S->breakdown = 1;
-    const long long nv = n / SV_VPL;
     double arr = 0.0, arz = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vp[SV_U], va[SV_U], vx[SV_U], vr[SV_U], vd[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                vp[u] = lanes(p)[v]; va[u] = lanes(Ap)[v];
-                vx[u] = lanes(x)[v]; vr[u] = lanes(r)[v];
-                if (dinv) vd[u] = lanes(dinv)[v];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                const svec_t nx = vx[u] + alpha * vp[u], nr = vr[u] - alpha * va[u];
-                lanes(x)[v] = nx;
-                lanes(r)[v] = nr;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) {
-                    arr += (double)nr[q] * (double)nr[q];
-                    if (dinv) arz += (double)nr[q] * (double)(val_t)(vd[u][q] * nr[q]);
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t nr = r[i] - alpha * Ap[i];
-            x[i] = x[i] + alpha * p[i];
-            r[i] = nr;
-            arr += (double)nr * (double)nr;
-            if (dinv) arz += (double)nr * (double)(val_t)(dinv[i] * nr);
-        }
+    sv_walk_loaded<CgUpdate>(
+        n, gridDim.x,
+        [&](auto at, auto &t) {
+            t.p = at(p); t.Ap = at(Ap); t.x = at(x); t.r = at(r);
+            if (dinv) t.d = at(dinv);
+        },
+        [&](auto at, const auto &t) {
+            const auto nx = t.x + alpha * t.p, nr = t.r - alpha * t.Ap;
+            at.put(x, nx);
+            at.put(r, nr);
+            sv_mac(arr, nr, nr);
+            if (dinv) sv_mac(arz, nr, t.d * nr);
+        });
     const double trr = block_sum(arr, s);
     if (threadIdx.x == 0) prr[blockIdx.x] = trr;
     if (dinv) {   // (plain CG: r.z is r.r, and prz is prr)
@@ -111,6 +76,7 @@ __global__ __launch_bounds__(SVB) void k_cg_update(long long n, const val_t *__r
     }
 }
 
+template <class T> struct CgDirection { T r, p, d; };
 __global__ __launch_bounds__(SVB) void k_cg_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ dinv,
                                                       const double *__restrict__ prr, const double *__restrict__ prz, int np, CgScal *__restrict__ S)
 {
@@ -121,28 +87,16 @@ __global__ __launch_bounds__(SVB) void k_cg_direction(long long n, const val_t *
         const double rr = dinv ? fold(prr, np, s) : rho_new;
         if (threadIdx.x == 0) { S->rr = rr; S->iterations = S->iterations + 1; }
     }
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vr[SV_U], vp[SV_U], vd[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                vr[u] = lanes(r)[v]; vp[u] = lanes(p)[v];
-                if (dinv) vd[u] = lanes(dinv)[v];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                const svec_t z = dinv ? vd[u] * vr[u] : vr[u];
-                lanes(p)[v] = z + beta * vp[u];
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) p[i] = (dinv ? (val_t)(dinv[i] * r[i]) : r[i]) + beta * p[i];
+    sv_walk_loaded<CgDirection>(
+        n, gridDim.x,
+        [&](auto at, auto &t) {
+            t.r = at(r); t.p = at(p);
+            if (dinv) t.d = at(dinv);
+        },
+        [&](auto at, const auto &t) {
+            const auto z = dinv ? t.d * t.r : t.r;
+            at.put(p, z + beta * t.p);
+        });
 }
 
 // the start of a solve: r = b - A x (Ax holds the product), p = z, partial sums of r.r, r.z and b.b
@@ -150,32 +104,16 @@ __global__ __launch_bounds__(SVB) void k_cg_begin(long long n, const val_t *__re
                                                   const val_t *__restrict__ dinv, double *__restrict__ prr, double *__restrict__ prz, double *__restrict__ pbb)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double arr = 0.0, arz = 0.0, abb = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                const svec_t vb = lanes(b)[v], nr = vb - lanes(Ax)[v];
-                const svec_t z = dinv ? lanes(dinv)[v] * nr : nr;
-                lanes(r)[v] = nr;
-                lanes(p)[v] = z;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) {
-                    arr += (double)nr[q] * (double)nr[q];
-                    arz += (double)nr[q] * (double)z[q];
-                    abb += (double)vb[q] * (double)vb[q];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t nr = b[i] - Ax[i], z = dinv ? (val_t)(dinv[i] * nr) : nr;
-            r[i] = nr; p[i] = z;
-            arr += (double)nr * (double)nr; arz += (double)nr * (double)z; abb += (double)b[i] * (double)b[i];
-        }
+    sv_walk(n, gridDim.x, [&](auto at) {
+        const auto vb = at(b), nr = vb - at(Ax);
+        const auto z = dinv ? at(dinv) * nr : nr;
+        at.put(r, nr);
+        at.put(p, z);
+        sv_mac(arr, nr, nr);
+        sv_mac(arz, nr, z);
+        sv_mac(abb, vb, vb);
+    });
     const double trr = block_sum(arr, s), trz = block_sum(arz, s), tbb = block_sum(abb, s);
     if (threadIdx.x == 0) {
         prr[blockIdx.x] = trr; pbb[blockIdx.x] = tbb;
@@ -204,6 +142,7 @@ __global__ __launch_bounds__(SVB) void k_csr_diagonal(int rows, const int *__res
 
 // the direction with a STORED z (block Jacobi: z = M^-1 r and the r.z partials come from k_bj_apply, hip_precond.hip): beta = rho_new / rho;  p = z + beta p.  The scalars are
 // k_cg_direction's, with rr folded from the r.r partials of k_cg_update (k_cg_direction with z in r's place would take rr = rho_new).
+template <class T> struct CgZstep { T z, p; };
 __global__ __launch_bounds__(SVB) void k_cg_zstep(long long n, const val_t *__restrict__ z, val_t *__restrict__ p, const double *__restrict__ prr, const double *__restrict__ prz,
                                                   int np, CgScal *__restrict__ S)
 {
@@ -214,22 +153,8 @@ __global__ __launch_bounds__(SVB) void k_cg_zstep(long long n, const val_t *__re
         const double rr = fold(prr, np, s);
         if (threadIdx.x == 0) { S->rr = rr; S->iterations = S->iterations + 1; }
     }
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vz[SV_U], vp[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) { vz[u] = lanes(z)[v]; vp[u] = lanes(p)[v]; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) lanes(p)[v] = vz[u] + beta * vp[u];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) p[i] = z[i] + beta * p[i];
+    sv_walk_loaded<CgZstep>(
+        n, gridDim.x, [&](auto at, auto &t) { t.z = at(z); t.p = at(p); }, [&](auto at, const auto &t) { at.put(p, t.z + beta * t.p); });
 }
 
 }  // namespace

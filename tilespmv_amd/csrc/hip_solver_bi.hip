@@ -13,8 +13,8 @@
 // With a block-Jacobi object (tilespmv_bicgstab_create_block; hip_precond.hip) the kernels run with dinv = NULL and phat, shat are filled by k_bj_apply: phat = M^-1 p
 // at the end of begin and after k_bi_direction, shat = M^-1 s after k_bi_half — 7 work vectors, 18 n + 2 (bs + 2) n elements.  Under a guard that froze the vectors the applies write the
 // same bits again.
-// The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail are those of hip_solver_common.h; the number of partials
-// is solver_parts(n).  alpha, omega and beta are formed in double and rounded to the value type once, where they multiply.
+// The launch shape and the partial sums with their fixed order of additions are those of hip_solver_common.h, and so is the walk over a vector: every kernel here hands its body,
+// written once for lane vectors and tail elements alike, to sv_dot, sv_walk_loaded or sv_walk.  The number of partials is solver_parts(n).  alpha, omega and beta are formed in double and rounded to the value type once, where they multiply.
 //
 // The scalar block (BiScal) has ONE writing kernel per field and no kernel reads a field it (or a concurrent workgroup of it) writes:
 //   rho, live          k_bi_dot1, workgroup 0 (rho: fold of the rhat.r partials the previous update left; live: |r|^2 != 0, folded from that update's r.r partials, and no breakdown)
@@ -50,23 +50,8 @@ __global__ __launch_bounds__(SVB) void k_bi_dot1(long long n, const val_t *__res
                                                  const double *__restrict__ prr, int np, BiScal *__restrict__ S)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t a[SV_U], b[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) { a[u] = lanes(rhat)[i]; b[u] = lanes(v)[i]; }
-            else { a[u] = (val_t)0; b[u] = (val_t)0; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++)
-#pragma unroll
-            for (int q = 0; q < SV_VPL; q++) acc += (double)a[u][q] * (double)b[u][q];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) acc += (double)rhat[i] * (double)v[i];
+    sv_dot(n, gridDim.x, rhat, v, [&](auto a, auto b) { sv_mac(acc, a, b); });
     const double t = block_sum(acc, s);
     if (threadIdx.x == 0) psig[blockIdx.x] = t;
     if (blockIdx.x == 0) {   // rho of this iteration and whether it runs at all, for the kernels that follow
@@ -76,6 +61,7 @@ __global__ __launch_bounds__(SVB) void k_bi_dot1(long long n, const val_t *__res
 }
 
 // s = r - alpha v over r (, shat = dinv o s)
+template <class T> struct BiHalf { T r, v, d; };
 __global__ __launch_bounds__(SVB) void k_bi_half(long long n, val_t *__restrict__ r, const val_t *__restrict__ v, const val_t *__restrict__ dinv, val_t *__restrict__ shat,
                                                  const double *__restrict__ psig, int np, const BiScal *__restrict__ S)
 {
@@ -83,59 +69,25 @@ __global__ __launch_bounds__(SVB) void k_bi_half(long long n, val_t *__restrict_
     const double sigma = fold(psig, np, s), rho = S->rho;
     if (!S->live || rho == 0.0 || sigma == 0.0) return;
     const val_t alpha = (val_t)(rho / sigma);
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vr[SV_U], vv[SV_U], vd[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                vr[u] = lanes(r)[i]; vv[u] = lanes(v)[i];
-                if (dinv) vd[u] = lanes(dinv)[i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t ns = vr[u] - alpha * vv[u];
-                lanes(r)[i] = ns;
-                if (dinv) lanes(shat)[i] = vd[u] * ns;
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t ns = r[i] - alpha * v[i];
-            r[i] = ns;
-            if (dinv) shat[i] = dinv[i] * ns;
-        }
+    sv_walk_loaded<BiHalf>(
+        n, gridDim.x,
+        [&](auto at, auto &t) {
+            t.r = at(r); t.v = at(v);
+            if (dinv) t.d = at(dinv);
+        },
+        [&](auto at, const auto &t) {
+            const auto ns = t.r - alpha * t.v;
+            at.put(r, ns);
+            if (dinv) at.put(shat, t.d * ns);
+        });
 }
 
 __global__ __launch_bounds__(SVB) void k_bi_dot2(long long n, const val_t *__restrict__ t, const val_t *__restrict__ sv, double *__restrict__ pts, double *__restrict__ ptt,
                                                  const double *__restrict__ psig, int np, BiScal *__restrict__ S)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double ats = 0.0, att = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t a[SV_U], b[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) { a[u] = lanes(t)[i]; b[u] = lanes(sv)[i]; }
-            else { a[u] = (val_t)0; b[u] = (val_t)0; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++)
-#pragma unroll
-            for (int q = 0; q < SV_VPL; q++) {
-                ats += (double)a[u][q] * (double)b[u][q];
-                att += (double)a[u][q] * (double)a[u][q];
-            }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) { ats += (double)t[i] * (double)sv[i]; att += (double)t[i] * (double)t[i]; }
+    sv_dot(n, gridDim.x, t, sv, [&](auto a, auto b) { sv_mac(ats, a, b); sv_mac(att, a, a); });
     const double tts = block_sum(ats, s), ttt = block_sum(att, s);
     if (threadIdx.x == 0) { pts[blockIdx.x] = tts; ptt[blockIdx.x] = ttt; }
     if (blockIdx.x == 0) {   // alpha as the half step formed it, for the two kernels that follow
@@ -146,6 +98,7 @@ __global__ __launch_bounds__(SVB) void k_bi_dot2(long long n, const val_t *__res
 }
 
 // x += alpha phat + omega shat;  r = s - omega t (s lives in r; shat = NULL: shat is s)
+template <class T> struct BiUpdate { T x, phat, s, shat, t, rhat; };
 __global__ __launch_bounds__(SVB) void k_bi_update(long long n, val_t *__restrict__ x, const val_t *__restrict__ phat, val_t *__restrict__ r, const val_t *__restrict__ shat,
                                                    const val_t *__restrict__ t, const val_t *__restrict__ rhat, const double *__restrict__ pts, const double *__restrict__ ptt,
                                                    double *__restrict__ prr, double *__restrict__ prho, int np, const BiScal *__restrict__ S)
@@ -154,49 +107,27 @@ __global__ __launch_bounds__(SVB) void k_bi_update(long long n, val_t *__restric
     if (!S->live || S->half_broke) return;
     const double ts = fold(pts, np, s), tt = fold(ptt, np, s);
     const val_t alpha = (val_t)S->alpha, omega = (val_t)bi_omega(ts, tt);
-    const long long nv = n / SV_VPL;
     double arr = 0.0, arho = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vx[SV_U], vp[SV_U], vs[SV_U], vh[SV_U], vt[SV_U], vq[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                vx[u] = lanes(x)[i]; vp[u] = lanes(phat)[i]; vs[u] = lanes(r)[i];
-                vt[u] = lanes(t)[i]; vq[u] = lanes(rhat)[i];
-                if (shat) vh[u] = lanes(shat)[i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t sh = shat ? vh[u] : vs[u];
-                const svec_t nx = vx[u] + alpha * vp[u] + omega * sh, nr = vs[u] - omega * vt[u];
-                lanes(x)[i] = nx;
-                lanes(r)[i] = nr;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) {
-                    arr += (double)nr[q] * (double)nr[q];
-                    arho += (double)vq[u][q] * (double)nr[q];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t sh = shat ? shat[i] : r[i];
-            const val_t nx = x[i] + alpha * phat[i] + omega * sh, nr = r[i] - omega * t[i];
-            x[i] = nx;
-            r[i] = nr;
-            arr += (double)nr * (double)nr;
-            arho += (double)rhat[i] * (double)nr;
-        }
+    sv_walk_loaded<BiUpdate>(
+        n, gridDim.x,
+        [&](auto at, auto &v) {
+            v.x = at(x); v.phat = at(phat); v.s = at(r); v.t = at(t); v.rhat = at(rhat);
+            if (shat) v.shat = at(shat);
+        },
+        [&](auto at, const auto &v) {
+            const auto sh = shat ? v.shat : v.s;
+            const auto nx = v.x + alpha * v.phat + omega * sh, nr = v.s - omega * v.t;
+            at.put(x, nx);
+            at.put(r, nr);
+            sv_mac(arr, nr, nr);
+            sv_mac(arho, v.rhat, nr);
+        });
     const double trr = block_sum(arr, s), trho = block_sum(arho, s);
     if (threadIdx.x == 0) { prr[blockIdx.x] = trr; prho[blockIdx.x] = trho; }
 }
 
 // p = r + beta (p - omega v) (, phat = dinv o p)
+template <class T> struct BiDirection { T r, p, v, d; };
 __global__ __launch_bounds__(SVB) void k_bi_direction(long long n, const val_t *__restrict__ r, val_t *__restrict__ p, const val_t *__restrict__ v, const val_t *__restrict__ dinv,
                                                       val_t *__restrict__ phat, const double *__restrict__ pts, const double *__restrict__ ptt, const double *__restrict__ prr,
                                                       const double *__restrict__ prho, int np, BiScal *__restrict__ S)
@@ -219,33 +150,17 @@ __global__ __launch_bounds__(SVB) void k_bi_direction(long long n, const val_t *
     if (!go || om == 0.0) return;
     const double rho_new = fold(prho, np, s);
     const val_t beta = (val_t)((rho_new / S->rho) * (S->alpha / om)), omega = (val_t)om;
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vr[SV_U], vp[SV_U], vv[SV_U], vd[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                vr[u] = lanes(r)[i]; vp[u] = lanes(p)[i]; vv[u] = lanes(v)[i];
-                if (dinv) vd[u] = lanes(dinv)[i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t np_ = vr[u] + beta * (vp[u] - omega * vv[u]);
-                lanes(p)[i] = np_;
-                if (dinv) lanes(phat)[i] = vd[u] * np_;
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t np_ = r[i] + beta * (p[i] - omega * v[i]);
-            p[i] = np_;
-            if (dinv) phat[i] = dinv[i] * np_;
-        }
+    sv_walk_loaded<BiDirection>(
+        n, gridDim.x,
+        [&](auto at, auto &t) {
+            t.r = at(r); t.p = at(p); t.v = at(v);
+            if (dinv) t.d = at(dinv);
+        },
+        [&](auto at, const auto &t) {
+            const auto np_ = t.r + beta * (t.p - omega * t.v);
+            at.put(p, np_);
+            if (dinv) at.put(phat, t.d * np_);
+        });
 }
 
 // the start of a solve: r = rhat = p = b - A x (Ax holds the product) (, phat = dinv o p), partial sums of r.r (= rhat.r) and b.b
@@ -254,33 +169,16 @@ __global__ __launch_bounds__(SVB) void k_bi_begin(long long n, const val_t *__re
                                                   double *__restrict__ pbb)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double arr = 0.0, abb = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t vb = lanes(b)[i], nr = vb - lanes(Ax)[i];
-                lanes(r)[i] = nr;
-                lanes(rhat)[i] = nr;
-                lanes(p)[i] = nr;
-                if (dinv) lanes(phat)[i] = lanes(dinv)[i] * nr;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) {
-                    arr += (double)nr[q] * (double)nr[q];
-                    abb += (double)vb[q] * (double)vb[q];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t nr = b[i] - Ax[i];
-            r[i] = nr; rhat[i] = nr; p[i] = nr;
-            if (dinv) phat[i] = dinv[i] * nr;
-            arr += (double)nr * (double)nr; abb += (double)b[i] * (double)b[i];
-        }
+    sv_walk(n, gridDim.x, [&](auto at) {
+        const auto vb = at(b), nr = vb - at(Ax);
+        at.put(r, nr);
+        at.put(rhat, nr);
+        at.put(p, nr);
+        if (dinv) at.put(phat, at(dinv) * nr);
+        sv_mac(arr, nr, nr);
+        sv_mac(abb, vb, vb);
+    });
     const double trr = block_sum(arr, s), tbb = block_sum(abb, s);
     if (threadIdx.x == 0) { prr[blockIdx.x] = trr; prho[blockIdx.x] = trr; pbb[blockIdx.x] = tbb; }
 }

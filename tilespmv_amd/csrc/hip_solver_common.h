@@ -1,5 +1,6 @@
 // hip_solver_common.h — what the device-resident solvers share (hip_solver.hip, hip_solver_mv.hip, hip_solver_ls.hip, hip_solver_bi.hip, hip_solver_mr.hip, hip_solver_gm.hip): the launch shape, the number of
-// partial sums, the reduction tree, the walk over a vector, and the host-side driver around the kernels: the one allocation (DeviceBlock), the versioned state structs (cg_state_of,
+// partial sums, the reduction tree, the walk over a vector in its three forms (sv_walk, sv_walk_loaded, sv_dot: a kernel states its element-wise body once, for the 16-byte lane
+// vectors and the scalar tail alike), and the host-side driver around the kernels: the one allocation (DeviceBlock), the versioned state structs (cg_state_of,
 // state_read, put_versioned), the loop of *_solve with its convergence test (solve_loop, RrBbTest), the start of a create and the end of a solver (square_system, destroy_solver),
 // and the one-thread-per-row launch of tilespmv_csr_*_device (launch_per_row).
 //
@@ -61,6 +62,87 @@ __device__ __forceinline__ const svec_t *lanes(const val_t *p) { return reinterp
 // blockIdx.x + nwg, ...; the n % SV_VPL elements behind them belong to thread 0 of workgroup 0 (scalar accesses: nothing past element n - 1 of a caller's vector is touched).
 // nwg is gridDim.x, or less: then the kernel keeps the workgroups from nwg on out of the walk itself (no guard here: it would cost the kernels that need none).
 #define SV_FOR_TRIPS(base, nv, nwg) for (long long base = (long long)blockIdx.x * (SV_U * SVB) + threadIdx.x; base < (nv); base += (long long)(nwg) * (SV_U * SVB))
+
+// A kernel states its element-wise body ONCE, as a generic lambda over a position of the walk: SvLane (lane vector v, values are svec_t) in the trips, SvTail (element i, values are
+// val_t) in the scalar tail.  at(p) loads from the vector p, at.put(p, x) stores; the arithmetic in between is the same expression on either value type, so the two forms round alike.
+// SV_FOR_TRIPS is still written out where a trip is more than that: the loops over the basis of hip_solver_gm.hip (gm_group_dots, gm_subtract, k_gm_update), the per-column
+// accumulators of hip_solver_mv.hip (k_cgm_*), the LDS slab of hip_precond.hip (k_bj_apply).
+struct SvLane {
+    long long v;
+    __device__ __forceinline__ svec_t operator()(const val_t *p) const { return lanes(p)[v]; }
+    __device__ __forceinline__ void put(val_t *p, svec_t x) const { lanes(p)[v] = x; }
+};
+struct SvTail {
+    long long i;
+    __device__ __forceinline__ val_t operator()(const val_t *p) const { return p[i]; }
+    __device__ __forceinline__ void put(val_t *p, val_t x) const { p[i] = x; }
+};
+// acc += a . b in double: the SV_VPL products of a lane vector in element order, or the one product of a tail element
+__device__ __forceinline__ void sv_mac(double &acc, svec_t a, svec_t b)
+{
+#pragma unroll
+    for (int q = 0; q < SV_VPL; q++) acc += (double)a[q] * (double)b[q];
+}
+__device__ __forceinline__ void sv_mac(double &acc, val_t a, val_t b) { acc += (double)a * (double)b; }
+
+// f(at) at every position of a vector of n elements: a lane vector is loaded, used and stored before the trip's next one is touched
+template <class F> __device__ __forceinline__ void sv_walk(long long n, int nwg, F f)
+{
+    const long long nv = n / SV_VPL;
+    SV_FOR_TRIPS(base, nv, nwg) {
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) f(SvLane{v});
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long i = nv * SV_VPL; i < n; i++) f(SvTail{i});
+}
+// The same in two phases: load(at, t) fills the kernel's value struct Vals<svec_t or val_t> t, use(at, t) computes and stores.  All SV_U loads of a trip are issued before any
+// arithmetic: more bytes in flight (and more registers) than sv_walk, for the kernels of the iteration that are bound by the memory.
+template <template <class> class Vals, class Load, class Use> __device__ __forceinline__ void sv_walk_loaded(long long n, int nwg, Load load, Use use)
+{
+    const long long nv = n / SV_VPL;
+    SV_FOR_TRIPS(base, nv, nwg) {
+        Vals<svec_t> t[SV_U];
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) load(SvLane{v}, t[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) use(SvLane{v}, t[u]);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long i = nv * SV_VPL; i < n; i++) {
+            Vals<val_t> t;
+            load(SvTail{i}, t);
+            use(SvTail{i}, t);
+        }
+}
+// The pure dot kernels: f(a, b) with the values of the vectors a and b at every position (a == b: of the one vector).  Nothing is stored, so the lane vectors behind the end of a
+// partial last trip are zeros and f runs unguarded: f adds into 1-3 accumulators with sv_mac, and a zero adds nothing.
+template <class F> __device__ __forceinline__ void sv_dot(long long n, int nwg, const val_t *a, const val_t *b, F f)
+{
+    const long long nv = n / SV_VPL;
+    SV_FOR_TRIPS(base, nv, nwg) {
+        svec_t va[SV_U], vb[SV_U];
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) {
+            const long long v = base + u * SVB;
+            if (v < nv) { va[u] = lanes(a)[v]; vb[u] = lanes(b)[v]; }
+            else { va[u] = (val_t)0; vb[u] = (val_t)0; }
+        }
+#pragma unroll
+        for (int u = 0; u < SV_U; u++) f(va[u], vb[u]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (long long i = nv * SV_VPL; i < n; i++) f(a[i], b[i]);
+}
 
 // the tail of the k_csr_* kernels under `invert`: 1 / d, 1 where d is 0 (a macro: as an inlined function it reaches the kernels as a select, and their code changes)
 #define SV_INVERSE_OR_ONE(d) ((d) == (val_t)0 ? (val_t)1 : (val_t)1 / (d))

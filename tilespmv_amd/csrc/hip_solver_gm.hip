@@ -24,7 +24,8 @@
 // 2 MiB, where a kernel is bound by its launch.  MEASURED (scripts/gmres_time.py, profiles/gmres_fused_ab.txt): with 256 workgroups everywhere a 16.8 M-row fp64 system took 3.14 ms per inner iteration of GMRES(30),
 // with 1024 there 1.96 ms — one workgroup per CU does not keep enough loads in flight.  A fold is done by the four waves in turn, each sum by one wave in a fixed order: the same
 // bits in every workgroup, no finishing launch, no atomics.
-// The scalar tail, block_sum and the walk over a vector are those of hip_solver_common.h.  h1_i, h2_i, 1 / h_{j+1,j}, 1 / beta and y_i are formed in double and rounded to the value
+// The scalar tail, block_sum and the walk over a vector are those of hip_solver_common.h: k_gm_next, k_gm_resid and k_gm_axpy hand their body to sv_walk; gm_group_dots, gm_subtract
+// and k_gm_update loop over the basis inside a trip and write SV_FOR_TRIPS and the tail out.  h1_i, h2_i, 1 / h_{j+1,j}, 1 / beta and y_i are formed in double and rounded to the value
 // type once, where they multiply.
 //
 // The scalar block (GmScal) and the small arrays have ONE writing kernel per field, and no kernel reads a field that it (or a concurrent workgroup of it) writes:
@@ -266,24 +267,11 @@ __global__ __launch_bounds__(SVB) void k_gm_next(long long n, const val_t *__res
     if (!form) return;
     const val_t scale = (val_t)(1.0 / hh);
     val_t *__restrict__ Vn = V + (long long)(jc + 1) * stride;
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t v = scale * lanes(w)[i];
-                lanes(Vn)[i] = v;
-                if (dinv) lanes(zhat)[i] = lanes(dinv)[i] * v;
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t v = scale * w[i];
-            Vn[i] = v;
-            if (dinv) zhat[i] = dinv[i] * v;
-        }
+    sv_walk(n, gridDim.x, [&](auto at) {
+        const auto v = scale * at(w);
+        at.put(Vn, v);
+        if (dinv) at.put(zhat, at(dinv) * v);
+    });
 }
 
 // r = b - A x over the product (w holds A x) with the partial sums of r.r; at the start of a solve (bcopy != NULL) also the solver's copy of b and the partial sums of b.b
@@ -291,31 +279,14 @@ __global__ __launch_bounds__(SVB) void k_gm_resid(long long n, const val_t *__re
                                                   double *__restrict__ pbb)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double arr = 0.0, abb = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t vb = lanes(b)[i], nr = vb - lanes(w)[i];
-                lanes(w)[i] = nr;
-                if (bcopy) lanes(bcopy)[i] = vb;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) {
-                    arr += (double)nr[q] * (double)nr[q];
-                    abb += (double)vb[q] * (double)vb[q];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t vb = b[i], nr = vb - w[i];
-            w[i] = nr;
-            if (bcopy) bcopy[i] = vb;
-            arr += (double)nr * (double)nr; abb += (double)vb * (double)vb;
-        }
+    sv_walk(n, gridDim.x, [&](auto at) {
+        const auto vb = at(b), nr = vb - at(w);
+        at.put(w, nr);
+        if (bcopy) at.put(bcopy, vb);
+        sv_mac(arr, nr, nr);
+        sv_mac(abb, vb, vb);
+    });
     const double trr = block_sum(arr, s), tbb = block_sum(abb, s);
     if (threadIdx.x == 0) {
         pnorm[blockIdx.x] = trr;
@@ -398,16 +369,7 @@ __global__ __launch_bounds__(SVB) void k_gm_update(long long n, val_t *__restric
 __global__ __launch_bounds__(SVB) void k_gm_axpy(long long n, val_t *__restrict__ x, const val_t *__restrict__ z, int restart, const GmScal *__restrict__ S)
 {
     if (gm_close_columns(S, restart) == 0) return;
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) lanes(x)[i] = lanes(x)[i] + lanes(z)[i];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) x[i] = x[i] + z[i];
+    sv_walk(n, gridDim.x, [&](auto at) { at.put(x, at(x) + at(z)); });
 }
 
 }  // namespace

@@ -11,7 +11,8 @@
 // damping adds 3 cols (p in the dot; x read and s stored in the normal pass), cinv adds 2 cols (read in the normal and the direction pass).
 // The loop of torch operations it replaces (operator.cgls) moves 7 rows + 12 cols in about a dozen launches.
 //
-// The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail are those of hip_solver_common.h.  Row-length sums
+// The launch shape and the partial sums with their fixed order of additions are those of hip_solver_common.h, and so is the walk over a vector: every kernel here hands its body,
+// written once for lane vectors and tail elements alike, to sv_dot, sv_walk_loaded or sv_walk.  Row-length sums
 // (q.q, r.r, b.b) have npr = solver_parts(rows) partials, column-length sums (p.p, s.s, s.z) npc = solver_parts(cols).  A kernel that walks both lengths is launched over
 // max(npr, npc) workgroups, so every walk here is guarded: the workgroups from the vector's own count on skip it.  alpha, beta and damp^2 are rounded to the value type once,
 // where they multiply.
@@ -39,23 +40,8 @@ struct LsScal {
 // partial sums of v.v over n elements
 __device__ __forceinline__ double sq_partial(long long n, const val_t *__restrict__ v, int nwg)
 {
-    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    if ((int)blockIdx.x < nwg) SV_FOR_TRIPS(base, nv, nwg) {
-        svec_t a[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) a[u] = lanes(v)[i];
-            else a[u] = (val_t)0;
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++)
-#pragma unroll
-            for (int k = 0; k < SV_VPL; k++) acc += (double)a[u][k] * (double)a[u][k];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) acc += (double)v[i] * (double)v[i];
+    if ((int)blockIdx.x < nwg) sv_dot(n, nwg, v, v, [&](auto a, auto) { sv_mac(acc, a, a); });
     return acc;
 }
 
@@ -76,6 +62,7 @@ __global__ __launch_bounds__(SVB) void k_ls_dot(long long rows, long long cols, 
     }
 }
 
+template <class T> struct LsAxpy { T a, y; };   // y +- alpha a
 __global__ __launch_bounds__(SVB) void k_ls_update(long long rows, long long cols, const val_t *__restrict__ p, const val_t *__restrict__ q, val_t *__restrict__ x,
                                                    val_t *__restrict__ r, const double *__restrict__ pqq, const double *__restrict__ ppp, double *__restrict__ prr, int npr, int npc,
                                                    LsScal *__restrict__ S)
@@ -87,53 +74,25 @@ __global__ __launch_bounds__(SVB) void k_ls_update(long long rows, long long col
     const bool broke = gamma < 0.0 || (gamma > 0.0 && !(delta > 0.0));
     const val_t alpha = (val_t)((gamma > 0.0 && delta > 0.0) ? gamma / delta : 0.0);
     if (broke && blockIdx.x == 0 && threadIdx.x == 0) S->breakdown = 1;
-    const long long nvc = cols / SV_VPL, nvr = rows / SV_VPL;
-    if ((int)blockIdx.x < npc) SV_FOR_TRIPS(base, nvc, npc) {
-        svec_t vp[SV_U], vx[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nvc) { vp[u] = lanes(p)[v]; vx[u] = lanes(x)[v]; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nvc) lanes(x)[v] = vx[u] + alpha * vp[u];
-        }
-    }
+    if ((int)blockIdx.x < npc)
+        sv_walk_loaded<LsAxpy>(
+            cols, npc, [&](auto at, auto &t) { t.a = at(p); t.y = at(x); }, [&](auto at, const auto &t) { at.put(x, t.y + alpha * t.a); });
     double arr = 0.0;
-    if ((int)blockIdx.x < npr) SV_FOR_TRIPS(base, nvr, npr) {
-        svec_t vq[SV_U], vr[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nvr) { vq[u] = lanes(q)[v]; vr[u] = lanes(r)[v]; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nvr) {
-                const svec_t nr = vr[u] - alpha * vq[u];
-                lanes(r)[v] = nr;
-#pragma unroll
-                for (int k = 0; k < SV_VPL; k++) arr += (double)nr[k] * (double)nr[k];
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (long long i = nvc * SV_VPL; i < cols; i++) x[i] = x[i] + alpha * p[i];
-        for (long long i = nvr * SV_VPL; i < rows; i++) {
-            const val_t nr = r[i] - alpha * q[i];
-            r[i] = nr;
-            arr += (double)nr * (double)nr;
-        }
-    }
+    if ((int)blockIdx.x < npr)
+        sv_walk_loaded<LsAxpy>(
+            rows, npr, [&](auto at, auto &t) { t.a = at(q); t.y = at(r); },
+            [&](auto at, const auto &t) {
+                const auto nr = t.y - alpha * t.a;
+                at.put(r, nr);
+                sv_mac(arr, nr, nr);
+            });
     const double trr = block_sum(arr, s);
     if (threadIdx.x == 0 && (int)blockIdx.x < npr) prr[blockIdx.x] = trr;
 }
 
 // The normal residual s = A^T r (the product left it) - damp^2 x, its squared norm and s.z.  plain != 0: s as it stands, no damping, no cinv (|A^T b|^2 at the start of a solve).
 // p_out != NULL (the start of a solve): p = z as well.
+template <class T> struct LsNormal { T s, x, c; };
 __global__ __launch_bounds__(SVB) void k_ls_normal(long long cols, val_t *__restrict__ sv, const val_t *__restrict__ x, const val_t *__restrict__ cinv_, double *__restrict__ pss,
                                                    double *__restrict__ psz, val_t *__restrict__ p_out, int plain, int npc, const LsScal *__restrict__ S)
 {
@@ -141,44 +100,23 @@ __global__ __launch_bounds__(SVB) void k_ls_normal(long long cols, val_t *__rest
     const val_t d2 = plain ? (val_t)0 : (val_t)S->damp2;
     const val_t *__restrict__ cinv = plain ? nullptr : cinv_;
     const bool damped = d2 != (val_t)0;
-    const long long nv = cols / SV_VPL;
     double ass = 0.0, asz = 0.0;
-    if ((int)blockIdx.x < npc) SV_FOR_TRIPS(base, nv, npc) {
-        svec_t vs[SV_U], vx[SV_U], vc[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                vs[u] = lanes(sv)[v];
-                if (damped) vx[u] = lanes(x)[v];
-                if (cinv) vc[u] = lanes(cinv)[v];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                svec_t ns = vs[u];
-                if (damped) { ns = vs[u] - d2 * vx[u]; lanes(sv)[v] = ns; }
-                const svec_t z = cinv ? vc[u] * ns : ns;
-                if (p_out) lanes(p_out)[v] = z;
-#pragma unroll
-                for (int k = 0; k < SV_VPL; k++) {
-                    ass += (double)ns[k] * (double)ns[k];
-                    if (cinv) asz += (double)ns[k] * (double)z[k];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < cols; i++) {
-            val_t ns = sv[i];
-            if (damped) { ns = ns - d2 * x[i]; sv[i] = ns; }
-            const val_t z = cinv ? (val_t)(cinv[i] * ns) : ns;
-            if (p_out) p_out[i] = z;
-            ass += (double)ns * (double)ns;
-            if (cinv) asz += (double)ns * (double)z;
-        }
+    if ((int)blockIdx.x < npc)
+        sv_walk_loaded<LsNormal>(
+            cols, npc,
+            [&](auto at, auto &t) {
+                t.s = at(sv);
+                if (damped) t.x = at(x);
+                if (cinv) t.c = at(cinv);
+            },
+            [&](auto at, const auto &t) {
+                auto ns = t.s;
+                if (damped) { ns = t.s - d2 * t.x; at.put(sv, ns); }
+                const auto z = cinv ? t.c * ns : ns;
+                if (p_out) at.put(p_out, z);
+                sv_mac(ass, ns, ns);
+                if (cinv) sv_mac(asz, ns, z);
+            });
     const double tss = block_sum(ass, s);
     if (threadIdx.x == 0) pss[blockIdx.x] = tss;
     if (cinv) {   // (without cinv: s.z is s.s, and psz is pss)
@@ -187,6 +125,7 @@ __global__ __launch_bounds__(SVB) void k_ls_normal(long long cols, val_t *__rest
     }
 }
 
+template <class T> struct LsDirection { T s, p, c; };
 __global__ __launch_bounds__(SVB) void k_ls_direction(long long cols, const val_t *__restrict__ sv, val_t *__restrict__ p, const val_t *__restrict__ cinv,
                                                       const double *__restrict__ pss, const double *__restrict__ psz, const double *__restrict__ prr, int npr, int npc,
                                                       LsScal *__restrict__ S)
@@ -198,28 +137,17 @@ __global__ __launch_bounds__(SVB) void k_ls_direction(long long cols, const val_
         const double nn = cinv ? fold(pss, npc, s) : g_new, rr = fold(prr, npr, s);
         if (threadIdx.x == 0) { S->nn = nn; S->rr = rr; S->iterations = S->iterations + 1; }
     }
-    const long long nv = cols / SV_VPL;
-    if ((int)blockIdx.x < npc) SV_FOR_TRIPS(base, nv, npc) {
-        svec_t vs[SV_U], vp[SV_U], vc[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                vs[u] = lanes(sv)[v]; vp[u] = lanes(p)[v];
-                if (cinv) vc[u] = lanes(cinv)[v];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                const svec_t z = cinv ? vc[u] * vs[u] : vs[u];
-                lanes(p)[v] = z + beta * vp[u];
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < cols; i++) p[i] = (cinv ? (val_t)(cinv[i] * sv[i]) : sv[i]) + beta * p[i];
+    if ((int)blockIdx.x < npc)
+        sv_walk_loaded<LsDirection>(
+            cols, npc,
+            [&](auto at, auto &t) {
+                t.s = at(sv); t.p = at(p);
+                if (cinv) t.c = at(cinv);
+            },
+            [&](auto at, const auto &t) {
+                const auto z = cinv ? t.c * t.s : t.s;
+                at.put(p, z + beta * t.p);
+            });
 }
 
 // the start of a solve: r = b - A x (Ax holds the product), partial sums of r.r and b.b; the damping of this solve goes into the scalar block
@@ -227,31 +155,15 @@ __global__ __launch_bounds__(SVB) void k_ls_begin_r(long long rows, const val_t 
                                                     double *__restrict__ pbb, double damp2, int npr, LsScal *__restrict__ S)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = rows / SV_VPL;
     double arr = 0.0, abb = 0.0;
-    if ((int)blockIdx.x < npr) SV_FOR_TRIPS(base, nv, npr) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long v = base + u * SVB;
-            if (v < nv) {
-                const svec_t vb = lanes(b)[v], nr = vb - lanes(Ax)[v];
-                lanes(r)[v] = nr;
-#pragma unroll
-                for (int k = 0; k < SV_VPL; k++) {
-                    arr += (double)nr[k] * (double)nr[k];
-                    abb += (double)vb[k] * (double)vb[k];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (long long i = nv * SV_VPL; i < rows; i++) {
-            const val_t nr = b[i] - Ax[i];
-            r[i] = nr;
-            arr += (double)nr * (double)nr; abb += (double)b[i] * (double)b[i];
-        }
-        S->damp2 = damp2;
-    }
+    if ((int)blockIdx.x < npr)
+        sv_walk(rows, npr, [&](auto at) {
+            const auto vb = at(b), nr = vb - at(Ax);
+            at.put(r, nr);
+            sv_mac(arr, nr, nr);
+            sv_mac(abb, vb, vb);
+        });
+    if (blockIdx.x == 0 && threadIdx.x == 0) S->damp2 = damp2;
     const double trr = block_sum(arr, s), tbb = block_sum(abb, s);
     if (threadIdx.x == 0) { prr[blockIdx.x] = trr; pbb[blockIdx.x] = tbb; }
 }

@@ -12,8 +12,8 @@
 // and 16.25 KB of partial sums and scalars.
 // The three-term history is not rotated on the host (a captured iterate(k) has its pointers baked in) and not shifted by copies either: the kernels choose roles from the parity of
 // the DEVICE-side iteration counter.  In an iteration of parity p, r2 is R[p], r1 is R[1 - p] and receives y' (the next r2); w is W[p], w2 is W[1 - p] and receives w'.
-// The launch shape, the partial sums with their fixed order of additions, and the walk over a vector with its scalar tail are those of hip_solver_common.h; the number of partials
-// is solver_parts(n).  1/beta, alfa/beta, beta/oldb, oldeps, delta, 1/gamma and phi are formed in double and rounded to the value type once, where they multiply.
+// The launch shape and the partial sums with their fixed order of additions are those of hip_solver_common.h, and so is the walk over a vector: every kernel here hands its body,
+// written once for lane vectors and tail elements alike, to sv_dot, sv_walk_loaded or sv_walk.  The number of partials is solver_parts(n).  1/beta, alfa/beta, beta/oldb, oldeps, delta, 1/gamma and phi are formed in double and rounded to the value type once, where they multiply.
 //
 // The scalar block (MrScal) has ONE writing kernel per field and no kernel reads a field it (or a concurrent workgroup of it) writes:
 //   at (beta, oldb, dbar, epsln, phibar, cs, sn), parity, live   k_mr_dot, workgroup 0: the recurrence as the previous iteration left it (a copy of `next`), the parity of the
@@ -52,25 +52,8 @@ __global__ __launch_bounds__(SVB) void k_mr_dot(long long n, const val_t *__rest
 {
     __shared__ double s[SVB / 64];
     const val_t ib = (val_t)mr_inverse(S->next.beta);
-    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t a[SV_U], b[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) { a[u] = lanes(V)[i]; b[u] = lanes(y)[i]; }
-            else { a[u] = (val_t)0; b[u] = (val_t)0; }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const svec_t va = ib * a[u], vb = ib * b[u];
-#pragma unroll
-            for (int q = 0; q < SV_VPL; q++) acc += (double)va[q] * (double)vb[q];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) acc += (double)(ib * V[i]) * (double)(ib * y[i]);
+    sv_dot(n, gridDim.x, V, y, [&](auto a, auto b) { sv_mac(acc, ib * a, ib * b); });
     const double t = block_sum(acc, s);
     if (threadIdx.x == 0) {
         palfa[blockIdx.x] = t;
@@ -83,6 +66,7 @@ __global__ __launch_bounds__(SVB) void k_mr_dot(long long n, const val_t *__rest
 }
 
 // y' = y / beta - (beta / oldb) r1 - (alfa / beta) r2 over r1;  partial sums of y'.(minv o y')
+template <class T> struct MrLanczos { T y, r1, r2, d; };
 __global__ __launch_bounds__(SVB) void k_mr_lanczos(long long n, const val_t *__restrict__ y, val_t *__restrict__ Ra, val_t *__restrict__ Rb, const val_t *__restrict__ minv,
                                                     const double *__restrict__ palfa, double *__restrict__ pbeta, int np, const MrScal *__restrict__ S)
 {
@@ -92,41 +76,24 @@ __global__ __launch_bounds__(SVB) void k_mr_lanczos(long long n, const val_t *__
     const val_t ib = (val_t)(1.0 / beta), c1 = (val_t)(oldb != 0.0 ? beta / oldb : 0.0), c2 = (val_t)(alfa / beta);
     const val_t *const r2 = S->parity ? Rb : Ra;
     val_t *const r1 = S->parity ? Ra : Rb;
-    const long long nv = n / SV_VPL;
     double acc = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vy[SV_U], v1[SV_U], v2[SV_U], vd[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                vy[u] = lanes(y)[i]; v1[u] = lanes(r1)[i]; v2[u] = lanes(r2)[i];
-                if (minv) vd[u] = lanes(minv)[i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t ny = ib * vy[u] - c1 * v1[u] - c2 * v2[u];
-                lanes(r1)[i] = ny;
-                const svec_t nz = minv ? vd[u] * ny : ny;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) acc += (double)ny[q] * (double)nz[q];
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t ny = ib * y[i] - c1 * r1[i] - c2 * r2[i];
-            r1[i] = ny;
-            acc += (double)ny * (double)(minv ? minv[i] * ny : ny);
-        }
+    sv_walk_loaded<MrLanczos>(
+        n, gridDim.x,
+        [&](auto at, auto &t) {
+            t.y = at(y); t.r1 = at(r1); t.r2 = at(r2);
+            if (minv) t.d = at(minv);
+        },
+        [&](auto at, const auto &t) {
+            const auto ny = ib * t.y - c1 * t.r1 - c2 * t.r2;
+            at.put(r1, ny);
+            sv_mac(acc, ny, minv ? t.d * ny : ny);
+        });
     const double t = block_sum(acc, s);
     if (threadIdx.x == 0) pbeta[blockIdx.x] = t;
 }
 
 // the rotation;  w' = (v - oldeps w2 - delta w) / gamma over w2;  x += phi w';  V = minv o y'
+template <class T> struct MrUpdate { T x, v, w, w2, yn, d; };
 __global__ __launch_bounds__(SVB) void k_mr_update(long long n, val_t *__restrict__ x, val_t *__restrict__ V, val_t *__restrict__ Wa, val_t *__restrict__ Wb,
                                                    const val_t *__restrict__ Ra, const val_t *__restrict__ Rb, const val_t *__restrict__ minv, const double *__restrict__ palfa,
                                                    const double *__restrict__ pbeta, int np, MrScal *__restrict__ S)
@@ -156,35 +123,18 @@ __global__ __launch_bounds__(SVB) void k_mr_update(long long n, val_t *__restric
     const val_t ib = (val_t)(1.0 / c.beta), oe = (val_t)oldeps, de = (val_t)delta, ig = (val_t)(1.0 / gamma), phi = (val_t)phi64;
     const val_t *const w = S->parity ? Wb : Wa, *const yn = S->parity ? Ra : Rb;
     val_t *const w2 = S->parity ? Wa : Wb;
-    const long long nv = n / SV_VPL;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-        svec_t vx[SV_U], vv[SV_U], vw[SV_U], v2[SV_U], vy[SV_U], vd[SV_U];
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                vx[u] = lanes(x)[i]; vv[u] = lanes(V)[i]; vw[u] = lanes(w)[i]; v2[u] = lanes(w2)[i]; vy[u] = lanes(yn)[i];
-                if (minv) vd[u] = lanes(minv)[i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t nw = (ib * vv[u] - oe * v2[u] - de * vw[u]) * ig;
-                lanes(w2)[i] = nw;
-                lanes(x)[i] = vx[u] + phi * nw;
-                lanes(V)[i] = minv ? vd[u] * vy[u] : vy[u];
-            }
-        }
-    }
-    if (first)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t nw = (ib * V[i] - oe * w2[i] - de * w[i]) * ig;
-            w2[i] = nw;
-            x[i] = x[i] + phi * nw;
-            V[i] = minv ? minv[i] * yn[i] : yn[i];
-        }
+    sv_walk_loaded<MrUpdate>(
+        n, gridDim.x,
+        [&](auto at, auto &t) {
+            t.x = at(x); t.v = at(V); t.w = at(w); t.w2 = at(w2); t.yn = at(yn);
+            if (minv) t.d = at(minv);
+        },
+        [&](auto at, const auto &t) {
+            const auto nw = (ib * t.v - oe * t.w2 - de * t.w) * ig;
+            at.put(w2, nw);
+            at.put(x, t.x + phi * nw);
+            at.put(V, minv ? t.d * t.yn : t.yn);
+        });
 }
 
 // the start of a solve: r2 = b - A x (Ax holds the product) into R[0], V = z = minv o r2, r1 = w = w2 = 0, partial sums of r2.z and b.(minv o b)
@@ -193,35 +143,18 @@ __global__ __launch_bounds__(SVB) void k_mr_begin(long long n, const val_t *__re
                                                   double *__restrict__ pbb)
 {
     __shared__ double s[SVB / 64];
-    const long long nv = n / SV_VPL;
     double arz = 0.0, abb = 0.0;
-    SV_FOR_TRIPS(base, nv, gridDim.x) {
-#pragma unroll
-        for (int u = 0; u < SV_U; u++) {
-            const long long i = base + u * SVB;
-            if (i < nv) {
-                const svec_t vb = lanes(b)[i], nr = vb - lanes(Ax)[i];
-                svec_t nz = nr, mb = vb, zero;
-                if (minv) { const svec_t vd = lanes(minv)[i]; nz = vd * nr; mb = vd * vb; }
-                zero = (val_t)0;
-                lanes(Ra)[i] = nr;
-                lanes(V)[i] = nz;
-                lanes(Rb)[i] = zero; lanes(Wa)[i] = zero; lanes(Wb)[i] = zero;
-#pragma unroll
-                for (int q = 0; q < SV_VPL; q++) {
-                    arz += (double)nr[q] * (double)nz[q];
-                    abb += (double)vb[q] * (double)mb[q];
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (long long i = nv * SV_VPL; i < n; i++) {
-            const val_t nr = b[i] - Ax[i], nz = minv ? minv[i] * nr : nr, mb = minv ? minv[i] * b[i] : b[i];
-            Ra[i] = nr; V[i] = nz;
-            Rb[i] = (val_t)0; Wa[i] = (val_t)0; Wb[i] = (val_t)0;
-            arz += (double)nr * (double)nz; abb += (double)b[i] * (double)mb;
-        }
+    sv_walk(n, gridDim.x, [&](auto at) {
+        const auto vb = at(b), nr = vb - at(Ax);
+        auto nz = nr, mb = vb, zero = nr;
+        if (minv) { const auto vd = at(minv); nz = vd * nr; mb = vd * vb; }
+        zero = (val_t)0;
+        at.put(Ra, nr);
+        at.put(V, nz);
+        at.put(Rb, zero); at.put(Wa, zero); at.put(Wb, zero);
+        sv_mac(arz, nr, nz);
+        sv_mac(abb, vb, mb);
+    });
     const double trz = block_sum(arz, s), tbb = block_sum(abb, s);
     if (threadIdx.x == 0) { prz[blockIdx.x] = trz; pbb[blockIdx.x] = tbb; }
 }
