@@ -10,54 +10,15 @@ import pytest
 
 import block_jacobi_mirror as M
 import cg_mirror as CM
+import gpu_solver_util as U
 import solver_sizes as SS
+from gpu_solver_util import DTYPES, PRODUCT_TOL, SENTINEL, torch_cuda  # noqa: F401
 from tilespmv_amd import _lib, api
-from tilespmv_amd.operator import SparseOperator
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [np.float64, np.float32]
-PRODUCT_TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.float32): 1e-5}   # README: the project's per-product tolerance on real-valued data
-SENTINEL = 777.0
 CASES = [("lap55", bs) for bs in (1, 2, 3, 5, 7, 16)] + [("femblk10", bs) for bs in (3, 6, 16)]
 _CACHE = {}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _tt(torch, dt):
-    return torch.float64 if np.dtype(dt) == np.float64 else torch.float32
-
-
-def _vec(torch, a, n, dtype):
-    """A device vector of n elements with 16 sentinel elements behind it (the whole tensor)."""
-    t = torch.full((n + 16,), SENTINEL, dtype=_tt(torch, dtype), device="cuda")
-    if a is None:
-        t[:n].zero_()
-    else:
-        t[:n].copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)))
-    return t
-
-
-def _host(t, n):
-    return t.cpu().numpy()[:n].copy()
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _relerr(x, xs):
-    return float(np.linalg.norm(x.astype(np.float64) - xs) / np.linalg.norm(xs))
-
-
-def _dist(a, b):
-    return abs(a - b) / abs(b)
 
 
 def _system(name, dtype):
@@ -66,33 +27,23 @@ def _system(name, dtype):
     return n, rp, ci, v.astype(dt), M.rhs(n).astype(dt)
 
 
-def _device_csr(torch, rp, ci, v):
-    return torch.from_numpy(rp).cuda(), torch.from_numpy(ci).cuda(), torch.from_numpy(v).cuda()
-
-
 def _updated(torch, n, bs, dt, csr):
     bj = api.BlockJacobi(n, bs, dt)
-    bj.update(csr[0].data_ptr(), csr[1].data_ptr(), csr[2].data_ptr(), _stream(torch))
+    bj.update(csr[0].data_ptr(), csr[1].data_ptr(), csr[2].data_ptr(), U.stream(torch))
     return bj
 
 
 def _planes(torch, bj, n, bs, dt):
     """M^-1 as the library holds it, [bs, n], read by bs applies to indicator vectors."""
     P = np.zeros((bs, n), dtype=dt)
-    zd = _vec(torch, None, n, dt)
+    zd = U.vec(torch, None, n, dt)
     for j in range(bs):
         e = np.zeros(n, dtype=dt)
         e[j::bs] = 1
-        bj.apply(_vec(torch, e, n, dt).data_ptr(), zd.data_ptr(), _stream(torch))
+        bj.apply(U.vec(torch, e, n, dt).data_ptr(), zd.data_ptr(), U.stream(torch))
         torch.cuda.synchronize()
-        P[j] = _host(zd, n)
+        P[j] = U.host(zd, n)
     return P
-
-
-def _op(n, rp, ci, v, dtype, **kw):
-    kw.setdefault("deterministic", 1)
-    kw.setdefault("placement_tries", 1)
-    return SparseOperator(n, n, rp, ci, np.ascontiguousarray(v, dtype=dtype), dtype=dtype, **kw)
 
 
 def _solved(name, dtype):
@@ -105,7 +56,7 @@ def _solved(name, dtype):
         mirror = (M.BiCGStab if name.endswith("_ns") else M.CG)(M.scipy_csr(n, rp, ci, vt), dt, P)
         xm, itm, stm, relm = mirror.solve(b, rtol=M.RTOL[dt], maxiter=2000, check_every=1)
         assert stm == M.CONVERGED
-        _CACHE[(name, dt)] = (xs, itm, _relerr(xm, xs), P)
+        _CACHE[(name, dt)] = (xs, itm, U.relerr(xm, xs), P)
     return _CACHE[(name, dt)]
 
 
@@ -131,9 +82,9 @@ def test_the_inverse_equals_the_mirror(torch_cuda, name, bs, dtype):
     the value type, eps max|inv64| / 2, is inside it).  bs = 1 in fp64: the bits of tilespmv_csr_diagonal_device(invert = 1)."""
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, b = _system(name, dt)
-    csr = _device_csr(torch, rp, ci, vt)
+    csr = U.device_csr(torch, rp, ci, vt)
     with _updated(torch, n, bs, dt, csr) as bj:
-        info = bj.info(_stream(torch))
+        info = bj.info(U.stream(torch))
         got = _planes(torch, bj, n, bs, dt)
     nb = (n + bs - 1) // bs
     assert info == {"rows": n, "block_size": bs, "blocks": nb, "singular_blocks": 0, "device_bytes": info["device_bytes"], "dot_partials": SS.parts(n, SS.vpl(dt))}
@@ -145,10 +96,10 @@ def test_the_inverse_equals_the_mirror(torch_cuda, name, bs, dtype):
     if short:
         assert not got[short:, n - short:].any()
     if bs == 1 and dt == np.float64:
-        dinv = _vec(torch, None, n, dt)
-        api.csr_diagonal_device(n, csr[0].data_ptr(), csr[1].data_ptr(), csr[2].data_ptr(), dinv.data_ptr(), invert=True, stream=_stream(torch), dtype=dt)
+        dinv = U.vec(torch, None, n, dt)
+        api.csr_diagonal_device(n, csr[0].data_ptr(), csr[1].data_ptr(), csr[2].data_ptr(), dinv.data_ptr(), invert=True, stream=U.stream(torch), dtype=dt)
         torch.cuda.synchronize()
-        assert np.array_equal(got[0], _host(dinv, n))
+        assert np.array_equal(got[0], U.host(dinv, n))
 
 
 # ---- 2. pivoting, singular blocks
@@ -156,9 +107,9 @@ def test_the_inverse_equals_the_mirror(torch_cuda, name, bs, dtype):
 def test_pivoting_and_singular_blocks(torch_cuda, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, v = M.problem("pivot2")
-    csr = _device_csr(torch, rp, ci, v.astype(dt))
+    csr = U.device_csr(torch, rp, ci, v.astype(dt))
     with _updated(torch, n, 2, dt, csr) as bj:
-        assert bj.info(_stream(torch))["singular_blocks"] == 1
+        assert bj.info(U.stream(torch))["singular_blocks"] == 1
         P = _planes(torch, bj, n, 2, dt)
         third, half = dt.type(1.0 / 3.0), dt.type(0.5)
         for k in range(n // 2):
@@ -169,8 +120,8 @@ def test_pivoting_and_singular_blocks(torch_cuda, dtype):
         rows = np.repeat(np.arange(n), np.diff(rp))
         v2[(rows == 10) & (ci == 10)] = 3.0
         v2d = torch.from_numpy(v2.astype(dt)).cuda()
-        bj.update(csr[0].data_ptr(), csr[1].data_ptr(), v2d.data_ptr(), _stream(torch))
-        assert bj.info(_stream(torch))["singular_blocks"] == 0
+        bj.update(csr[0].data_ptr(), csr[1].data_ptr(), v2d.data_ptr(), U.stream(torch))
+        assert bj.info(U.stream(torch))["singular_blocks"] == 0
         P2 = _planes(torch, bj, n, 2, dt)
         assert _inverse_ratio(P2, n, rp, ci, v2.astype(dt), 2, dt) <= 1.0 and np.array_equal(P2[:, :10], P[:, :10]) and np.array_equal(P2[:, 12:], P[:, 12:])
 
@@ -181,21 +132,21 @@ def _check_apply(torch, dt, n, bs, bj, P, label):
     r = np.random.default_rng(41).uniform(-1, 1, n).astype(dt)
     want = M.apply(P, r)
     bound = 100 * PRODUCT_TOL[dt]
-    rd, zd, z2 = _vec(torch, r, n, dt), _vec(torch, None, n, dt), _vec(torch, None, n, dt)
+    rd, zd, z2 = U.vec(torch, r, n, dt), U.vec(torch, None, n, dt), U.vec(torch, None, n, dt)
     parts = torch.full((1024 + 16,), SENTINEL, dtype=torch.float64, device="cuda")
-    bj.apply(rd.data_ptr(), zd.data_ptr(), _stream(torch))
-    bj.apply(rd.data_ptr(), z2.data_ptr(), _stream(torch), d_partials=parts.data_ptr())
+    bj.apply(rd.data_ptr(), zd.data_ptr(), U.stream(torch))
+    bj.apply(rd.data_ptr(), z2.data_ptr(), U.stream(torch), d_partials=parts.data_ptr())
     torch.cuda.synchronize()
-    z = _host(zd, n)
+    z = U.host(zd, n)
     np_ = SS.parts(n, SS.vpl(dt))
     p = parts.cpu().numpy()
     dot = float(np.dot(r.astype(np.float64), want.astype(np.float64)))
-    err, derr = _relerr(z, want.astype(np.float64)), _dist(float(p[:np_].sum()), dot)
+    err, derr = U.relerr(z, want.astype(np.float64)), U.dist(float(p[:np_].sum()), dot)
     print("%s bs %d %s: |z - numpy| / |numpy| = %.3g, r.z from %d partials %.3g (bound %.3g)" % (label, bs, dt, err, np_, derr, bound))
     assert err <= bound and derr <= bound
-    assert np.array_equal(z, _host(z2, n))
-    assert (p[np_:] == SENTINEL).all() and (zd.cpu().numpy()[n:] == SENTINEL).all() and (z2.cpu().numpy()[n:] == SENTINEL).all() and (rd.cpu().numpy()[n:] == SENTINEL).all()
-    assert np.array_equal(_host(rd, n), r)
+    assert np.array_equal(z, U.host(z2, n))
+    U.intact((parts, np_), (zd, n), (z2, n), (rd, n))
+    assert np.array_equal(U.host(rd, n), r)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -203,7 +154,7 @@ def _check_apply(torch, dt, n, bs, bj, P, label):
 def test_apply_equals_numpy(torch_cuda, name, bs, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, b = _system(name, dt)
-    with _updated(torch, n, bs, dt, _device_csr(torch, rp, ci, vt)) as bj:
+    with _updated(torch, n, bs, dt, U.device_csr(torch, rp, ci, vt)) as bj:
         _check_apply(torch, dt, n, bs, bj, _planes(torch, bj, n, bs, dt), name)
 
 
@@ -216,22 +167,22 @@ def test_apply_past_the_partial_sum_cap(torch_cuda, dtype):
     vt = v.astype(dt)
     assert SS.walk(n, SS.vpl(dt)).parts == 1024 and SS.walk(n, SS.vpl(dt)).sweeps == 2
     P, count = M.update(n, rp, ci, vt, 3, dt)
-    csr = _device_csr(torch, rp, ci, vt)
+    csr = U.device_csr(torch, rp, ci, vt)
     with _updated(torch, n, 3, dt, csr) as bj:
         _check_apply(torch, dt, n, 3, bj, P, "tri_capped")
         b = M.rhs(n).astype(dt)
         m = M.CG(M.scipy_csr(n, rp, ci, vt), dt, P)
         m.begin(b); m.iterate(1)
         plan = api.Plan.from_csr(n, n, len(ci), rp, ci, vt, dtype=dt, deterministic=1, placement_tries=1)
-        bd, xd = _vec(torch, b, n, dt), _vec(torch, None, n, dt)
+        bd, xd = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt)
         with api.CG(plan, block=bj) as cg:
-            cg.begin(bd.data_ptr(), xd.data_ptr(), _stream(torch))
-            cg.iterate(xd.data_ptr(), 1, _stream(torch))
-            s = cg.state(_stream(torch))
+            cg.begin(bd.data_ptr(), xd.data_ptr(), U.stream(torch))
+            cg.iterate(xd.data_ptr(), 1, U.stream(torch))
+            s = cg.state(U.stream(torch))
         plan.close()
-        dx, drr = _relerr(_host(xd, n), m.x.astype(np.float64)), _dist(s["rr"], m.rr)
+        dx, drr = U.relerr(U.host(xd, n), m.x.astype(np.float64)), U.dist(s["rr"], m.rr)
         print("tri_capped %s: after 1 iteration |x - mirror| / |mirror| = %.3g, rr %.3g" % (dt, dx, drr))
-        assert s["iterations"] == 1 and max(dx, drr, _dist(s["bb"], m.bb)) <= 100 * PRODUCT_TOL[dt]
+        assert s["iterations"] == 1 and max(dx, drr, U.dist(s["bb"], m.bb)) <= 100 * PRODUCT_TOL[dt]
 
 
 # ---- 4 / 5. the solvers
@@ -239,21 +190,22 @@ def _early(torch, dt, make_solver, mirror, b, n, label):
     """x and rr after 1 and after 3 iterations against the mirror, within 100 x the per-product tolerance (the bound of the solvers' own tests)."""
     mirror.begin(b)
     bound = 100 * PRODUCT_TOL[dt]
-    bd, xd = _vec(torch, b, n, dt), _vec(torch, None, n, dt)
+    bd, xd = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt)
     with make_solver() as sv:
-        sv.begin(bd.data_ptr(), xd.data_ptr(), _stream(torch))
-        s0 = sv.state(_stream(torch))
+        sv.begin(bd.data_ptr(), xd.data_ptr(), U.stream(torch))
+        s0 = sv.state(U.stream(torch))
         assert s0["iterations"] == 0 and s0["status"] == api.CG_RUNNING
-        assert max(_dist(s0["rr"], mirror.rr), _dist(s0["bb"], mirror.bb)) <= bound
+        assert max(U.dist(s0["rr"], mirror.rr), U.dist(s0["bb"], mirror.bb)) <= bound
         done = 0
         for step in (1, 2):
-            sv.iterate(xd.data_ptr(), step, _stream(torch)); mirror.iterate(step); done += step
-            s = sv.state(_stream(torch))
-            dx, drr = _relerr(_host(xd, n), mirror.x.astype(np.float64)), _dist(s["rr"], mirror.rr)
+            sv.iterate(xd.data_ptr(), step, U.stream(torch)); mirror.iterate(step); done += step
+            s = sv.state(U.stream(torch))
+            dx, drr = U.relerr(U.host(xd, n), mirror.x.astype(np.float64)), U.dist(s["rr"], mirror.rr)
             print("%s %s after %d iterations: |x - mirror| / |mirror| = %.3g, rr %.3g (bound %.3g)" % (label, dt, done, dx, drr, bound))
             assert s["iterations"] == done == mirror.iterations and s["status"] == api.CG_RUNNING == mirror.status()
             assert dx <= bound and drr <= bound
-    assert (xd.cpu().numpy()[n:] == SENTINEL).all() and np.array_equal(_host(bd, n), b)
+    U.intact((xd, n))
+    assert np.array_equal(U.host(bd, n), b)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -262,21 +214,21 @@ def test_the_solvers_with_a_block_preconditioner(torch_cuda, name, Solver, dtype
     """Early iterations equal the mirror; solve with maxiter = 2 x the mirror's count: CONVERGED, error against spsolve within 10 x the mirror's; the point-Jacobi solver on the
     same plan at that cap: MAXITER."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     n, rp, ci, vt, b = _system(name, dt)
     xs, itm, errm, P = _solved(name, dt)
     Api, Mirror = getattr(api, Solver), getattr(M, Solver)
-    csr = _device_csr(torch, rp, ci, vt)
-    with _op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, csr) as bj:
+    csr = U.device_csr(torch, rp, ci, vt)
+    with U.square_op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, csr) as bj:
         _early(torch, dt, lambda: Api(op.A, block=bj), Mirror(M.scipy_csr(n, rp, ci, vt), dt, P), b, n, name)
-        bd, xd = _vec(torch, b, n, dt), _vec(torch, None, n, dt)
+        bd, xd = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt)
         with Api(op.A, block=bj) as sv:
             s = sv.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * itm, check_every=8, stream=stream)
-        err = _relerr(_host(xd, n), xs)
+        err = U.relerr(U.host(xd, n), xs)
         print("%s %s: block Jacobi %d iterations (mirror %d), sqrt(rr/bb) %.3g, error vs spsolve %.3g (mirror %.3g)" % (name, dt, s["iterations"], itm, s["relative_residual"], err, errm))
         assert s["status"] == api.CG_CONVERGED and s["relative_residual"] <= M.RTOL[dt] and s["iterations"] <= 2 * itm
         assert err <= 10 * errm
-        dinv = _vec(torch, None, n, dt)
+        dinv = U.vec(torch, None, n, dt)
         api.csr_diagonal_device(n, csr[0].data_ptr(), csr[1].data_ptr(), csr[2].data_ptr(), dinv.data_ptr(), invert=True, stream=stream, dtype=dt)
         xd[:n].zero_()
         with Api(op.A, dinv.data_ptr()) as sv:
@@ -292,9 +244,9 @@ def test_sparse_operator_takes_the_preconditioner(torch_cuda):
         n, rp, ci, vt, b = _system(name, dt)
         xs, itm, errm, P = _solved(name, dt)
         bd = torch.from_numpy(b).cuda()
-        with _op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, _device_csr(torch, rp, ci, vt)) as bj:
+        with U.square_op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, U.device_csr(torch, rp, ci, vt)) as bj:
             x, info = getattr(op, method)(bd, rtol=M.RTOL[dt], maxiter=2 * itm, precond=bj)
-            assert info["converged"] and info["iterations"] <= 2 * itm and _relerr(x.cpu().numpy(), xs) <= 10 * errm
+            assert info["converged"] and info["iterations"] <= 2 * itm and U.relerr(x.cpu().numpy(), xs) <= 10 * errm
             with pytest.raises(ValueError):
                 getattr(op, method)(torch.stack([bd, bd], dim=1).contiguous(), precond=bj)
             with pytest.raises(ValueError):
@@ -307,14 +259,14 @@ def test_value_refresh(torch_cuda, dtype):
     """A plan with a value map and an object updated from lap55-like values on femblk10's pattern; update_values and bj.update from femblk10's values: the inverse has the bytes of
     a fresh object's and the solve the bits of a fresh solver's."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     n, rp, ci, v2, b = _system("femblk10", dt)
     v1 = CM.spd_values(n, rp, ci).astype(dt)
     xs, itm, errm, P = _solved("femblk10", dt)
-    rpd, cid, v1d = _device_csr(torch, rp, ci, v1)
+    rpd, cid, v1d = U.device_csr(torch, rp, ci, v1)
     v2d = torch.from_numpy(v2).cuda()
-    bd, xd = _vec(torch, b, n, dt), _vec(torch, None, n, dt)
-    with _op(n, rp, ci, v1, dt, value_map=True) as op, _updated(torch, n, 3, dt, (rpd, cid, v1d)) as bj:
+    bd, xd = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt)
+    with U.square_op(n, rp, ci, v1, dt, value_map=True) as op, _updated(torch, n, 3, dt, (rpd, cid, v1d)) as bj:
         with api.CG(op.A, block=bj) as cg:
             s1 = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=stream)
             assert s1["status"] == api.CG_CONVERGED
@@ -323,18 +275,18 @@ def test_value_refresh(torch_cuda, dtype):
             bj.update(rpd.data_ptr(), cid.data_ptr(), v2d.data_ptr(), stream)
             xd[:n].zero_()
             s2 = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * itm, stream=stream)
-            x2 = _host(xd, n)
+            x2 = U.host(xd, n)
         P2 = _planes(torch, bj, n, 3, dt)
-    with _op(n, rp, ci, v2, dt, value_map=True) as fresh, _updated(torch, n, 3, dt, (rpd, cid, v2d)) as bjf:
+    with U.square_op(n, rp, ci, v2, dt, value_map=True) as fresh, _updated(torch, n, 3, dt, (rpd, cid, v2d)) as bjf:
         Pf = _planes(torch, bjf, n, 3, dt)
-        xf = _vec(torch, None, n, dt)
+        xf = U.vec(torch, None, n, dt)
         with api.CG(fresh.A, block=bjf) as cg:
             sf = cg.solve(bd.data_ptr(), xf.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * itm, stream=stream)
-    print("%s: refreshed %d iterations, fresh %d; error vs spsolve %.3g" % (dt, s2["iterations"], sf["iterations"], _relerr(x2, xs)))
+    print("%s: refreshed %d iterations, fresh %d; error vs spsolve %.3g" % (dt, s2["iterations"], sf["iterations"], U.relerr(x2, xs)))
     assert not np.array_equal(P1, P2) and P2.tobytes() == Pf.tobytes()
     assert s2["status"] == api.CG_CONVERGED and sf["status"] == api.CG_CONVERGED
-    assert s2["iterations"] == sf["iterations"] and s2["rr"] == sf["rr"] and np.array_equal(x2, _host(xf, n))
-    assert _relerr(x2, xs) <= 10 * errm
+    assert s2["iterations"] == sf["iterations"] and s2["rr"] == sf["rr"] and np.array_equal(x2, U.host(xf, n))
+    assert U.relerr(x2, xs) <= 10 * errm
 
 
 # ---- 7. fixed order
@@ -343,16 +295,16 @@ def test_update_and_the_sums_have_a_fixed_order(torch_cuda, dtype):
     """Two runs of update + 10 CG iterations on separately created objects and operators: bit-identical M^-1, x and rr."""
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, b = _system("femblk10", dt)
-    bd = _vec(torch, b, n, dt)
+    bd = U.vec(torch, b, n, dt)
     results = []
     for _ in range(2):
-        with _op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, _device_csr(torch, rp, ci, vt)) as bj:
-            xd = _vec(torch, None, n, dt)
+        with U.square_op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, U.device_csr(torch, rp, ci, vt)) as bj:
+            xd = U.vec(torch, None, n, dt)
             with api.CG(op.A, block=bj) as cg:
-                cg.begin(bd.data_ptr(), xd.data_ptr(), _stream(torch))
-                cg.iterate(xd.data_ptr(), 10, _stream(torch))
-                s = cg.state(_stream(torch))
-            results.append((_planes(torch, bj, n, 3, dt), _host(xd, n), s))
+                cg.begin(bd.data_ptr(), xd.data_ptr(), U.stream(torch))
+                cg.iterate(xd.data_ptr(), 10, U.stream(torch))
+                s = cg.state(U.stream(torch))
+            results.append((_planes(torch, bj, n, 3, dt), U.host(xd, n), s))
     (Pa, xa, sa), (Pb, xb, sb) = results
     assert sa["iterations"] == 10 and sa["status"] == api.CG_RUNNING and xa.any()
     assert Pa.tobytes() == Pb.tobytes() and np.array_equal(xa, xb) and sa["rr"] == sb["rr"]
@@ -366,10 +318,10 @@ def test_update_begin_and_iterate_are_capturable_into_a_hip_graph(torch_cuda, dt
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, b = _system("femblk10", dt)
     x0 = (0.01 * M.rhs(n)[::-1]).astype(dt)
-    rpd, cid, vd = _device_csr(torch, rp, ci, vt)
+    rpd, cid, vd = U.device_csr(torch, rp, ci, vt)
     other = torch.from_numpy(CM.spd_values(n, rp, ci).astype(dt)).cuda()
-    with _op(n, rp, ci, vt, dt) as op, api.BlockJacobi(n, 3, dt) as bj:
-        bd, xd = _vec(torch, b, n, dt), _vec(torch, x0, n, dt)
+    with U.square_op(n, rp, ci, vt, dt) as op, api.BlockJacobi(n, 3, dt) as bj:
+        bd, xd = U.vec(torch, b, n, dt), U.vec(torch, x0, n, dt)
         cg = api.CG(op.A, block=bj)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -383,21 +335,21 @@ def test_update_begin_and_iterate_are_capturable_into_a_hip_graph(torch_cuda, dt
         with torch.cuda.stream(side):
             st = side.cuda_stream
             chain(st)                                             # (uncaptured: the comparison, and the warm-up)
-            s5 = cg.state(st); x5 = _host(xd, n)
+            s5 = cg.state(st); x5 = U.host(xd, n)
             xd[:n].copy_(torch.from_numpy(x0))
             side.synchronize()
             with torch.cuda.graph(graph, stream=side):
                 chain(st)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        assert np.array_equal(_host(xd, n), x0)                   # (captured, not run)
+        assert np.array_equal(U.host(xd, n), x0)                   # (captured, not run)
         for _ in range(2):
             xd[:n].copy_(torch.from_numpy(x0))
-            bj.update(rpd.data_ptr(), cid.data_ptr(), other.data_ptr(), _stream(torch))
+            bj.update(rpd.data_ptr(), cid.data_ptr(), other.data_ptr(), U.stream(torch))
             torch.cuda.synchronize()
             graph.replay(); torch.cuda.synchronize()
-            s = cg.state(_stream(torch))
-            assert np.array_equal(_host(xd, n), x5) and not np.array_equal(x5, x0)
+            s = cg.state(U.stream(torch))
+            assert np.array_equal(U.host(xd, n), x5) and not np.array_equal(x5, x0)
             assert s["iterations"] == 5 and s["rr"] == s5["rr"] and s["status"] == api.CG_RUNNING
         del graph
         cg.close()
@@ -415,20 +367,20 @@ def test_refusals(torch_cuda, dtype):
         assert lib.tilespmv_block_jacobi_create(C.byref(h), n, bs) == api.HIP_ERROR_INVALID_VALUE and not h
         with pytest.raises(ValueError):
             api.BlockJacobi(n, bs, dt)
-    csr = _device_csr(torch, rp, ci, vt)
-    with _op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, csr) as bj, api.BlockJacobi(n + 1, 3, dt) as longer:
+    csr = U.device_csr(torch, rp, ci, vt)
+    with U.square_op(n, rp, ci, vt, dt) as op, _updated(torch, n, 3, dt, csr) as bj, api.BlockJacobi(n + 1, 3, dt) as longer:
         for create, Api in ((lib.tilespmv_cg_create_block, api.CG), (lib.tilespmv_bicgstab_create_block, api.BiCGStab)):
             h = C.c_void_p(1)
             assert create(C.byref(h), op.A.h, longer.h) == api.HIP_ERROR_INVALID_VALUE and not h
             with pytest.raises(ValueError):
                 Api(op.A, block=longer)
-            dinv = _vec(torch, np.ones(n), n, dt)
+            dinv = U.vec(torch, np.ones(n), n, dt)
             with pytest.raises(ValueError):
                 Api(op.A, dinv.data_ptr(), block=bj)
             with Api(op.A, block=bj) as sv:
                 assert sv.h
-        rd, zd = _vec(torch, np.ones(n + 1), n + 1, dt), _vec(torch, None, n + 1, dt)
-        st = _stream(torch)
+        rd, zd = U.vec(torch, np.ones(n + 1), n + 1, dt), U.vec(torch, None, n + 1, dt)
+        st = U.stream(torch)
         item = dt.itemsize
         for r_, z_ in ((rd.data_ptr() + item, zd.data_ptr()), (rd.data_ptr(), zd.data_ptr() + item), (rd.data_ptr(), rd.data_ptr()), (0, zd.data_ptr()), (rd.data_ptr(), 0)):
             assert lib.tilespmv_block_jacobi_apply(bj.h, C.c_void_p(r_), C.c_void_p(z_), C.c_void_p(st)) == api.HIP_ERROR_INVALID_VALUE
@@ -436,7 +388,7 @@ def test_refusals(torch_cuda, dtype):
                 bj.apply(r_, z_, st)
         assert lib.tilespmv_block_jacobi_apply_dot(bj.h, C.c_void_p(rd.data_ptr()), C.c_void_p(zd.data_ptr()), None, C.c_void_p(st)) == api.HIP_ERROR_INVALID_VALUE
         torch.cuda.synchronize()
-        assert not _host(zd, n + 1).any()                         # (nothing was launched)
+        assert not U.host(zd, n + 1).any()                         # (nothing was launched)
         bj.apply(rd.data_ptr(), zd.data_ptr(), st)                # (aligned and distinct: accepted)
         torch.cuda.synchronize()
-        assert _host(zd, n).any()
+        assert U.host(zd, n).any()

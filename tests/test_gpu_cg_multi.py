@@ -8,61 +8,11 @@ import pytest
 
 import cg_mirror as M
 import cg_multi_cases as MC
+import gpu_solver_util as U
+from gpu_solver_util import DTYPES, PRODUCT_TOL, torch_cuda  # noqa: F401
 from tilespmv_amd import _lib, api, generators as G
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [np.float64, np.float32]
-PRODUCT_TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.float32): 1e-5}   # README: the project's per-product tolerance on real-valued data
-SENTINEL = 777.0
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _plan(n, rp, ci, v, dtype, **kw):
-    kw.setdefault("deterministic", 1)
-    kw.setdefault("placement_tries", 1)
-    return api.Plan.from_csr(n, n, len(ci), rp, ci, np.ascontiguousarray(v, dtype=dtype), dtype=dtype, **kw)
-
-
-def _tdt(torch, dtype):
-    return torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
-
-
-def _mat(torch, a, n, nvec, dtype):
-    """A device array of (n, nvec) elements, row-major, with 16 sentinel rows behind it."""
-    t = torch.full((n + 16, nvec), SENTINEL, dtype=_tdt(torch, dtype), device="cuda")
-    if a is None:
-        t[:n].zero_()
-    else:
-        t[:n].copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).reshape(n, nvec)))
-    return t
-
-
-def _vec(torch, a, n, dtype):
-    t = torch.full((n + 16,), SENTINEL, dtype=_tdt(torch, dtype), device="cuda")
-    if a is None:
-        t[:n].zero_()
-    else:
-        t[:n].copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)))
-    return t
-
-
-def _host(t, n):
-    return t.cpu().numpy()[:n].copy()
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _relerr(x, xs):
-    return float(np.linalg.norm(x.astype(np.float64) - xs) / np.linalg.norm(xs))
 
 
 def _xs(n, rp, ci, vt, b):
@@ -82,7 +32,7 @@ def _check_columns(label, dt, n, rp, ci, vt, B, X, states, mirrors):
             assert s["status"] == api.CG_CONVERGED and s["iterations"] == 0 and s["rr"] == 0.0 and not X[:, j].any(), (label, j, s)
             continue
         xs = _xs(n, rp, ci, vt, B[:, j])
-        err, errm = _relerr(X[:, j], xs), _relerr(xm, xs)
+        err, errm = U.relerr(X[:, j], xs), U.relerr(xm, xs)
         print("%s %s column %d: GPU %d iterations (mirror %d), sqrt(rr/bb) %.3g, error vs spsolve %.3g (mirror %.3g)" % (label, dt, j, s["iterations"], itm, s["relative_residual"], err, errm))
         assert s["status"] == api.CG_CONVERGED and s["relative_residual"] <= M.RTOL[dt] and s["iterations"] <= 2 * itm, (label, j, s, itm)
         assert err <= 10 * errm, (label, j, err, errm)
@@ -100,12 +50,12 @@ def test_early_iterations_equal_the_mirror_per_column(torch_cuda, nvec, dtype):
     mirrors = [M.Mirror(A, dt) for _ in range(nvec)]
     for j, m in enumerate(mirrors):
         m.begin(B[:, j])
-    plan = _plan(n, rp, ci, vt, dt)
-    bd, xd = _mat(torch, B, n, nvec, dt), _mat(torch, None, n, nvec, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt)
+    bd, xd = U.vec(torch, B, n, dt, nvec), U.vec(torch, None, n, dt, nvec)
     tol = 100 * PRODUCT_TOL[dt]
     with api.CGMulti(plan, nvec) as cg:
-        cg.begin(bd.data_ptr(), xd.data_ptr(), _stream(torch))
-        s0 = cg.state(_stream(torch))
+        cg.begin(bd.data_ptr(), xd.data_ptr(), U.stream(torch))
+        s0 = cg.state(U.stream(torch))
         assert len(s0) == nvec
         for j, m in enumerate(mirrors):
             assert s0[j]["iterations"] == 0
@@ -115,9 +65,9 @@ def test_early_iterations_equal_the_mirror_per_column(torch_cuda, nvec, dtype):
                 assert s0[j]["bb"] == 0.0 and s0[j]["rr"] == 0.0
         done = 0
         for step in (1, 2):
-            cg.iterate(xd.data_ptr(), step, _stream(torch)); done += step
-            s = cg.state(_stream(torch))
-            X = _host(xd, n)
+            cg.iterate(xd.data_ptr(), step, U.stream(torch)); done += step
+            s = cg.state(U.stream(torch))
+            X = U.host(xd, n)
             for j, m in enumerate(mirrors):
                 m.iterate(step)
                 assert s[j]["iterations"] == done
@@ -131,7 +81,7 @@ def test_early_iterations_equal_the_mirror_per_column(torch_cuda, nvec, dtype):
                     drr = abs(s[j]["rr"] - m.rr) / m.rr
                     print("%s nvec %d column %d after %d iterations: |x - mirror| / |mirror| = %.3g, |rr - mirror| / mirror = %.3g (bound %.3g)" % (dt, nvec, j, done, dx, drr, tol))
                     assert s[j]["status"] == api.CG_RUNNING and dx <= tol and drr <= tol, (j, done, dx, drr)
-    assert (bd.cpu().numpy()[n:] == SENTINEL).all() and (xd.cpu().numpy()[n:] == SENTINEL).all()
+    U.intact((bd, n), (xd, n))
     plan.close()
 
 
@@ -146,11 +96,11 @@ def test_solves(torch_cuda, name, kw, nvec, dtype):
     # nvec 2: columns 0 and 1; nvec 4: 0-3 (with the zero column); nvec 8: all
     B = np.ascontiguousarray(B8[:, :nvec])
     mirrors = _mirror_solves(M.scipy_csr(n, rp, ci, vt), dt, B, range(nvec))
-    plan = _plan(n, rp, ci, vt, dt, **kw)
-    bd, xd = _mat(torch, B, n, nvec, dt), _mat(torch, None, n, nvec, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt, **kw)
+    bd, xd = U.vec(torch, B, n, dt, nvec), U.vec(torch, None, n, dt, nvec)
     with api.CGMulti(plan, nvec) as cg:
-        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * max(m[1] for m in mirrors), check_every=1, stream=_stream(torch))
-    _check_columns("%s nvec %d" % (name, nvec), dt, n, rp, ci, vt, B, _host(xd, n), states, mirrors)
+        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * max(m[1] for m in mirrors), check_every=1, stream=U.stream(torch))
+    _check_columns("%s nvec %d" % (name, nvec), dt, n, rp, ci, vt, B, U.host(xd, n), states, mirrors)
     plan.close()
 
 
@@ -160,11 +110,11 @@ def test_solve_on_the_default_plan(torch_cuda, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, B = MC.system("lap128", dt)
     mirrors = _mirror_solves(M.scipy_csr(n, rp, ci, vt), dt, B, range(8))
-    plan = _plan(n, rp, ci, vt, dt, deterministic=-1, placement_tries=-1)
-    bd, xd = _mat(torch, B, n, 8, dt), _mat(torch, None, n, 8, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt, deterministic=-1, placement_tries=-1)
+    bd, xd = U.vec(torch, B, n, dt, 8), U.vec(torch, None, n, dt, 8)
     with api.CGMulti(plan, 8) as cg:
-        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * max(m[1] for m in mirrors), check_every=8, stream=_stream(torch))
-    _check_columns("lap128 default plan", dt, n, rp, ci, vt, B, _host(xd, n), states, mirrors)
+        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * max(m[1] for m in mirrors), check_every=8, stream=U.stream(torch))
+    _check_columns("lap128 default plan", dt, n, rp, ci, vt, B, U.host(xd, n), states, mirrors)
     plan.close()
 
 
@@ -176,21 +126,21 @@ def test_jacobi(torch_cuda, dtype):
     n, rp, ci, vt, B8 = MC.system("lap128_scaled", dt)
     B = np.ascontiguousarray(B8[:, :4])
     A = M.scipy_csr(n, rp, ci, vt)
-    rpd, cid, vd = torch.from_numpy(rp).cuda(), torch.from_numpy(ci).cuda(), torch.from_numpy(vt).cuda()
-    dinv = _vec(torch, None, n, dt)
-    api.csr_diagonal_device(n, rpd.data_ptr(), cid.data_ptr(), vd.data_ptr(), dinv.data_ptr(), invert=True, stream=_stream(torch), dtype=dt)
+    rpd, cid, vd = U.device_csr(torch, rp, ci, vt)
+    dinv = U.vec(torch, None, n, dt)
+    api.csr_diagonal_device(n, rpd.data_ptr(), cid.data_ptr(), vd.data_ptr(), dinv.data_ptr(), invert=True, stream=U.stream(torch), dtype=dt)
     torch.cuda.synchronize()
-    mirrors = _mirror_solves(A, dt, B, range(4), _host(dinv, n))
+    mirrors = _mirror_solves(A, dt, B, range(4), U.host(dinv, n))
     cap = 2 * max(m[1] for m in mirrors)
-    plan = _plan(n, rp, ci, vt, dt)
-    bd, xd = _mat(torch, B, n, 4, dt), _mat(torch, None, n, 4, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt)
+    bd, xd = U.vec(torch, B, n, dt, 4), U.vec(torch, None, n, dt, 4)
     with api.CGMulti(plan, 4, dinv.data_ptr()) as cg:
-        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=cap, stream=_stream(torch))
-    _check_columns("lap128_scaled Jacobi", dt, n, rp, ci, vt, B, _host(xd, n), states, mirrors)
-    assert (dinv.cpu().numpy()[n:] == SENTINEL).all()
+        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=cap, stream=U.stream(torch))
+    _check_columns("lap128_scaled Jacobi", dt, n, rp, ci, vt, B, U.host(xd, n), states, mirrors)
+    U.intact((dinv, n))
     xd[:n].zero_()
     with api.CGMulti(plan, 4) as cg:
-        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=cap, stream=_stream(torch))
+        states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=cap, stream=U.stream(torch))
     for j, s in enumerate(states):
         print("%s: plain CG, column %d: %d iterations, status %s, sqrt(rr/bb) %.3g" % (dt, j, s["iterations"], s["status_name"], s["relative_residual"]))
         if j == 2:
@@ -206,23 +156,23 @@ def test_converged_columns_are_frozen(torch_cuda, dtype):
     while the others run on: a second solve that ends at column 1's count returns the same x[:, 1]."""
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, B = MC.system("lap128", dt)
-    plan = _plan(n, rp, ci, vt, dt)
-    bd, xd = _mat(torch, B, n, 8, dt), _mat(torch, None, n, 8, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt)
+    bd, xd = U.vec(torch, B, n, dt, 8), U.vec(torch, None, n, dt, 8)
     with api.CGMulti(plan, 8) as cg:
-        s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2000, check_every=8, stream=_stream(torch))
-        X = _host(xd, n)
+        s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2000, check_every=8, stream=U.stream(torch))
+        X = U.host(xd, n)
         its = [c["iterations"] for c in s]
         print(dt, "iterations per column:", its)
         assert all(c["status"] == api.CG_CONVERGED and c["relative_residual"] <= M.RTOL[dt] for c in s)
         assert all(i % 8 == 0 for i in its) and its[2] == 0 and 0 < its[1] < its[0]
         # the device's own scalars after the solve agree with what solve returned: frozen columns kept their count and their rr
-        after = cg.state(_stream(torch))
+        after = cg.state(U.stream(torch))
         for j in range(8):
             if j != 2:
                 assert after[j]["iterations"] == its[j] and after[j]["rr"] == s[j]["rr"], (j, after[j], s[j])
         xd[:n].zero_()
-        s2 = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=its[1], check_every=8, stream=_stream(torch))
-        X2 = _host(xd, n)
+        s2 = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=its[1], check_every=8, stream=U.stream(torch))
+        X2 = U.host(xd, n)
         assert s2[1]["status"] == api.CG_CONVERGED and s2[1]["iterations"] == its[1] and s2[1]["rr"] == s[1]["rr"]
         assert s2[0]["status"] == api.CG_MAXITER and s2[0]["iterations"] == its[1]
         assert np.array_equal(X2[:, 1], X[:, 1])
@@ -236,32 +186,32 @@ def test_sums_have_a_fixed_order_and_columns_are_independent(torch_cuda, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, B = MC.system("lap128", dt)
     B = np.ascontiguousarray(B[:, :4])
-    plan, plan2 = _plan(n, rp, ci, vt, dt), _plan(n, rp, ci, vt, dt)
-    bd = _mat(torch, B, n, 4, dt)
+    plan, plan2 = U.square_plan(n, rp, ci, vt, dt), U.square_plan(n, rp, ci, vt, dt)
+    bd = U.vec(torch, B, n, dt, 4)
     ys = []
     for p in (plan, plan, plan2):
-        yd = _mat(torch, None, n, 4, dt)
-        p.spmm(bd.data_ptr(), yd.data_ptr(), 4, _stream(torch))
+        yd = U.vec(torch, None, n, dt, 4)
+        p.spmm(bd.data_ptr(), yd.data_ptr(), 4, U.stream(torch))
         torch.cuda.synchronize()
-        ys.append(_host(yd, n))
+        ys.append(U.host(yd, n))
     assert np.array_equal(ys[0], ys[1]) and np.array_equal(ys[0], ys[2]), "the precondition: Plan.spmm is bit-reproducible on this plan"
     results = []
     for p in (plan, plan, plan2):
-        xd = _mat(torch, None, n, 4, dt)
+        xd = U.vec(torch, None, n, dt, 4)
         with api.CGMulti(p, 4) as cg:
-            s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2000, stream=_stream(torch))
+            s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2000, stream=U.stream(torch))
         assert all(c["status"] == api.CG_CONVERGED for c in s)
-        results.append((_host(xd, n), [c["iterations"] for c in s], [c["rr"] for c in s]))
+        results.append((U.host(xd, n), [c["iterations"] for c in s], [c["rr"] for c in s]))
     for X, it, rr in results[1:]:
         assert np.array_equal(X, results[0][0]) and it == results[0][1] and rr == results[0][2]
     # other neighbours: a breakdown-free but very different batch (scaled, permuted, a zero column)
     B2 = B.copy()
     B2[:, 1] = 1e6 * B[::-1, 3]; B2[:, 2] = B[:, 1]; B2[:, 3] = 0
-    b2d, xd = _mat(torch, B2, n, 4, dt), _mat(torch, None, n, 4, dt)
+    b2d, xd = U.vec(torch, B2, n, dt, 4), U.vec(torch, None, n, dt, 4)
     with api.CGMulti(plan, 4) as cg:
-        s = cg.solve(b2d.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2000, stream=_stream(torch))
+        s = cg.solve(b2d.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2000, stream=U.stream(torch))
     assert s[0]["iterations"] == results[0][1][0] and s[0]["rr"] == results[0][2][0]
-    assert np.array_equal(_host(xd, n)[:, 0], results[0][0][:, 0])
+    assert np.array_equal(U.host(xd, n)[:, 0], results[0][0][:, 0])
     plan.close(); plan2.close()
 
 
@@ -270,22 +220,22 @@ def test_nvec_1_is_the_single_solver(torch_cuda, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, B = MC.system("fem12", dt)
     b = np.ascontiguousarray(B[:, 0])
-    plan = _plan(n, rp, ci, vt, dt)
-    bd, x1, xm = _vec(torch, b, n, dt), _vec(torch, None, n, dt), _vec(torch, None, n, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt)
+    bd, x1, xm = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt), U.vec(torch, None, n, dt)
     with api.CG(plan) as cg:
-        s1 = cg.solve(bd.data_ptr(), x1.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=_stream(torch))
+        s1 = cg.solve(bd.data_ptr(), x1.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=U.stream(torch))
     with api.CGMulti(plan, 1) as cg:
-        sm = cg.solve(bd.data_ptr(), xm.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=_stream(torch))
+        sm = cg.solve(bd.data_ptr(), xm.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=U.stream(torch))
         assert len(sm) == 1 and sm[0] == s1 and s1["status"] == api.CG_CONVERGED
-        assert np.array_equal(_host(xm, n), _host(x1, n))
+        assert np.array_equal(U.host(xm, n), U.host(x1, n))
         xm[:n].zero_()
-        cg.begin(bd.data_ptr(), xm.data_ptr(), _stream(torch)); cg.iterate(xm.data_ptr(), 5, _stream(torch))
-        st5 = cg.state(_stream(torch))
+        cg.begin(bd.data_ptr(), xm.data_ptr(), U.stream(torch)); cg.iterate(xm.data_ptr(), 5, U.stream(torch))
+        st5 = cg.state(U.stream(torch))
     x1[:n].zero_()
     with api.CG(plan) as cg:
-        cg.begin(bd.data_ptr(), x1.data_ptr(), _stream(torch)); cg.iterate(x1.data_ptr(), 5, _stream(torch))
-        assert [cg.state(_stream(torch))] == st5
-    assert np.array_equal(_host(xm, n), _host(x1, n))
+        cg.begin(bd.data_ptr(), x1.data_ptr(), U.stream(torch)); cg.iterate(x1.data_ptr(), 5, U.stream(torch))
+        assert [cg.state(U.stream(torch))] == st5
+    assert np.array_equal(U.host(xm, n), U.host(x1, n))
     plan.close()
 
 
@@ -297,8 +247,8 @@ def test_iterate_is_capturable_into_a_hip_graph(torch_cuda, kw, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     n, rp, ci, vt, B = MC.system("lap128", dt)
     B = np.ascontiguousarray(B[:, :4])
-    plan = _plan(n, rp, ci, vt, dt, **kw)
-    bd, xd = _mat(torch, B, n, 4, dt), _mat(torch, None, n, 4, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt, **kw)
+    bd, xd = U.vec(torch, B, n, dt, 4), U.vec(torch, None, n, dt, 4)
     cg = api.CGMulti(plan, 4)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -307,9 +257,9 @@ def test_iterate_is_capturable_into_a_hip_graph(torch_cuda, kw, dtype):
         st = side.cuda_stream
         cg.begin(bd.data_ptr(), xd.data_ptr(), st)
         cg.iterate(xd.data_ptr(), 8, st)                      # (uncaptured: the comparison, and the warm-up)
-        s8 = cg.state(st); x8 = _host(xd, n)
+        s8 = cg.state(st); x8 = U.host(xd, n)
         cg.iterate(xd.data_ptr(), 8, st)
-        s16 = cg.state(st); x16 = _host(xd, n)
+        s16 = cg.state(st); x16 = U.host(xd, n)
         xd[:n].zero_()
         cg.begin(bd.data_ptr(), xd.data_ptr(), st)
         side.synchronize()
@@ -317,11 +267,11 @@ def test_iterate_is_capturable_into_a_hip_graph(torch_cuda, kw, dtype):
             cg.iterate(xd.data_ptr(), 8, st)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
-    assert not _host(xd, n).any()                             # (captured, not run)
+    assert not U.host(xd, n).any()                             # (captured, not run)
     for want_x, want_s in ((x8, s8), (x16, s16)):
         graph.replay(); torch.cuda.synchronize()
-        s = cg.state(_stream(torch))
-        assert np.array_equal(_host(xd, n), want_x)
+        s = cg.state(U.stream(torch))
+        assert np.array_equal(U.host(xd, n), want_x)
         assert s == want_s and s[0]["status"] == api.CG_RUNNING and s[0]["iterations"] == want_s[0]["iterations"]
     del graph
     cg.close(); plan.close()
@@ -333,40 +283,40 @@ def test_guards_per_column(torch_cuda, dtype):
     column stays at 0; solve zeroes the x of a zero column whatever the start vector was.  A = -(the Laplacian): p.Ap < 0 in every column in the first iteration — BREAKDOWN at
     the first check, x untouched."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     n = 4096
     rp, ci, v = np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), np.full(n, 2.0, dtype=dt)
     B = MC.columns(n, M.scipy_csr(n, rp, ci, v.astype(np.float64)))[:, [0, 2, 3, 7]].astype(dt)      # (column 1 of the batch is zero)
     B = np.ascontiguousarray(B)
-    plan = _plan(n, rp, ci, v, dt)
-    bd, xd = _mat(torch, B, n, 4, dt), _mat(torch, None, n, 4, dt)
+    plan = U.square_plan(n, rp, ci, v, dt)
+    bd, xd = U.vec(torch, B, n, dt, 4), U.vec(torch, None, n, dt, 4)
     with api.CGMulti(plan, 4) as cg:
         cg.begin(bd.data_ptr(), xd.data_ptr(), stream)
         cg.iterate(xd.data_ptr(), 1, stream)
         s = cg.state(stream)
-        X1 = _host(xd, n)
+        X1 = U.host(xd, n)
         assert all(c["rr"] == 0.0 and c["iterations"] == 1 for c in s) and np.array_equal(X1, B / dt.type(2))
         cg.iterate(xd.data_ptr(), 16, stream)
         s = cg.state(stream)
-        assert all(c["rr"] == 0.0 and c["iterations"] == 17 and c["status"] == api.CG_CONVERGED for c in s) and np.array_equal(_host(xd, n), X1)
+        assert all(c["rr"] == 0.0 and c["iterations"] == 17 and c["status"] == api.CG_CONVERGED for c in s) and np.array_equal(U.host(xd, n), X1)
         x0 = np.ascontiguousarray(np.tile(M.rhs(n)[:, None], (1, 4)).astype(dt))
         xd[:n].copy_(torch.from_numpy(x0))
         s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=100, check_every=8, stream=stream)
-        X = _host(xd, n)
+        X = U.host(xd, n)
         assert s[1]["status"] == api.CG_CONVERGED and s[1]["iterations"] == 0 and s[1]["rr"] == 0.0 and not X[:, 1].any()
         for j in (0, 2, 3):
             assert s[j]["status"] == api.CG_CONVERGED and s[j]["iterations"] == 8 and s[j]["relative_residual"] <= M.RTOL[dt], (j, s[j])
-            assert _relerr(X[:, j], B[:, j].astype(np.float64) / 2) <= 100 * PRODUCT_TOL[dt]
+            assert U.relerr(X[:, j], B[:, j].astype(np.float64) / 2) <= 100 * PRODUCT_TOL[dt]
     plan.close()
     n, rp, ci, vt, B8 = MC.system("lap128", dt)
     B = np.ascontiguousarray(B8[:, [0, 3, 5, 7]])
     x0 = np.ascontiguousarray(np.stack([M.rhs(n)[::-1], M.rhs(n), 2 * M.rhs(n)[::-1], np.ones(n)], axis=1).astype(dt))
-    neg = _plan(n, rp, ci, -vt, dt)
-    bd, xd = _mat(torch, B, n, 4, dt), _mat(torch, x0, n, 4, dt)
+    neg = U.square_plan(n, rp, ci, -vt, dt)
+    bd, xd = U.vec(torch, B, n, dt, 4), U.vec(torch, x0, n, dt, 4)
     with api.CGMulti(neg, 4) as cg:
         s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=100, check_every=8, stream=stream)
         assert all(c["status"] == api.CG_BREAKDOWN and c["iterations"] == 8 for c in s), s      # (the first check)
-        assert np.array_equal(_host(xd, n), x0)
+        assert np.array_equal(U.host(xd, n), x0)
     neg.close()
 
 
@@ -377,7 +327,7 @@ def test_nothing_is_touched_past_the_end(torch_cuda, nvec, jacobi, dtype):
     """B, X (and dinv) with 16 sentinel rows behind them, on fem12 and on tri_mesh(53, 39) (2067 rows: in fp32 with nvec 2 the flat arrays end in half a 16-byte vector): the
     sentinels survive a solve, B is unchanged, and the odd-sized solve is within 100 x rtol of the direct solution."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     for label, (m, n, rp, ci) in (("fem12", G.fem_hex(12, 12, 12, 3)), ("tri53x39", G.tri_mesh(53, 39))):
         assert m == n and (label == "fem12" or n == 2067)
         rp, ci = np.ascontiguousarray(rp, dtype=np.int32), np.ascontiguousarray(ci, dtype=np.int32)
@@ -386,28 +336,27 @@ def test_nothing_is_touched_past_the_end(torch_cuda, nvec, jacobi, dtype):
         B = np.ascontiguousarray(MC.columns(n, M.scipy_csr(n, rp, ci, v))[:, :nvec].astype(dt))
         A = M.scipy_csr(n, rp, ci, vt)
         dinv = (dt.type(1) / A.diagonal().astype(dt)).astype(dt) if jacobi else None
-        plan = _plan(n, rp, ci, vt, dt)
-        bd, xd = _mat(torch, B, n, nvec, dt), _mat(torch, None, n, nvec, dt)
-        dd = _vec(torch, dinv, n, dt) if jacobi else None
+        plan = U.square_plan(n, rp, ci, vt, dt)
+        bd, xd = U.vec(torch, B, n, dt, nvec), U.vec(torch, None, n, dt, nvec)
+        dd = U.vec(torch, dinv, n, dt) if jacobi else None
         m3 = M.Mirror(A, dt, dinv); m3.begin(B[:, 0]); m3.iterate(3)
         with api.CGMulti(plan, nvec, dd.data_ptr() if jacobi else None) as cg:
             cg.begin(bd.data_ptr(), xd.data_ptr(), stream)
             cg.iterate(xd.data_ptr(), 3, stream)
             s = cg.state(stream)
-            x3 = _host(xd, n)[:, 0]
+            x3 = U.host(xd, n)[:, 0]
             dx = float(np.linalg.norm(x3.astype(np.float64) - m3.x.astype(np.float64)) / np.linalg.norm(m3.x.astype(np.float64)))
             print("%s %s nvec %d jacobi=%s: 3 iterations, column 0 |x - mirror| / |mirror| = %.3g, rr %.6g (mirror %.6g)" % (label, dt, nvec, jacobi, dx, s[0]["rr"], m3.rr))
             assert dx <= 100 * PRODUCT_TOL[dt] and abs(s[0]["rr"] - m3.rr) <= 100 * PRODUCT_TOL[dt] * m3.rr
             xd[:n].zero_()
             s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=stream)
-        X = _host(xd, n)
+        X = U.host(xd, n)
         for j in range(nvec):
             assert s[j]["status"] == api.CG_CONVERGED, (label, j, s[j])
             if B[:, j].any():
-                assert _relerr(X[:, j], _xs(n, rp, ci, vt, B[:, j])) <= 100 * M.RTOL[dt], (label, j)      # (degree + 1 on the diagonal: condition number below 50)
-        for t in (bd, xd) + ((dd,) if jacobi else ()):
-            assert (t.cpu().numpy()[n:] == SENTINEL).all(), label
-        assert np.array_equal(_host(bd, n), B)
+                assert U.relerr(X[:, j], _xs(n, rp, ci, vt, B[:, j])) <= 100 * M.RTOL[dt], (label, j)      # (degree + 1 on the diagonal: condition number below 50)
+        U.intact((bd, n), (xd, n), *(((dd, n),) if jacobi else ()))
+        assert np.array_equal(U.host(bd, n), B)
         plan.close()
 
 
@@ -417,7 +366,7 @@ def test_refusals(torch_cuda, dtype):
     torch, dt = torch_cuda, np.dtype(dtype)
     lib = _lib.load(dt)
     n, rp, ci, vt, B = MC.system("lap128", dt)
-    shard = _plan(n, rp, ci, vt, dt, tilerow_end=(n // 16) // 2)
+    shard = U.square_plan(n, rp, ci, vt, dt, tilerow_end=(n // 16) // 2)
     m, nc, brp, bci = G.band(2048, 40, ncols=4096)
     wide = api.Plan.from_csr(m, nc, len(bci), brp, bci, G.real_values(len(bci), dt), dtype=dt, deterministic=1, placement_tries=1)
     for plan in (shard, wide):
@@ -427,23 +376,23 @@ def test_refusals(torch_cuda, dtype):
             with pytest.raises(ValueError):
                 api.CGMulti(plan, nvec)
         plan.close()
-    plan = _plan(n, rp, ci, vt, dt)
+    plan = U.square_plan(n, rp, ci, vt, dt)
     for nvec in (0, 3, 16):
         with pytest.raises(ValueError):
             api.CGMulti(plan, nvec)
-    bd, xd, dd = _mat(torch, B[:, :2], n, 2, dt), _mat(torch, None, n, 2, dt), _vec(torch, np.ones(n), n, dt)
+    bd, xd, dd = U.vec(torch, B[:, :2], n, dt, 2), U.vec(torch, None, n, dt, 2), U.vec(torch, np.ones(n), n, dt)
     off = dt.itemsize
     with pytest.raises(ValueError):
         api.CGMulti(plan, 2, dd.data_ptr() + off)
     with api.CGMulti(plan, 2) as cg:
         with pytest.raises(ValueError):
-            cg.begin(bd.data_ptr() + off, xd.data_ptr(), _stream(torch))
+            cg.begin(bd.data_ptr() + off, xd.data_ptr(), U.stream(torch))
         with pytest.raises(ValueError):
-            cg.begin(bd.data_ptr(), xd.data_ptr() + off, _stream(torch))
+            cg.begin(bd.data_ptr(), xd.data_ptr() + off, U.stream(torch))
         with pytest.raises(ValueError):
-            cg.iterate(xd.data_ptr() + off, 1, _stream(torch))
+            cg.iterate(xd.data_ptr() + off, 1, U.stream(torch))
         with pytest.raises(ValueError):
-            cg.solve(bd.data_ptr(), xd.data_ptr() + off, stream=_stream(torch))
+            cg.solve(bd.data_ptr(), xd.data_ptr() + off, stream=U.stream(torch))
     plan.close()
 
 
@@ -465,10 +414,10 @@ def test_sparse_operator_cg_with_a_matrix_of_right_hand_sides(torch_cuda, dtype)
             for g, w, nvec in SparseOperator.cg_groups(k):
                 Bg = np.zeros((n, nvec), dtype=dt)
                 Bg[:, :w] = B[:, g:g + w]
-                bd, xd = _mat(torch, Bg, n, nvec, dt), _mat(torch, None, n, nvec, dt)
+                bd, xd = U.vec(torch, Bg, n, dt, nvec), U.vec(torch, None, n, dt, nvec)
                 with api.CGMulti(op.A, nvec) as cg:
-                    s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=_stream(torch))
-                Xg = _host(xd, n)
+                    s = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=U.stream(torch))
+                Xg = U.host(xd, n)
                 assert not Xg[:, w:].any() and all(c["iterations"] == 0 and c["status"] == api.CG_CONVERGED for c in s[w:])      # the padding
                 for j in range(w):
                     info = infos[g + j]
@@ -477,10 +426,10 @@ def test_sparse_operator_cg_with_a_matrix_of_right_hand_sides(torch_cuda, dtype)
                     assert info["converged"] and info["relative_residual"] <= M.RTOL[dt]
         b = torch.from_numpy(np.ascontiguousarray(B8[:, 0])).cuda()
         x, info = op.cg(b, rtol=M.RTOL[dt], maxiter=500)
-        xd = _vec(torch, None, n, dt)
+        xd = U.vec(torch, None, n, dt)
         with api.CG(op.A) as cg:
-            s = cg.solve(b.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=_stream(torch))
-        assert isinstance(info, dict) and x.dim() == 1 and info["iterations"] == s["iterations"] and np.array_equal(x.cpu().numpy(), _host(xd, n))
+            s = cg.solve(b.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=500, stream=U.stream(torch))
+        assert isinstance(info, dict) and x.dim() == 1 and info["iterations"] == s["iterations"] and np.array_equal(x.cpu().numpy(), U.host(xd, n))
         # a whole group in place: (rows, 4) needs no copies
         X4, infos4 = op.cg(torch.from_numpy(np.ascontiguousarray(B8[:, :4])).cuda(), rtol=M.RTOL[dt], maxiter=500)
         assert all(i["converged"] for i in infos4) and np.array_equal(X4.cpu().numpy()[:, :3], op.cg(torch.from_numpy(np.ascontiguousarray(B8[:, :3])).cuda(), rtol=M.RTOL[dt], maxiter=500)[0].cpu().numpy())

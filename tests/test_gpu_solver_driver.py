@@ -1,9 +1,10 @@
-"""The host-side driver around the kernels of the five device-resident solvers (tilespmv_{cg,cg_multi,cgls,bicgstab,minres}_{state_read,solve}; include/tilespmv.h):
-the versioned state struct with a short or a long ``size``, the refusals of ``*_solve``, ``maxiter = 0``, the ``check_every < 1`` clamp, the clipping of the last batch of
-iterations and the zero right-hand side.  What the iterations compute is the business of tests/test_gpu_{cg,cg_multi,cgls,bicgstab,minres}.py.
+"""The host-side driver around the kernels of the six device-resident solvers (tilespmv_{cg,cg_multi,cgls,bicgstab,minres,gmres}_{state_read,solve}; include/tilespmv.h,
+DESIGN.md §3.7): the versioned state struct with a short or a long ``size``, the refusals of ``*_solve``, ``maxiter = 0``, the ``check_every < 1`` clamp, the clipping of the last
+batch of iterations and the zero right-hand side.  What the iterations compute is the business of tests/test_gpu_{cg,cg_multi,cgls,bicgstab,minres,gmres}.py.
 
 One matrix for all: the SPD tridiagonal with 2.5 on the diagonal and -1 beside it, n = 37 (odd: both builds walk the scalar tail; one workgroup), through SparseOperator
-(deterministic=1, placement_tries=1), b = cg_mirror.rhs(n).  cg_multi runs with nvec = 2: column 1 is b, column 0 is b reversed, or zero where a test says "zero column".
+(deterministic=1, placement_tries=1), b = cg_mirror.rhs(n).  cg_multi runs with nvec = 2: column 1 is b, column 0 is b reversed, or zero where a test says "zero column"; gmres
+with restart 16, as tests/test_gpu_gmres.py.
 The library is called through ``op.A.lib`` with ctypes and raw byte buffers, so that state structs of any length are possible.  No case here launches anything it should not:
 every refused call returns before a launch."""
 import ctypes as C
@@ -14,17 +15,16 @@ import numpy as np
 import pytest
 
 import cg_mirror as M
+import gpu_solver_util as U
+from gpu_solver_util import DTYPES, SENTINEL, torch_cuda  # noqa: F401
 from tilespmv_amd import _lib, api
-from tilespmv_amd.operator import SparseOperator
 
 pytestmark = pytest.mark.gpu
 
-N, NVEC = 37, 2
-SOLVERS = ["cg", "cg_multi", "cgls", "bicgstab", "minres"]
-DTYPES = [np.float64, np.float32]
+N, NVEC, RESTART = 37, 2, 16
+SOLVERS = ["cg", "cg_multi", "cgls", "bicgstab", "minres", "gmres"]
 INVALID = api.HIP_ERROR_INVALID_VALUE
 FILL, GUARD = 0xA5, 32      # every byte of a state buffer before a call; bytes behind the last struct
-SENTINEL = 777.0
 HEAD = 3 * C.sizeof(C.c_int)   # size, iterations, status: the shortest struct state_read serves
 
 
@@ -38,17 +38,10 @@ def _tridiagonal():
 
 
 @pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
 def ops(torch_cuda):
     """The operator of each value type, shared by every test of the module."""
     rp, ci, v = _tridiagonal()
-    made = {np.dtype(dt): SparseOperator(N, N, rp, ci, np.ascontiguousarray(v, dtype=dt), dtype=dt, deterministic=1, placement_tries=1) for dt in DTYPES}
+    made = {np.dtype(dt): U.square_op(N, rp, ci, v, dt) for dt in DTYPES}
     yield made
     for op in made.values():
         op.close()
@@ -78,7 +71,7 @@ class Driver:
         self.State = _lib.CGLSState if name == "cgls" else _lib.CGState
         self.count = NVEC if name == "cg_multi" else 1      # state structs per call
         self.damp = (0.0,) if name == "cgls" else ()
-        self.tdt = torch.float64 if op.dtype == np.float64 else torch.float32
+        self.tdt = U.tdt(torch, op.dtype)
         self.dt = op.dtype
         self.h = C.c_void_p()
         create = self._fn("create")
@@ -86,6 +79,8 @@ class Driver:
             rc = create(C.byref(self.h), op.A.h, NVEC, None)
         elif name == "cgls":
             rc = create(C.byref(self.h), op.A.h, op.AT.h, None)
+        elif name == "gmres":
+            rc = create(C.byref(self.h), op.A.h, RESTART, None)
         else:
             rc = create(C.byref(self.h), op.A.h, None)
         assert rc == 0 and self.h
@@ -100,7 +95,7 @@ class Driver:
         self._fn("destroy")(self.h)
 
     def stream(self):
-        return self.torch.cuda.current_stream().cuda_stream
+        return U.stream(self.torch)
 
     # ---- device vectors: N elements (cg_multi: N rows of NVEC) with 16 sentinel rows behind them
     def vec(self, a):
@@ -139,6 +134,11 @@ class Driver:
 
     def iterate(self, x, count):
         return self._fn("iterate")(self.h, _vp(x.data_ptr()), count, _vp(self.stream()))
+
+    def current(self, x):
+        """After ``iterate``, before x is read.  GMRES holds the iterate in x only after a close (DESIGN.md §3.13), and ``tilespmv_gmres_solve`` ends with a flush: so a flush;
+        nothing for the others."""
+        return self._fn("flush")(self.h, _vp(x.data_ptr()), _vp(self.stream())) if self.name == "gmres" else 0
 
     def state_read(self, buf):
         return self._fn("state_read")(self.h, _vp(self.stream()), C.cast(buf, C.POINTER(self.State)))
@@ -249,13 +249,14 @@ def test_check_every_below_one_is_one(torch_cuda, ops, name, dt):
 
 @pytest.mark.parametrize("name", SOLVERS)
 def test_the_last_batch_is_clipped(torch_cuda, ops, name, dt):
-    """rtol = 0, maxiter = 10, check_every = 4: MAXITER at 10 iterations (4 + 4 + 2), and x has the bits of begin and iterate(10) on a second solver from the same x0."""
+    """rtol = 0, maxiter = 10, check_every = 4: MAXITER at 10 iterations (4 + 4 + 2), and x has the bits of begin and iterate(10) on a second solver from the same x0 (gmres:
+    after the flush that its solve ends with, Driver.current)."""
     x0 = M.rhs(N)[::-1] / 2 if name != "cg_multi" else np.stack([M.rhs(N) / 2, M.rhs(N)[::-1] / 2], axis=1)
     with Driver(name, ops[dt], torch_cuda) as d, Driver(name, ops[dt], torch_cuda) as d2:
         b, x, x2 = d.rhs(), d.vec(x0), d2.vec(x0)
         rc, states = d.solved(b, x, 0.0, 10, 4)
         assert rc == 0 and [(s.iterations, s.status) for s in states] == [(10, api.CG_MAXITER)] * d.count
-        assert d2.begin(b, x2) == 0 and d2.iterate(x2, 10) == 0
+        assert d2.begin(b, x2) == 0 and d2.iterate(x2, 10) == 0 and d2.current(x2) == 0
         assert np.array_equal(d.bits(x), d2.bits(x2))
 
 
@@ -283,4 +284,4 @@ def test_zero_right_hand_side(torch_cuda, ops, name, dt):
             print("%s column 1 beside a zero column: %d iterations, sqrt(rr/bb) %.3g, error vs spsolve %.3g (mirror %.3g)" % (dt, s1.iterations, (s1.rr / s1.bb) ** 0.5, err, errm))
             assert s1.status == api.CG_CONVERGED and s1.iterations > 0 and s1.rr <= 1e-8 * 1e-8 * s1.bb
             assert err <= 10 * errm, (err, errm)
-        assert (x.cpu().numpy()[N:] == SENTINEL).all()
+        U.intact((x, N))

@@ -13,15 +13,13 @@ import bicgstab_mirror as BM
 import cg_mirror as M
 import cg_multi_cases as MC
 import cgls_mirror as LM
+import gpu_solver_util as U
 import solver_sizes as Z
+from gpu_solver_util import DTYPES, PRODUCT_TOL, torch_cuda  # noqa: F401
 from tilespmv_amd import api
 from tilespmv_amd.operator import SparseOperator
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [np.float64, np.float32]
-PRODUCT_TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.float32): 1e-5}   # README: the project's per-product tolerance on real-valued data
-SENTINEL = 777.0
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -30,13 +28,6 @@ def _torch_opens_the_device_first():
     import torch
     torch.zeros(1, device="cuda")
     yield
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -76,51 +67,15 @@ def _scattered(built, case, dt):
     return built(("scattered", case, np.dtype(dt).name), make)
 
 
-def _tdt(torch, dt):
-    return torch.float64 if np.dtype(dt) == np.float64 else torch.float32
-
-
-def _vec(torch, a, n, dt, nvec=None):
-    """A device vector of n elements (an (n, nvec) row-major array) with 16 sentinel elements (rows) behind it: the whole tensor."""
-    t = torch.full((n + 16,) if nvec is None else (n + 16, nvec), SENTINEL, dtype=_tdt(torch, dt), device="cuda")
-    if a is None:
-        t[:n].zero_()
-    else:
-        t[:n].copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=dt)))
-    return t
-
-
-def _host(t, n):
-    return t.cpu().numpy()[:n].copy()
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _intact(*tensors_and_lengths):
-    for t, n in tensors_and_lengths:
-        assert (t.cpu().numpy()[n:] == SENTINEL).all(), "a sentinel behind a caller vector was overwritten"
-
-
-def _relerr(x, ref):
-    ref = np.asarray(ref, dtype=np.float64)
-    return float(np.linalg.norm(np.asarray(x, dtype=np.float64) - ref) / np.linalg.norm(ref))
-
-
-def _dist(a, b):
-    return abs(a - b) / abs(b) if b != 0 else abs(a)
-
-
 # ---- against the mirrors
 def _steps_equal_the_mirror(torch, label, dt, solver, mirror, begin, bd, b, xd, x0, nx, keys0, keys, repeat, bound=None):
     """begin, iterate(1), iterate(2) on the GPU and on the mirror: x and the state's scalars after every step within `bound` (100 x PRODUCT_TOL unless the caller measured
     another one); with `repeat`, a second begin + iterate(3) on the same handle gives the same bits.  Returns the largest differences seen."""
-    stream = _stream(torch)
+    stream = U.stream(torch)
     bound = 100 * PRODUCT_TOL[dt] if bound is None else bound
     begin()
     s0 = solver.state(stream)
-    d0 = max(_dist(s0[k], getattr(mirror, k)) for k in keys0)
+    d0 = max(U.dist(s0[k], getattr(mirror, k)) for k in keys0)
     print("%s %s begin: largest relative difference of %s = %.3g (bound %.3g)" % (label, dt, "/".join(keys0), d0, bound))
     assert s0["iterations"] == 0 and s0["status"] == api.CG_RUNNING
     assert d0 <= bound
@@ -128,9 +83,9 @@ def _steps_equal_the_mirror(torch, label, dt, solver, mirror, begin, bd, b, xd, 
     for step in (1, 2):
         solver.iterate(xd.data_ptr(), step, stream); mirror.iterate(step); done += step
         s = solver.state(stream)
-        x = _host(xd, nx)
-        dx = _relerr(x, mirror.x)
-        dk = max(_dist(s[k], getattr(mirror, k)) for k in keys)
+        x = U.host(xd, nx)
+        dx = U.relerr(x, mirror.x)
+        dk = max(U.dist(s[k], getattr(mirror, k)) for k in keys)
         print("%s %s after %d iterations: |x - mirror| / |mirror| = %.3g, %s %.3g (bound %.3g)" % (label, dt, done, dx, "/".join(keys), dk, bound))
         assert s["iterations"] == done and s["status"] == api.CG_RUNNING
         assert dx <= bound and dk <= bound
@@ -140,8 +95,8 @@ def _steps_equal_the_mirror(torch, label, dt, solver, mirror, begin, bd, b, xd, 
         begin()
         solver.iterate(xd.data_ptr(), 3, stream)
         s2 = solver.state(stream)
-        assert np.array_equal(_host(xd, nx), x) and all(s2[k] == s[k] for k in keys) and s2["iterations"] == 3
-    assert np.array_equal(_host(bd, len(b)), b)
+        assert np.array_equal(U.host(xd, nx), x) and all(s2[k] == s[k] for k in keys) and s2["iterations"] == 3
+    assert np.array_equal(U.host(bd, len(b)), b)
     return worst
 
 
@@ -161,14 +116,14 @@ def test_cg_equals_the_mirror(torch_cuda, built, case, preconditioned, dtype):
     dinv = Z.diagonal_preconditioner(n).astype(dt) if preconditioned else None
     m = M.Mirror(M.scipy_csr(n, rp, ci, vt), dt, dinv)
     m.begin(b, x0)
-    bd, xd = _vec(torch, b, n, dt), _vec(torch, x0, n, dt)
-    dd = _vec(torch, dinv, n, dt) if preconditioned else None
+    bd, xd = U.vec(torch, b, n, dt), U.vec(torch, x0, n, dt)
+    dd = U.vec(torch, dinv, n, dt) if preconditioned else None
     with api.CG(plan, dd.data_ptr() if preconditioned else None) as cg:
         _steps_equal_the_mirror(torch, "CG %s%s" % (case, " preconditioned" if preconditioned else ""), dt, cg, m,
-                                lambda: cg.begin(bd.data_ptr(), xd.data_ptr(), _stream(torch)), bd, b, xd, x0, n, ("bb", "rr"), ("rr",), case == "capped")
-    _intact((bd, n), (xd, n), *(((dd, n),) if preconditioned else ()))
+                                lambda: cg.begin(bd.data_ptr(), xd.data_ptr(), U.stream(torch)), bd, b, xd, x0, n, ("bb", "rr"), ("rr",), case == "capped")
+    U.intact((bd, n), (xd, n), *(((dd, n),) if preconditioned else ()))
     if preconditioned:
-        assert np.array_equal(_host(dd, n), dinv)
+        assert np.array_equal(U.host(dd, n), dinv)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -183,14 +138,14 @@ def test_bicgstab_equals_the_mirror(torch_cuda, built, case, preconditioned, dty
     dinv = Z.diagonal_preconditioner(n).astype(dt) if preconditioned else None
     m = BM.Mirror(BM.scipy_csr(n, rp, ci, vt), dt, dinv)
     m.begin(b, x0)
-    bd, xd = _vec(torch, b, n, dt), _vec(torch, x0, n, dt)
-    dd = _vec(torch, dinv, n, dt) if preconditioned else None
+    bd, xd = U.vec(torch, b, n, dt), U.vec(torch, x0, n, dt)
+    dd = U.vec(torch, dinv, n, dt) if preconditioned else None
     with api.BiCGStab(plan, dd.data_ptr() if preconditioned else None) as bs:
         _steps_equal_the_mirror(torch, "BiCGStab %s%s" % (case, " preconditioned" if preconditioned else ""), dt, bs, m,
-                                lambda: bs.begin(bd.data_ptr(), xd.data_ptr(), _stream(torch)), bd, b, xd, x0, n, ("bb", "rr"), ("rr",), case == "capped")
-    _intact((bd, n), (xd, n), *(((dd, n),) if preconditioned else ()))
+                                lambda: bs.begin(bd.data_ptr(), xd.data_ptr(), U.stream(torch)), bd, b, xd, x0, n, ("bb", "rr"), ("rr",), case == "capped")
+    U.intact((bd, n), (xd, n), *(((dd, n),) if preconditioned else ()))
     if preconditioned:
-        assert np.array_equal(_host(dd, n), dinv)
+        assert np.array_equal(U.host(dd, n), dinv)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -206,14 +161,14 @@ def test_cgls_equals_the_mirror(torch_cuda, built, case, preconditioned, dtype):
     cinv = LM.column_cinv(A, dt) if preconditioned else None
     m = LM.Mirror(A, dt, cinv)
     m.begin(b, x0)
-    bd, xd = _vec(torch, b, rows, dt), _vec(torch, x0, cols, dt)
-    cd = _vec(torch, cinv, cols, dt) if preconditioned else None
+    bd, xd = U.vec(torch, b, rows, dt), U.vec(torch, x0, cols, dt)
+    cd = U.vec(torch, cinv, cols, dt) if preconditioned else None
     with api.CGLS(op.A, op.AT, cd.data_ptr() if preconditioned else None) as ls:
         _steps_equal_the_mirror(torch, "CGLS %s%s" % (case, " with cinv" if preconditioned else ""), dt, ls, m,
-                                lambda: ls.begin(bd.data_ptr(), xd.data_ptr(), 0.0, _stream(torch)), bd, b, xd, x0, cols, ("bb", "rr", "nn", "nn0"), ("nn", "rr"), True)
-    _intact((bd, rows), (xd, cols), *(((cd, cols),) if preconditioned else ()))
+                                lambda: ls.begin(bd.data_ptr(), xd.data_ptr(), 0.0, U.stream(torch)), bd, b, xd, x0, cols, ("bb", "rr", "nn", "nn0"), ("nn", "rr"), True)
+    U.intact((bd, rows), (xd, cols), *(((cd, cols),) if preconditioned else ()))
     if preconditioned:
-        assert np.array_equal(_host(cd, cols), cinv)
+        assert np.array_equal(U.host(cd, cols), cinv)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -224,7 +179,7 @@ def test_cg_multi_equals_the_mirror_per_column(torch_cuda, built, case, nvec, pr
     column).  First run on the MI355X, largest difference of x or rr over the columns and steps: fp64 capped nvec 8 / 4 / 2: 2.7e-15 / 2.6e-15 / 5.7e-16, fold2 2.9e-15,
     preconditioned 2.4e-15; fp32 1.3e-06 / 1.3e-06 / 8.6e-08, fold2 1.3e-06, preconditioned 1.2e-06."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     bound = 100 * PRODUCT_TOL[dt]
     rows = Z.multi_rows(case, nvec, dt)
     plan, (_, rp, ci, vt) = _square(built, "spd", rows, dt)
@@ -235,24 +190,24 @@ def test_cg_multi_equals_the_mirror_per_column(torch_cuda, built, case, nvec, pr
     mirrors = [M.Mirror(A, dt, dinv) for _ in range(nvec)]
     for j, m in enumerate(mirrors):
         m.begin(B[:, j], X0[:, j])
-    bd, xd = _vec(torch, B, rows, dt, nvec), _vec(torch, X0, rows, dt, nvec)
-    dd = _vec(torch, dinv, rows, dt) if preconditioned else None
+    bd, xd = U.vec(torch, B, rows, dt, nvec), U.vec(torch, X0, rows, dt, nvec)
+    dd = U.vec(torch, dinv, rows, dt) if preconditioned else None
     worst = 0.0
     with api.CGMulti(plan, nvec, dd.data_ptr() if preconditioned else None) as cg:
         cg.begin(bd.data_ptr(), xd.data_ptr(), stream)
         s0 = cg.state(stream)
         for j, m in enumerate(mirrors):
-            d0 = max(_dist(s0[j]["bb"], m.bb), _dist(s0[j]["rr"], m.rr))
+            d0 = max(U.dist(s0[j]["bb"], m.bb), U.dist(s0[j]["rr"], m.rr))
             assert s0[j]["iterations"] == 0 and s0[j]["status"] == api.CG_RUNNING and d0 <= bound, (j, s0[j], m.bb, m.rr)
             worst = max(worst, d0)
         done = 0
         for step in (1, 2):
             cg.iterate(xd.data_ptr(), step, stream); done += step
             s = cg.state(stream)
-            X = _host(xd, rows)
+            X = U.host(xd, rows)
             for j, m in enumerate(mirrors):
                 m.iterate(step)
-                dx, drr = _relerr(X[:, j], m.x), _dist(s[j]["rr"], m.rr)
+                dx, drr = U.relerr(X[:, j], m.x), U.dist(s[j]["rr"], m.rr)
                 print("CGMulti %s nvec %d %s column %d after %d iterations: |x - mirror| / |mirror| = %.3g, rr %.3g (bound %.3g)" % (case, nvec, dt, j, done, dx, drr, bound))
                 assert s[j]["iterations"] == done and s[j]["status"] == api.CG_RUNNING
                 assert dx <= bound and drr <= bound, (j, dx, drr)
@@ -262,10 +217,10 @@ def test_cg_multi_equals_the_mirror_per_column(torch_cuda, built, case, nvec, pr
             cg.begin(bd.data_ptr(), xd.data_ptr(), stream)
             cg.iterate(xd.data_ptr(), 3, stream)
             s2 = cg.state(stream)
-            assert np.array_equal(_host(xd, rows), X) and [c["rr"] for c in s2] == [c["rr"] for c in s]
+            assert np.array_equal(U.host(xd, rows), X) and [c["rr"] for c in s2] == [c["rr"] for c in s]
     print("CGMulti %s nvec %d %s%s: largest difference %.3g" % (case, nvec, dt, " preconditioned" if preconditioned else "", worst))
-    assert np.array_equal(_host(bd, rows), B)
-    _intact((bd, rows), (xd, rows), *(((dd, rows),) if preconditioned else ()))
+    assert np.array_equal(U.host(bd, rows), B)
+    U.intact((bd, rows), (xd, rows), *(((dd, rows),) if preconditioned else ()))
 
 
 # ---- exact cases: A = 2 I, integer data, no tolerance
@@ -276,14 +231,14 @@ def test_two_identity_is_solved_exactly(torch_cuda, built, solver, dtype):
     alpha = 1/2; with dinv = 1/2: alpha = 1; BiCGStab: alpha = 1/2, s = 0, omega = 0, converged at the half step; CGLS: alpha = 1/4), status CONVERGED, and sixteen more
     iterations change nothing.  An element dropped, visited twice or left unwritten by any sweep changes x or one of the integer sums."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     n = Z.capped_n(dt)
     plan, _ = _square(built, "2I", n, dt)
     b64 = Z.exact_rhs(n)
     bb = Z.exact_bb(b64)
     b, half = b64.astype(dt), (b64 / 2).astype(dt)
-    bd, xd = _vec(torch, b, n, dt), _vec(torch, None, n, dt)
-    dd = _vec(torch, np.full(n, 0.5), n, dt) if solver == "cg_dinv" else None
+    bd, xd = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt)
+    dd = U.vec(torch, np.full(n, 0.5), n, dt) if solver == "cg_dinv" else None
     if solver in ("cg", "cg_dinv"):
         s = api.CG(plan, dd.data_ptr() if dd is not None else None)
     elif solver == "bicgstab":
@@ -302,14 +257,14 @@ def test_two_identity_is_solved_exactly(torch_cuda, built, solver, dtype):
             assert s0["nn"] == 4 * bb and s0["nn0"] == 4 * bb
         s.iterate(xd.data_ptr(), 1, stream)
         s1 = s.state(stream)
-        x1 = _host(xd, n)
+        x1 = U.host(xd, n)
         assert np.array_equal(x1, half), "%d elements of x differ from b / 2, the first at %d" % (int((x1 != half).sum()), int(np.argmax(x1 != half)))
         assert s1[norm] == 0.0 and s1["rr"] == 0.0 and s1["bb"] == bb and s1["iterations"] == 1 and s1["status"] == api.CG_CONVERGED, s1
         s.iterate(xd.data_ptr(), 16, stream)
         s17 = s.state(stream)
-        assert s17["iterations"] == 17 and s17[norm] == 0.0 and s17["status"] == api.CG_CONVERGED and np.array_equal(_host(xd, n), half)
-    assert np.array_equal(_host(bd, n), b)
-    _intact((bd, n), (xd, n), *(((dd, n),) if dd is not None else ()))
+        assert s17["iterations"] == 17 and s17[norm] == 0.0 and s17["status"] == api.CG_CONVERGED and np.array_equal(U.host(xd, n), half)
+    assert np.array_equal(U.host(bd, n), b)
+    U.intact((bd, n), (xd, n), *(((dd, n),) if dd is not None else ()))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -320,7 +275,7 @@ def test_two_identity_is_solved_exactly_per_column(torch_cuda, built, nvec, zero
     as a swapped bb; after one iteration X = B / 2, rr = 0 and CONVERGED in every column.  alpha = 1/2 in every column of 2 I, so a ROTATED alpha would pass: with
     `zero_column` the last column but one is 0 (its alpha is 0 by the rho = 0 guard, its state CONVERGED from the start) and its neighbours still have to reach B / 2."""
     torch, dt = torch_cuda, np.dtype(dtype)
-    stream = _stream(torch)
+    stream = U.stream(torch)
     rows = Z.multi_rows("capped", nvec, dt)
     plan, _ = _square(built, "2I", rows, dt)
     B64 = Z.exact_columns(rows, nvec)
@@ -328,7 +283,7 @@ def test_two_identity_is_solved_exactly_per_column(torch_cuda, built, nvec, zero
         B64[:, nvec - 2] = 0
     bbs = [Z.exact_bb(B64[:, c]) for c in range(nvec)]
     B, half = np.ascontiguousarray(B64.astype(dt)), np.ascontiguousarray((B64 / 2).astype(dt))
-    bd, xd = _vec(torch, B, rows, dt, nvec), _vec(torch, None, rows, dt, nvec)
+    bd, xd = U.vec(torch, B, rows, dt, nvec), U.vec(torch, None, rows, dt, nvec)
     with api.CGMulti(plan, nvec) as cg:
         cg.begin(bd.data_ptr(), xd.data_ptr(), stream)
         s0 = cg.state(stream)
@@ -337,12 +292,12 @@ def test_two_identity_is_solved_exactly_per_column(torch_cuda, built, nvec, zero
         for count, total in ((1, 1), (16, 17)):
             cg.iterate(xd.data_ptr(), count, stream)
             s = cg.state(stream)
-            X = _host(xd, rows)
+            X = U.host(xd, rows)
             bad = [c for c in range(nvec) if not np.array_equal(X[:, c], half[:, c])]
             assert bad == [], "columns %s differ from B / 2 after %d iterations" % (bad, total)
             assert all(c["rr"] == 0.0 and c["status"] == api.CG_CONVERGED and c["iterations"] == total for c in s) and [c["bb"] for c in s] == bbs, s
-    assert np.array_equal(_host(bd, rows), B)
-    _intact((bd, rows), (xd, rows))
+    assert np.array_equal(U.host(bd, rows), B)
+    U.intact((bd, rows), (xd, rows))
 
 
 # ---- below one lane vector
@@ -370,13 +325,13 @@ def test_tiny_systems(torch_cuda, solver, dtype):
         xm, itm, stm, relm = Mir.Mirror(A, dt).solve(b, rtol=Mir.RTOL[dt], maxiter=50, check_every=1)
         assert stm == Mir.CONVERGED
         plan = api.Plan.from_csr(n, n, len(ci), rp, ci, vt, dtype=dt, deterministic=1, placement_tries=1)
-        bd, xd = _vec(torch, b, n, dt), _vec(torch, None, n, dt)
+        bd, xd = U.vec(torch, b, n, dt), U.vec(torch, None, n, dt)
         with Solver(plan) as s:
-            st = s.solve(bd.data_ptr(), xd.data_ptr(), rtol=Mir.RTOL[dt], maxiter=2 * itm + 2, check_every=1, stream=_stream(torch))
+            st = s.solve(bd.data_ptr(), xd.data_ptr(), rtol=Mir.RTOL[dt], maxiter=2 * itm + 2, check_every=1, stream=U.stream(torch))
         assert st["status"] == api.CG_CONVERGED and st["relative_residual"] <= Mir.RTOL[dt], (n, st)
-        _yardstick("%s n = %d, %d iterations (mirror %d)" % (solver, n, st["iterations"], itm), dt, _relerr(_host(xd, n), xs), _relerr(xm, xs))
-        assert np.array_equal(_host(bd, n), b)
-        _intact((bd, n), (xd, n))
+        _yardstick("%s n = %d, %d iterations (mirror %d)" % (solver, n, st["iterations"], itm), dt, U.relerr(U.host(xd, n), xs), U.relerr(xm, xs))
+        assert np.array_equal(U.host(bd, n), b)
+        U.intact((bd, n), (xd, n))
         plan.close()
 
 
@@ -394,19 +349,19 @@ def test_tiny_multi_systems(torch_cuda, dtype):
         for nvec in Z.TINY_NVEC:
             B = np.ascontiguousarray(B8[:, :nvec].astype(dt))
             mirrors = [M.Mirror(A, dt).solve(B[:, j], rtol=M.RTOL[dt], maxiter=50, check_every=1) for j in range(nvec)]
-            bd, xd = _vec(torch, B, rows, dt, nvec), _vec(torch, None, rows, dt, nvec)
+            bd, xd = U.vec(torch, B, rows, dt, nvec), U.vec(torch, None, rows, dt, nvec)
             with api.CGMulti(plan, nvec) as cg:
-                states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * max(m[1] for m in mirrors) + 2, check_every=1, stream=_stream(torch))
-            X = _host(xd, rows)
+                states = cg.solve(bd.data_ptr(), xd.data_ptr(), rtol=M.RTOL[dt], maxiter=2 * max(m[1] for m in mirrors) + 2, check_every=1, stream=U.stream(torch))
+            X = U.host(xd, rows)
             for j, (st, (xm, itm, stm, relm)) in enumerate(zip(states, mirrors)):
                 assert stm == M.CONVERGED and st["status"] == api.CG_CONVERGED and st["relative_residual"] <= M.RTOL[dt], (rows, nvec, j, st)
                 if not B[:, j].any():
                     assert st["iterations"] == 0 and not X[:, j].any()
                     continue
                 xs = np.linalg.solve(A.toarray().astype(np.float64), B[:, j].astype(np.float64))
-                _yardstick("multi rows = %d nvec = %d column %d" % (rows, nvec, j), dt, _relerr(X[:, j], xs), _relerr(xm, xs))
-            assert np.array_equal(_host(bd, rows), B)
-            _intact((bd, rows), (xd, rows))
+                _yardstick("multi rows = %d nvec = %d column %d" % (rows, nvec, j), dt, U.relerr(X[:, j], xs), U.relerr(xm, xs))
+            assert np.array_equal(U.host(bd, rows), B)
+            U.intact((bd, rows), (xd, rows))
         plan.close()
 
 
@@ -423,10 +378,10 @@ def test_tiny_least_squares(torch_cuda, dtype):
         xm, itm, stm, relm = LM.Mirror(A, dt).solve(b, rtol=LM.RTOL[dt], maxiter=50, check_every=1)
         assert stm == LM.CONVERGED
         with SparseOperator(rows, cols, rp, ci, vt, dtype=dt, deterministic=1, placement_tries=1) as op:
-            bd, xd = _vec(torch, b, rows, dt), _vec(torch, None, cols, dt)
+            bd, xd = U.vec(torch, b, rows, dt), U.vec(torch, None, cols, dt)
             with api.CGLS(op.A, op.AT) as ls:
-                st = ls.solve(bd.data_ptr(), xd.data_ptr(), damp=0.0, rtol=LM.RTOL[dt], maxiter=2 * itm + 2, check_every=1, stream=_stream(torch))
+                st = ls.solve(bd.data_ptr(), xd.data_ptr(), damp=0.0, rtol=LM.RTOL[dt], maxiter=2 * itm + 2, check_every=1, stream=U.stream(torch))
             assert st["status"] == api.CG_CONVERGED and st["relative_normal_residual"] <= LM.RTOL[dt], (rows, cols, st)
-            _yardstick("CGLS %d x %d, %d iterations (mirror %d)" % (rows, cols, st["iterations"], itm), dt, _relerr(_host(xd, cols), xs), _relerr(xm, xs))
-            assert np.array_equal(_host(bd, rows), b)
-            _intact((bd, rows), (xd, cols))
+            _yardstick("CGLS %d x %d, %d iterations (mirror %d)" % (rows, cols, st["iterations"], itm), dt, U.relerr(U.host(xd, cols), xs), U.relerr(xm, xs))
+            assert np.array_equal(U.host(bd, rows), b)
+            U.intact((bd, rows), (xd, cols))
