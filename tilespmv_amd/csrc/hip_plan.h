@@ -131,6 +131,26 @@ __host__ __device__ inline int pool_word_base_bits(int npatterns)   // bits left
     while ((1 << ib) < npatterns) ib++;
     return POOL_WORD_KR_SHIFT - ib;
 }
+// ---- the stored descriptor forms (DevStream::udesc), each packed HERE by the layout builder's host loops and device kernels alike and unpacked by the kernels (hip_units_kernel.h):
+__host__ __device__ inline UDesc unit_desc12(const uint4 d) { return UDesc{d.x, d.y, d.w}; }   // 12 bytes: the builder's 16-byte record (w0, n0, w0, n1) without the duplicate of word 0
+__host__ __device__ inline unsigned unit_word(unsigned w0, unsigned pid, int cb_bits) { return (w0 & ((1u << cb_bits) - 1u)) | (pid << cb_bits) | ((w0 >> UNIT_FLAG_SHIFT) << 27); }   // 4 bytes, classic dictionary plans: column block | pattern id << cb_bits | flags << 27
+__host__ __device__ inline uint2 pool_pair(unsigned w0, unsigned pid) { return make_uint2(w0, pid); }   // 8 bytes, pooled dictionary plans
+__host__ __device__ inline unsigned pool_word(unsigned w0, unsigned pid, int bb) { return (w0 & POOL_BASE_MASK) | (pid << bb) | ((w0 >> POOL_KR_SHIFT) << POOL_WORD_KR_SHIFT); }   // 4 bytes, pooled dictionary plans whose window base fits bb = pool_word_base_bits(patterns) bits
+// ... and a unit's pattern id = the place of its pattern in the shard's ascending dictionary.  Classic (DevStream::udict): among the entries [lo, hi) of the unit's shift code, by
+// the 64-bit nibble word; pooled (DevStream::pdict): by (n0, n1, r0, r1)
+__host__ __device__ inline unsigned unit_pattern_id(const uint4 *dict, int lo, int hi, unsigned n0, unsigned n1)
+{
+    const unsigned long long key = ((unsigned long long)n0 << 32) | n1;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if ((((unsigned long long)dict[mid].x << 32) | dict[mid].y) < key) lo = mid + 1; else hi = mid; }
+    return (unsigned)lo;
+}
+__host__ __device__ inline bool pool_pattern_less(const uint4 a, const uint4 b) { return a.x != b.x ? a.x < b.x : a.y != b.y ? a.y < b.y : a.z != b.z ? a.z < b.z : a.w < b.w; }
+__host__ __device__ inline unsigned pool_pattern_id(const uint4 *dict, int n, const uint4 q)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (pool_pattern_less(dict[mid], q)) lo = mid + 1; else hi = mid; }
+    return (unsigned)lo;
+}
 constexpr int POOL_MIN_FILL = sizeof(val_t) == 8 ? 12 : 10;   // 16 s_v + 20 bytes per unit against s_v + 5 (4 in the packed lists) per list entry
 #ifndef TILESPMV_POOL_STRIP_ROWS
 #define TILESPMV_POOL_STRIP_ROWS 4

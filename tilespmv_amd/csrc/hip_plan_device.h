@@ -1,6 +1,7 @@
 // hip_plan_device.h — the stages of the unit-stream builder (hip_plan_stream.hip) that touch every nonzero, as kernels over a device-resident Tile_matrix
-// (hip_tile_create.h DevTile): COUNT and EMIT call the same per-tile functions as the host builder (plan_tile_ops.h), ENCODE's descriptor pass and pattern dictionary
-// are a sort + run-length encoding.  The decisions in between (CHOOSE, CUT, ORDER: functions of per-tile-row counts) stay on the host.  SURVEY S8 f1; reference
+// (hip_tile_create.h DevTile): COUNT and EMIT call the same per-tile functions as the host builder (plan_tile_ops.h); ENCODE is one sequence of steps in the builder, whose
+// steps over every unit (pack, distinct patterns, compact, count) are the functions below in device mode and write the descriptor forms with the packers of hip_plan.h.
+// The decisions in between (CHOOSE, CUT, ORDER: functions of per-tile-row counts) stay on the host.  SURVEY S8 f1; reference
 // src/csr2tile.h:629-1020 is the preprocessing this replaces end to end: with tilespmv_plan_create_from_csr only the CSR arrays cross the bus.
 #pragma once
 #include <vector>
@@ -35,12 +36,19 @@ int dev_emit(const DevShard &S, const DevCounts &C, const hvec<long long> &pu, c
 int dev_fetch_word0(const uint4 *d_udesc, long long NU, hvec<unsigned> &w0);
 // ENCODE: units of task i move from [map.x, map.x + map.z) to [map.y, ..) of the packed numbering (padding units in between stay zero)
 int dev_pack_desc(const uint4 *d_udesc, const uint2 *d_urow, const uint4 *d_ucol, const int4 *d_map, int ntasks, UDesc *d_packed, URow *d_packed_row, uint4 *d_packed_col);   // d_map: device copy of the (old begin, new begin, count) triples
-// the distinct (n0, n1) patterns of NUP packed descriptors, ascending, if there are at most `cap` of them (else `over` = true); then the 4-byte form
 int dev_all_narrowable(const val_t *d_uval, long long n, bool *all_float, bool *all_half);   // fp64 build, one pass: is every one of the n emitted unit values narrowable / halvable (plan_tile_ops.h)?  fp32 build: false
 int dev_shift_histogram(const UDesc *d_packed, long long NUP, unsigned long long hist[8]);   // units per shift code (word 0 >> UNIT_SHIFT_SHIFT)
 int dev_count_flag(const UDesc *d_packed, long long NUP, unsigned flag, long long *count);      // units whose flags (word 0 >> UNIT_FLAG_SHIFT) have a bit of `flag` set
+// classic dictionary: the distinct (shift code, nibbles) patterns of the NUP packed units as dictionary entries, ascending, if there are at most `cap` (else over); then the 4-byte words
+int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vector<uint4> &dict, bool *over);
 struct DictRanges { int off[9]; };   // dictionary entries of shift code c (word 0 >> UNIT_SHIFT_SHIFT): [off[c], off[c + 1])
-int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vector<uint4> &dict, DictRanges *ranges, bool *over);   // distinct (shift code, nibbles) patterns in ascending order, as dictionary entries
+inline DictRanges dict_ranges(const std::vector<uint4> &dict)
+{
+    DictRanges R;
+    size_t i = 0;
+    for (unsigned c = 0; c <= 8; c++) { while (i < dict.size() && (dict[i].z >> UNIT_SHIFT_SHIFT) < c) i++; R.off[c] = (int)i; }
+    return R;
+}
 int dev_compact_desc(const UDesc *d_packed, long long NUP, const uint4 *d_dict, DictRanges ranges, int cb_bits, unsigned *d_compact);
 // pooled dictionary plans: the distinct 16-byte patterns (n0, n1, r0, r1) of the packed units, ascending, if at most `cap` (else over); then the 8-byte (word 0, pattern id) form
 int dev_pool_dict(const UDesc *d_packed, const URow *d_packed_row, long long NUP, size_t cap, std::vector<uint4> &sorted_patterns, bool *over);

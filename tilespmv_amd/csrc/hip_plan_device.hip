@@ -222,8 +222,7 @@ __global__ __launch_bounds__(256) void k_pd_pack_desc(const uint4 *__restrict__ 
     for (int t = blockIdx.x; t < ntasks; t += gridDim.x) {
         const int4 m = map[t];
         for (int j = threadIdx.x; j < m.z; j += 256) {
-            const uint4 d = udesc[(long long)m.x + j];
-            packed[(long long)m.y + j] = UDesc{d.x, d.y, d.w};
+            packed[(long long)m.y + j] = unit_desc12(udesc[(long long)m.x + j]);
             if (urow) { const uint2 r = urow[(long long)m.x + j]; packed_row[(long long)m.y + j] = URow{r.x, r.y}; }
             if (ucol) packed_col[(long long)m.y + j] = ucol[(long long)m.x + j];
         }
@@ -253,11 +252,8 @@ __global__ __launch_bounds__(256) void k_pd_compact(const UDesc *__restrict__ pa
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const UDesc d = packed[i];
-    const u64 key = ((u64)d.n0 << 32) | d.n1;
     const unsigned code = d.w0 >> UNIT_SHIFT_SHIFT;
-    int lo = ranges.off[code], hi = ranges.off[code + 1];   // lower bound among the entries of the unit's shift code (ascending nibbles)
-    while (lo < hi) { const int mid = (lo + hi) >> 1; const uint4 q = dict[mid]; if ((((u64)q.x << 32) | q.y) < key) lo = mid + 1; else hi = mid; }
-    compact[i] = (d.w0 & ((1u << cb_bits) - 1u)) | ((unsigned)lo << cb_bits) | ((d.w0 >> UNIT_FLAG_SHIFT) << 27);
+    compact[i] = unit_word(d.w0, unit_pattern_id(dict, ranges.off[code], ranges.off[code + 1], d.n0, d.n1), cb_bits);
 }
 
 
@@ -409,19 +405,9 @@ __global__ __launch_bounds__(256) void k_pd_pool_compact(const UDesc *__restrict
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const unsigned q[4] = {packed[i].n0, packed[i].n1, prow[i].r0, prow[i].r1};
-    int lo = 0, hi = ndict;   // lower bound in the ascending (n0, n1, r0, r1) dictionary
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const uint4 d = dict[mid];
-        const unsigned e[4] = {d.x, d.y, d.z, d.w};
-        bool less = false;
-        for (int k = 0; k < 4; k++) { if (e[k] != q[k]) { less = e[k] < q[k]; break; } }
-        if (less) lo = mid + 1; else hi = mid;
-    }
-    const unsigned w0 = packed[i].w0;
-    if (word_bits > 0) reinterpret_cast<unsigned *>(out)[i] = (w0 & POOL_BASE_MASK) | ((unsigned)lo << word_bits) | ((w0 >> POOL_KR_SHIFT) << POOL_WORD_KR_SHIFT);   // (hip_plan.h: 4-byte pooled descriptors)
-    else reinterpret_cast<uint2 *>(out)[i] = make_uint2(w0, (unsigned)lo);
+    const unsigned w0 = packed[i].w0, pid = pool_pattern_id(dict, ndict, make_uint4(packed[i].n0, packed[i].n1, prow[i].r0, prow[i].r1));
+    if (word_bits > 0) reinterpret_cast<unsigned *>(out)[i] = pool_word(w0, pid, word_bits);
+    else reinterpret_cast<uint2 *>(out)[i] = pool_pair(w0, pid);
 }
 }  // namespace
 
@@ -691,10 +677,9 @@ int dev_shift_histogram(const UDesc *d_packed, long long NUP, unsigned long long
     return 0;
 }
 
-int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vector<uint4> &dict, DictRanges *ranges, bool *over)
+int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vector<uint4> &dict, bool *over)
 {
     dict.clear(); *over = false;
-    for (int c = 0; c < 9; c++) ranges->off[c] = 0;
     if (NUP <= 0) return 0;
     // how many units carry each shift code: one sort + run-length pass per code that occurs (plans without absorbed entries: code 0 only, the whole array as before)
     Tmp<unsigned long long> hist;
@@ -708,7 +693,6 @@ int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vec
     PD_TRY(uniq.alloc((size_t)NUP, false)); PD_TRY(counts.alloc((size_t)NUP, false)); PD_TRY(nruns.alloc(1, true));
     std::vector<u64> got;
     for (unsigned code = 0; code < 8; code++) {
-        ranges->off[code] = (int)dict.size();
         const long long nc = (long long)h[code];
         if (nc == 0) continue;
         PD_TRY(hipMemset(hist.p + 8, 0, sizeof(unsigned long long)));
@@ -736,7 +720,6 @@ int dev_dict_patterns(const UDesc *d_packed, long long NUP, size_t cap, std::vec
         PD_TRY(hipMemcpy(got.data(), uniq.p, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
         for (u64 k : got) dict.push_back(make_uint4((unsigned)(k >> 32), (unsigned)(k & 0xffffffffull), code << UNIT_SHIFT_SHIFT, 0u));
     }
-    ranges->off[8] = (int)dict.size();
     return 0;
 }
 
@@ -759,12 +742,7 @@ int dev_pool_dict(const UDesc *d_packed, const URow *d_packed_row, long long NUP
     PD_TRY(hipMemcpy(ht.data(), table.p, ht.size() * sizeof(uint4), hipMemcpyDeviceToHost));
     PD_TRY(hipMemcpy(hs.data(), tags.p, hs.size() * sizeof(u64), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < ht.size(); i++) if (hs[i] != 0ull) sorted_patterns.push_back(ht[i]);
-    std::sort(sorted_patterns.begin(), sorted_patterns.end(), [](const uint4 &a, const uint4 &b) {
-        if (a.x != b.x) return a.x < b.x;
-        if (a.y != b.y) return a.y < b.y;
-        if (a.z != b.z) return a.z < b.z;
-        return a.w < b.w;
-    });
+    std::sort(sorted_patterns.begin(), sorted_patterns.end(), pool_pattern_less);
     return 0;
 }
 

@@ -84,7 +84,7 @@ inline void detect_strides(const Tile_matrix *T, int tr0, int tr1, bool csr_spli
 //   CUT      strips of whole tile-rows and pieces of split tile-rows -> task records
 //   EMIT     unit descriptors + values, entry triples, whole-tile and dense-tile payload, in tile order
 //   ORDER    task order: linear, or brick order (stencil-like shards) + the workgroups' x windows
-//   ENCODE   final HBM form of the units: value groups per task, 12-B descriptors or 4-B words + pattern dictionary
+//   ENCODE   final HBM form of the units: value groups per task, the descriptor form the shard's patterns allow (described once, at encode())
 //   ENTRIES  merged, column-ordered, packed entry lists per wavefront / workgroup
 //   FINISH   remaining uploads, cache-policy flags, byte model
 struct StreamBuilder {
@@ -137,14 +137,33 @@ struct StreamBuilder {
     long long value_group() const { return narrow ? UNIT_GROUP_NARROW : UNIT_GROUP; }
     void choose_value_width();
     void set_unit_facts(long long nrowunit, long long nderived) { S.unit_facts = (nrowunit == 0 ? UNIT_FACT_NO_ROWUNIT : 0) | (nderived == 0 ? UNIT_FACT_NO_DERIVED : 0); }   // end of ENCODE, classic plans: what the lean unit kernels rest on
-    int reserve_values()     // arena space for the NUP * 16 stored values, in the plan's form
+    int reserve_values(const void *host = nullptr)     // arena space for the NUP * 16 stored values, in the plan's form; host: the host pass's groups (nullptr: a kernel fills it)
     {
-        if (narrow == 2) return plan->reserve((size_t)NUP * 16, reinterpret_cast<const unsigned short **>(&S.uval));
-        if (narrow) return plan->reserve((size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
-        return plan->reserve((size_t)NUP * 16, &S.uval);
+        if (narrow == 2) return plan->upload((const unsigned short *)host, (size_t)NUP * 16, reinterpret_cast<const unsigned short **>(&S.uval));
+        if (narrow) return plan->upload((const float *)host, (size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
+        return plan->upload((const val_t *)host, (size_t)NUP * 16, &S.uval);
     }
     long long desc_bytes() const { return S.cb_bits > 0 ? 4 : wide ? 28 : pooled ? (pool_dict ? 8 : 20) : 12; }
     std::vector<long long> old_begin;
+    bool renumber_units(std::vector<int4> &map);
+    // The form rules of ENCODE.  Does this shard try the classic dictionary (4-byte words; not for pooled plans), and with which column-block bits and room for how many patterns?
+    // Only where it pays: 8 bytes per unit must be at least 2 % of the streams (an entry-dominated plan with a handful of units would only buy the dictionary hop at the start
+    // of every strip: webbase-1M stand-in 13.2 -> 13.6 us); desc_dict = 1 asks for it wherever it is possible, 0 switches it off
+    bool classic_dict_form(int *cb_bits, size_t *cap) const
+    {
+        if (K.desc_dict == 0 || pooled || NUP <= 0 || !(/* dict_pays: */ K.desc_dict > 0 || 8LL * NUP * 50 >= NUP * (12 + 16LL * sv) + NC * (sv + 4LL))) return false;
+        *cb_bits = std::max(1, 32 - __builtin_clz((unsigned)std::max(1, tilen - 1)));
+        const int pid_bits = std::min(DICT_MAX_BITS, 27 - *cb_bits);
+        *cap = (size_t)1 << std::max(pid_bits, 0);
+        return pid_bits >= 1;
+    }
+    // ... and does a pooled dictionary of n patterns take one 4-byte word per unit — window base, pattern id and tile-row fit it (hip_plan.h; desc_dict = 2 keeps the 8-byte
+    // pairs)?  The bits of the base if so, else 0
+    int pool_word_bits(int n) const
+    {
+        const int bb = pool_word_base_bits(n);
+        return K.desc_dict != 2 && POOL_STRIP_ROWS <= 4 && bb >= 4 && (long long)tilen * 16 <= (1ll << bb) ? bb : 0;
+    }
 
     StreamBuilder(tilespmv_plan *plan_, const Knobs &K_, const Tile_matrix *T_, int rowA_, int colA_, int tr0_, int tr1_, bool coo_in_tile_, bool dense_mfma_,
                   const std::vector<long long> &hyb_off_, std::vector<FixRow> &fix_, int &npartial_, const DevTile *DT_)
@@ -182,7 +201,6 @@ struct StreamBuilder {
     void emit();
     void order();
     void encode();
-    void encode_device();
     void entries();
     void finish(long long &n_tasks, long long &model_bytes);
 };
@@ -770,109 +788,132 @@ void StreamBuilder::choose_value_width()
     if (K.verbose) fprintf(stderr, "tilespmv: unit values: %s\n", narrow == 2 ? "every one is a half: stored in 2 bytes" : narrow ? "every one is a float: stored in 4 bytes" : "8 bytes (not all of them survive the narrowing the knob and the size rule allow)");
 }
 
-// ENCODE in device mode: the same final forms, produced from EMIT's device scratch (hip_plan_device.h)
-void StreamBuilder::encode_device()
+// ---- ENCODE: the final HBM form of the unit streams.
+// Values: the units of one task are stored in GROUPS of G = 16 / sizeof(value) units (2 in fp64, 4 in fp32) — the values of the G units interleaved per row, so that a lane
+// fetches G units with one 16-byte load (row r of the group at +16 r bytes).  A task whose unit count is not a multiple of G gets padding units (zero values, never executed:
+// unit_end excludes them) so that its last group exists.  Narrow plans (fp64, choose_value_width): the values are floats or halves and G = 4, the fp32 build's unit
+// numbering; row r of a group is 16 or 8 bytes.
+// Descriptors (packed and searched by the functions of hip_plan.h, here and in the kernels of hip_plan_device.hip):
+//   12 B  classic units: EMIT's record without the duplicate of word 0
+//    4 B  classic units of a shard with few distinct column patterns (stencil-like shards: 4 patterns in the 5- and 7-point grids, 36 in the KKT stand-in), classic_dict_form:
+//         column block | pattern id << cb_bits | flags << 27, the patterns — a unit's window shift (units that took list entries: plan_tile_ops.h) and its 16 column
+//         nibbles — in the dictionary udict the kernels gather from
+//   20 B  pooled units: the 12 bytes + the row nibbles (urow)
+//    8 B  pooled units of a shard with at most 2^DICT_MAX_BITS distinct 16-byte patterns (column + row nibbles; natural-order meshes use a few dozen — 27-point hex mesh x 3
+//         unknowns: 54; tetrahedral: 31 —, window-shuffled ones a hundred thousand and keep the 20 bytes): (word 0, pattern id), the patterns in pdict.  12 of 148 bytes per
+//         unit: always worth it where it applies (desc_dict = 0 switches it off)
+//    4 B  ... where window base, pattern id and tile-row fit one word (pool_word_bits)
+//   28 B  wide pooled units: the 12 bytes (their nibbles are the row nibbles) + the 16 column-offset bytes (ucol)
+// One sequence of steps for both modes, which differ in where EMIT's arrays are and who walks them: host loops over h_udesc / h_urow / h_ucol (below), or the kernels of
+// hip_plan_device.h over d_udesc / d_urow / d_ucol.  Finding the distinct patterns is the one step whose two implementations are different algorithms (per-thread sets and a
+// sort here; sort + run-length encoding, or a tagged table, there): both give the ascending dictionary.
+void host_pack_units(const std::vector<int4> &map, const std::vector<uint4> &udesc, const std::vector<uint2> &urow, const std::vector<uint4> &ucol, std::vector<UDesc> &packed,
+                     std::vector<URow> &packed_row, std::vector<uint4> &packed_col)
 {
-    const long long G = value_group();
-    auto padded = [&](long long n) { return (n + G - 1) / G * G; };
-    std::vector<int4> pair_map(tasks.size());
-    old_begin.assign(tasks.size(), 0);
-    long long at = 0;
-    for (size_t i = 0; i < tasks.size(); i++) {
-        STask &k = tasks[i];
-        const long long ub = k.unit_begin, n = k.unit_end - ub, nb = at;
-        old_begin[i] = ub;
-        at += padded(n);
-        pair_map[i] = make_int4((int)ub, (int)nb, (int)n, 0);
-        if (n > 0) { k.unit_begin = (int)nb; k.unit_end = (int)(nb + n); }
-    }
-    const double t0 = now_us();
-    const long long up0 = plan->info[TILESPMV_INFO_UPLOAD_US];   // (reserve() / upload() below count their own time: the stage's total replaces it at the end, not adds to it)
-    S.udict = nullptr; S.cb_bits = 0; S.urow = nullptr; S.ucol = nullptr; S.pooled = pooled ? 1 : 0; S.pdict = nullptr; pool_dict = false;
-    void *d_map = nullptr; UDesc *d_packed = nullptr; URow *d_prow = nullptr;
-    auto fail = [&](const char *what, hipError_t e) { fprintf(stderr, "tilespmv: device plan build: %s: %s\n", what, hipGetErrorString(e)); (void)hipGetLastError(); rc = -3; };
-    hipError_t e = hipMalloc(&d_map, std::max<size_t>(pair_map.size(), 1) * sizeof(int4));
-    if (e == hipSuccess && !pair_map.empty()) e = hipMemcpy(d_map, pair_map.data(), pair_map.size() * sizeof(int4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_packed, std::max<long long>(NUP, 1) * sizeof(UDesc) + 256);
-    if (e == hipSuccess) e = hipMemsetAsync(d_packed, 0, std::max<long long>(NUP, 1) * sizeof(UDesc) + 256, 0);
-    if (e != hipSuccess) fail("scratch for the packed descriptors", e);
-    if (wide) rc |= plan->reserve((size_t)NUP, &S.ucol);   // (wide pooled plans: the column-offset bytes are packed straight into the plan's arena)
-    if (pooled && !wide && e == hipSuccess) {   // packed row nibbles: scratch (they end up in the plan's arena, or — pooled dictionary plans — in the dictionary)
-        e = hipMalloc((void **)&d_prow, std::max<long long>(NUP, 1) * sizeof(URow) + 256);
-        if (e == hipSuccess) e = hipMemsetAsync(d_prow, 0, std::max<long long>(NUP, 1) * sizeof(URow) + 256, 0);
-        if (e != hipSuccess) fail("scratch for the packed row nibbles", e);
-    }
-    if (rc == 0 && dev_pack_desc(d_udesc, d_urow, d_ucol, (const int4 *)d_map, (int)pair_map.size(), d_packed, d_prow, const_cast<uint4 *>(S.ucol)) != 0) rc = -3;
-    if (rc == 0 && pooled && !wide && K.desc_dict != 0 && NUP > 0) {   // 8-B descriptors + pattern dictionary (the host builder's rule)
-        std::vector<uint4> pats;
-        bool over = false;
-        if (dev_pool_dict(d_packed, d_prow, NUP, (size_t)1 << DICT_MAX_BITS, pats, &over) != 0) rc = -3;
-        else if (!over) {
-            rc |= plan->upload(pats.data(), pats.size(), &S.pdict);
-            const int bb = pool_word_base_bits((int)pats.size());   // (4-byte words under the host builder's rule)
-            const bool word = K.desc_dict != 2 && POOL_STRIP_ROWS <= 4 && bb >= 4 && (long long)T->tilen * 16 <= (1ll << bb);
-            if (word) rc |= plan->reserve((size_t)NUP, reinterpret_cast<const unsigned **>(&S.udesc));
-            else rc |= plan->reserve((size_t)NUP, reinterpret_cast<const uint2 **>(&S.udesc));
-            if (rc == 0 && dev_pool_compact(d_packed, d_prow, NUP, S.pdict, (int)pats.size(), word ? bb : 0, const_cast<UDesc *>(S.udesc)) != 0) rc = -3;
-            pool_dict = true;
-            if (word) S.cb_bits = bb;
-        }
-    }
-    if (rc == 0 && pooled && !wide && !pool_dict) {
-        rc |= plan->reserve((size_t)NUP, &S.urow);
-        if (rc == 0 && NUP > 0 && (e = hipMemcpy(const_cast<URow *>(S.urow), d_prow, (size_t)NUP * sizeof(URow), hipMemcpyDeviceToDevice)) != hipSuccess) fail("row nibble copy", e);
-    }
-    // 4-B descriptors + pattern dictionary under the host builder's conditions (below); the distinct patterns come from a sort + run-length encoding of the packed descriptors
-    const bool dict_pays = K.desc_dict > 0 ? true : 8LL * NUP * 50 >= NUP * (12 + 16LL * sv) + NC * (sv + 4LL);
-    if (rc == 0 && K.desc_dict != 0 && dict_pays && !pooled && NUP > 0) {
-        const int cb_bits = std::max(1, 32 - __builtin_clz((unsigned)std::max(1, T->tilen - 1)));
-        const int pid_bits = std::min(DICT_MAX_BITS, 27 - cb_bits);
-        if (pid_bits >= 1) {
-            std::vector<uint4> dict;   // (the host builder's order: shift code, then nibbles)
-            DictRanges ranges;
-            bool over = false;
-            if (dev_dict_patterns(d_packed, NUP, (size_t)1 << pid_bits, dict, &ranges, &over) != 0) rc = -3;
-            else if (!over) {
-                rc |= plan->upload(dict.data(), dict.size(), &S.udict);
-                rc |= plan->reserve((size_t)NUP, reinterpret_cast<const unsigned **>(&S.udesc));
-                if (rc == 0 && dev_compact_desc(d_packed, NUP, S.udict, ranges, cb_bits, reinterpret_cast<unsigned *>(const_cast<UDesc *>(S.udesc))) != 0) rc = -3;
-                S.cb_bits = cb_bits;
+    parallel_chunks((int64_t)map.size(), 512, [&](int64_t b, int64_t e, int) {
+        for (int64_t i = b; i < e; i++) {
+            const int4 m = map[(size_t)i];
+            for (size_t from = (size_t)m.x, to = (size_t)m.y; from < (size_t)m.x + (size_t)m.z; from++, to++) {
+                packed[to] = unit_desc12(udesc[from]);
+                if (!packed_row.empty()) packed_row[to] = URow{urow[from].x, urow[from].y};
+                if (!packed_col.empty()) packed_col[to] = ucol[from];
             }
         }
+    });
+}
+// the distinct (shift code, nibbles) patterns of the packed units as dictionary entries, ascending; false: more than cap
+bool host_unit_patterns(const std::vector<UDesc> &packed, size_t cap, std::vector<uint4> &dict)
+{
+    typedef std::pair<unsigned, unsigned long long> Pat;
+    std::vector<std::array<std::unordered_set<unsigned long long>, 8>> local((size_t)host_threads());
+    std::atomic<int> over(0);
+    parallel_chunks((int64_t)packed.size(), 1 << 16, [&](int64_t b, int64_t e, int th) {
+        if (over.load(std::memory_order_relaxed)) return;
+        auto &L = local[(size_t)th];
+        size_t have = 0;
+        for (auto &q : L) have += q.size();
+        for (int64_t u = b; u < e; u++) {
+            if (L[packed[(size_t)u].w0 >> UNIT_SHIFT_SHIFT].insert(((unsigned long long)packed[(size_t)u].n0 << 32) | packed[(size_t)u].n1).second) have++;
+            if (have > cap) { over.store(1); return; }
+        }
+    });
+    if (over.load()) return false;
+    std::vector<Pat> all;
+    for (auto &L : local) for (unsigned sc = 0; sc < 8; sc++) for (unsigned long long k : L[sc]) all.push_back(Pat(sc, k));
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    if (all.size() > cap) return false;
+    for (const Pat &p : all) dict.push_back(make_uint4((unsigned)(p.second >> 32), (unsigned)(p.second & 0xffffffffull), p.first << UNIT_SHIFT_SHIFT, 0u));
+    return true;
+}
+// the distinct (n0, n1, r0, r1) patterns of the packed pooled units, ascending; false: more than cap
+bool host_pool_patterns(const std::vector<UDesc> &packed, const std::vector<URow> &packed_row, size_t cap, std::vector<uint4> &dict)
+{
+    typedef std::array<unsigned, 4> Pat;
+    std::vector<std::set<Pat>> local((size_t)host_threads());
+    std::atomic<int> over(0);
+    parallel_chunks((int64_t)packed.size(), 1 << 16, [&](int64_t b, int64_t e, int th) {
+        if (over.load(std::memory_order_relaxed)) return;
+        std::set<Pat> &L = local[(size_t)th];
+        Pat last{{~0u, ~0u, ~0u, ~0u}};
+        for (int64_t u = b; u < e; u++) {
+            const Pat q{{packed[(size_t)u].n0, packed[(size_t)u].n1, packed_row[(size_t)u].r0, packed_row[(size_t)u].r1}};
+            if (q == last) continue;
+            last = q;
+            L.insert(q);
+            if (L.size() > cap) { over.store(1); return; }
+        }
+    });
+    if (over.load()) return false;
+    std::vector<Pat> all;
+    for (auto &L : local) all.insert(all.end(), L.begin(), L.end());
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    if (all.size() > cap) return false;
+    for (const Pat &p : all) dict.push_back(make_uint4(p[0], p[1], p[2], p[3]));
+    return true;
+}
+// the value pass on the host: the 16 values of unit j of a task go to slot j % G of the task's group j / G, interleaved per row.  D, conv: the stored type, the conversion to it
+template <class D, class Conv>
+D *host_group_values(const std::vector<int4> &map, const val_t *uval, long long NUP, long long G, Conv conv)
+{
+    D *out = zalloc<D>((size_t)NUP * 16);
+    parallel_chunks((int64_t)map.size(), 512, [&](int64_t b, int64_t e, int) {
+        for (int64_t i = b; i < e; i++) {
+            const int4 m = map[(size_t)i];
+            for (long long j = 0; j < m.z; j++) {
+                const val_t *src = uval + (m.x + j) * 16;
+                D *dst = out + (m.y + j / G * G) * 16 + (j % G);
+                for (int r = 0; r < 16; r++) dst[G * r] = conv(src[r]);
+            }
+        }
+    });
+    return out;
+}
+
+// Every task's units padded to a multiple of the value group: NUP, old_begin, the (old begin, new begin, count) map that the pack step and the value pass read, and the tasks'
+// new unit ranges.  false: more units than 32-bit unit ids address (found before anything is allocated)
+bool StreamBuilder::renumber_units(std::vector<int4> &map)
+{
+    const long long G = value_group();
+    map.resize(tasks.size());
+    old_begin.assign(tasks.size(), 0);
+    NUP = 0;
+    for (size_t i = 0; i < tasks.size(); i++) {
+        STask &k = tasks[i];
+        const long long ub = k.unit_begin, n = k.unit_end - ub, nb = NUP;
+        NUP += (n + G - 1) / G * G;
+        if (NUP > INT32_MAX) return false;
+        old_begin[i] = ub;
+        map[i] = make_int4((int)ub, (int)nb, (int)n, 0);
+        if (n > 0) { k.unit_begin = (int)nb; k.unit_end = (int)(nb + n); }
     }
-    if (rc == 0 && S.cb_bits == 0 && !pool_dict) {
-        rc |= plan->reserve((size_t)NUP, &S.udesc);
-        if (rc == 0 && NUP > 0 && (e = hipMemcpy(const_cast<UDesc *>(S.udesc), d_packed, (size_t)NUP * sizeof(UDesc), hipMemcpyDeviceToDevice)) != hipSuccess) fail("descriptor copy", e);
-    }
-    plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
-    if (rc == 0 && !pooled) { unsigned long long hist[8]; if (dev_shift_histogram(d_packed, NUP, hist) != 0) rc = -3; else plan->info[TILESPMV_INFO_DERIVED_UNITS] = (long long)hist[UNIT_DERIVED_CODE]; }
-    if (rc == 0 && !pooled) {   // the facts the lean unit kernels rest on (hip_plan.h DevStream::unit_facts): one more reduction over the packed descriptors' flags
-        long long nrowunit = 0;
-        if (dev_count_flag(d_packed, NUP, UNIT_ROWUNIT, &nrowunit) != 0) rc = -3;
-        else set_unit_facts(nrowunit, plan->info[TILESPMV_INFO_DERIVED_UNITS]);
-    }
-    // the value pass (as in host mode: k_pair_values), its source already on the device
-    rc |= reserve_values();
-    if (rc == 0) {
-        e = launch_pair_values(d_uval, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size(), narrow);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) fail("value pass", e);
-    }
-    for (void *q : {(void *)d_map, (void *)d_packed, (void *)d_prow, (void *)d_udesc, (void *)d_urow, (void *)d_uval, (void *)d_ucol}) if (q) (void)hipFree(q);
-    d_udesc = nullptr; d_urow = nullptr; d_uval = nullptr; d_ucol = nullptr;
-    S.udesc_cb = S.udesc;
-    plan->info[TILESPMV_INFO_UPLOAD_US] = up0 + (long long)(now_us() - t0);
+    return true;
 }
 
 void StreamBuilder::encode()
 {
     const unsigned long long d0 = plan->digest;
-    // ---- final HBM form of the unit streams.  Descriptors: 12 B (the duplicate of word 0 is dropped).  Values: the
-    // units of one task are stored in GROUPS of G = 16 / sizeof(value) units (2 in fp64, 4 in fp32) — the values of
-    // the G units interleaved per row, so that a lane fetches G units with one 16-byte load (row r of the group at
-    // +16 r bytes).  A task whose unit count is not a multiple of G gets padding units (zero values, never executed:
-    // unit_end excludes them) so that its last group exists.
-    // Narrow plans (fp64, choose_value_width): the values are floats or halves and G = 4, the fp32 build's unit numbering; row r of a group is 16 or 8 bytes.
     choose_value_width();
     if (rc) return;
     S.uval_narrow = narrow;
@@ -880,215 +921,137 @@ void StreamBuilder::encode()
     // the estimate that sizes the arena blocks priced the values at sizeof(val_t); a plan of halves is up to four times smaller.  (The float form keeps the estimate — an upper
     // bound — it has always had, so that its plans are placed in memory as before.)
     if (narrow == 2) plan->size_hint -= std::min(plan->size_hint, (size_t)(NU * 16 * (sv - value_bytes())));
-    const long long G = value_group();
-    auto padded = [&](long long n) { return (n + G - 1) / G * G; };
-    NUP = 0;
-    for (const STask &k : tasks) NUP += padded(k.unit_end - k.unit_begin);
-    if (NUP > INT32_MAX) {
+    std::vector<int4> map;
+    if (!renumber_units(map)) {
         fprintf(stderr, "tilespmv: shard too large for 32-bit unit ids\n");
         rc = -2;
         return;
     }
-    if (DT) { encode_device(); return; }
-    {
-        std::vector<UDesc> packed((size_t)NUP, UDesc{0u, 0u, 0u});
-        std::vector<URow> packed_row(pooled && !wide ? (size_t)NUP : 0, URow{0u, 0u});
-        std::vector<uint4> packed_col(wide ? (size_t)NUP : 0, make_uint4(0u, 0u, 0u, 0u));
-        // The value pass (the plan's largest array, permuted into groups per task) runs on the DEVICE unless this is a layout-digest build or TILESPMV_ENCODE_ON_HOST=1 asks for
-        // the host pass — which stays as the checker: TILESPMV_ENCODE_CHECK=1 runs both and compares the device's stream with the host's, byte for byte (tests/test_gpu_parity.py)
-        const bool encode_check = !plan->dry && K.encode_check;
-        const bool on_device = !plan->dry && NUP > 0 && !K.encode_on_host;
-        val_t *paired = (on_device && !encode_check) || narrow ? nullptr : zalloc<val_t>((size_t)NUP * 16);
-        float *paired_n = (on_device && !encode_check) || narrow != 1 ? nullptr : zalloc<float>((size_t)NUP * 16);   // narrow plans: the same groups, of floats
-        unsigned short *paired_h = (on_device && !encode_check) || narrow != 2 ? nullptr : zalloc<unsigned short>((size_t)NUP * 16);   // ... or of halves
-        std::vector<int4> pair_map(on_device ? tasks.size() : 0);
-        std::vector<long long> new_begin(tasks.size());
-        old_begin.assign(tasks.size(), 0);
-        for (size_t i = 0; i < tasks.size(); i++) old_begin[i] = tasks[i].unit_begin;
-        long long at = 0;
-        for (size_t i = 0; i < tasks.size(); i++) { new_begin[i] = at; at += padded(tasks[i].unit_end - tasks[i].unit_begin); }
-        parallel_chunks((int64_t)tasks.size(), 512, [&](int64_t b, int64_t e, int) {
-            for (int64_t i = b; i < e; i++) {
-                STask &k = tasks[(size_t)i];
-                const long long ub = k.unit_begin, n = k.unit_end - ub, nb = new_begin[(size_t)i];
-                for (long long j = 0; j < n; j++) {
-                    const uint4 d = h_udesc[(size_t)(ub + j)];
-                    packed[(size_t)(nb + j)] = UDesc{d.x, d.y, d.w};
-                    if (pooled && !wide) packed_row[(size_t)(nb + j)] = URow{h_urow[(size_t)(ub + j)].x, h_urow[(size_t)(ub + j)].y};
-                    if (wide) packed_col[(size_t)(nb + j)] = h_ucol[(size_t)(ub + j)];
-                    if (paired) {
-                        const val_t *src = h_uval + (ub + j) * 16;
-                        val_t *dst = paired + (nb + j / G * G) * 16 + (j % G);
-                        for (int r = 0; r < 16; r++) dst[G * r] = src[r];
-                    }
-                    if (paired_n) {
-                        const val_t *src = h_uval + (ub + j) * 16;
-                        float *dst = paired_n + (nb + j / G * G) * 16 + (j % G);
-                        for (int r = 0; r < 16; r++) dst[G * r] = (float)src[r];
-                    }
-                    if (paired_h) {
-                        const val_t *src = h_uval + (ub + j) * 16;
-                        unsigned short *dst = paired_h + (nb + j / G * G) * 16 + (j % G);
-                        for (int r = 0; r < 16; r++) dst[G * r] = value_half_bits((double)src[r]);
-                    }
-                }
-                if (on_device) pair_map[(size_t)i] = make_int4((int)ub, (int)nb, (int)n, 0);
-                if (n > 0) { k.unit_begin = (int)nb; k.unit_end = (int)(nb + n); }
-            }
-        });
-        // ---- 4-B descriptors where the units of the shard use few distinct column patterns (stencil-like shards: 4 patterns in the
-        // 5- and 7-point grids, 36 in the KKT stand-in): column block | pattern id << cb_bits | flags << 27, the patterns (the
-        // two nibble words) in a dictionary the kernels gather from.  Not for x-window plans (their descriptors hold slots).
-        S.udict = nullptr; S.cb_bits = 0;
-        std::vector<uint4> dict;   // (nibbles of rows 0-7, of rows 8-15, window shift << UNIT_SHIFT_SHIFT, 0), ascending (shift code, nibbles)
-        std::vector<unsigned> compact;
-        // ... and only where it pays: 8 bytes per unit must be at least 2 % of the streams (an entry-dominated plan with a handful of units would only buy the dictionary
-        // hop at the start of every strip: webbase-1M stand-in 13.2 -> 13.6 us); desc_dict = 1 asks for it wherever it is possible
-        const bool dict_pays = K.desc_dict > 0 ? true : 8LL * NUP * 50 >= NUP * (12 + 16LL * sv) + NC * (sv + 4LL);
-        if (K.desc_dict != 0 && dict_pays && !pooled && NUP > 0) {
-            const int cb_bits = std::max(1, 32 - __builtin_clz((unsigned)std::max(1, T->tilen - 1)));
-            const int pid_bits = std::min(DICT_MAX_BITS, 27 - cb_bits);
-            if (pid_bits >= 1) {
-                const size_t cap = (size_t)1 << pid_bits;
-                // a pattern = the unit's window shift (units that took list entries: plan_tile_ops.h; code = word 0 >> UNIT_SHIFT_SHIFT) and its 16 column nibbles
-                typedef std::pair<unsigned, unsigned long long> Pat;
-                std::vector<std::array<std::unordered_set<unsigned long long>, 8>> local((size_t)host_threads());
-                std::atomic<int> over(0);
-                parallel_chunks((int64_t)NUP, 1 << 16, [&](int64_t b, int64_t e, int th) {
-                    if (over.load(std::memory_order_relaxed)) return;
-                    auto &L = local[(size_t)th];
-                    size_t have = 0;
-                    for (auto &q : L) have += q.size();
-                    for (int64_t u = b; u < e; u++) {
-                        if (L[packed[(size_t)u].w0 >> UNIT_SHIFT_SHIFT].insert(((unsigned long long)packed[(size_t)u].n0 << 32) | packed[(size_t)u].n1).second) have++;
-                        if (have > cap) { over.store(1); return; }
-                    }
-                });
-                std::vector<Pat> all;
-                if (!over.load()) {
-                    for (auto &L : local) for (unsigned sc = 0; sc < 8; sc++) for (unsigned long long k : L[sc]) all.push_back(Pat(sc, k));
-                    std::sort(all.begin(), all.end());
-                    all.erase(std::unique(all.begin(), all.end()), all.end());
-                }
-                if (!over.load() && all.size() <= cap) {
-                    dict.resize(all.size());
-                    for (size_t i = 0; i < all.size(); i++) dict[i] = make_uint4((unsigned)(all[i].second >> 32), (unsigned)(all[i].second & 0xffffffffull), all[i].first << UNIT_SHIFT_SHIFT, 0u);
-                    compact.resize((size_t)NUP);
-                    const unsigned cbmask = (1u << cb_bits) - 1u;
-                    parallel_chunks((int64_t)NUP, 1 << 16, [&](int64_t b, int64_t e, int) {
-                        for (int64_t u = b; u < e; u++) {
-                            const UDesc &d = packed[(size_t)u];
-                            const Pat key(d.w0 >> UNIT_SHIFT_SHIFT, ((unsigned long long)d.n0 << 32) | d.n1);
-                            const unsigned pid = (unsigned)(std::lower_bound(all.begin(), all.end(), key) - all.begin());
-                            compact[(size_t)u] = (d.w0 & cbmask) | (pid << cb_bits) | ((d.w0 >> UNIT_FLAG_SHIFT) << 27);
-                        }
-                    });
-                    S.cb_bits = cb_bits;
-                }
-            }
-        }
-        // ---- pooled plans: 8-B descriptors (word 0, pattern id) + a dictionary of 16-byte patterns (the unit's 16 column nibbles and 16 row nibbles) where the shard's units use at most
-        // 2^DICT_MAX_BITS distinct ones — natural-order meshes use a few dozen (27-point hex mesh x 3 unknowns: 54; tetrahedral: 31), window-shuffled ones a hundred thousand and keep
-        // the 20-byte form.  12 of 148 bytes per unit: always worth it where it applies (desc_dict = 0 switches it off).  Patterns in ascending (n0, n1, r0, r1) order.
-        S.pdict = nullptr; pool_dict = false;
-        std::vector<uint4> pdict;
-        std::vector<uint2> compact2;
-        std::vector<unsigned> compact1;
-        if (pooled && !wide && K.desc_dict != 0 && NUP > 0) {
-            typedef std::array<unsigned, 4> Pat;
-            const size_t cap = (size_t)1 << DICT_MAX_BITS;
-            std::vector<std::set<Pat>> local((size_t)host_threads());
-            std::atomic<int> over(0);
-            parallel_chunks((int64_t)NUP, 1 << 16, [&](int64_t b, int64_t e, int th) {
-                if (over.load(std::memory_order_relaxed)) return;
-                std::set<Pat> &L = local[(size_t)th];
-                Pat last{{~0u, ~0u, ~0u, ~0u}};
-                for (int64_t u = b; u < e; u++) {
-                    const Pat q{{packed[(size_t)u].n0, packed[(size_t)u].n1, packed_row[(size_t)u].r0, packed_row[(size_t)u].r1}};
-                    if (q == last) continue;
-                    last = q;
-                    L.insert(q);
-                    if (L.size() > cap) { over.store(1); return; }
-                }
-            });
-            std::vector<Pat> all;
-            if (!over.load()) {
-                for (auto &L : local) all.insert(all.end(), L.begin(), L.end());
-                std::sort(all.begin(), all.end());
-                all.erase(std::unique(all.begin(), all.end()), all.end());
-            }
-            if (!over.load() && all.size() <= cap) {
-                pdict.resize(all.size());
-                for (size_t i = 0; i < all.size(); i++) pdict[i] = make_uint4(all[i][0], all[i][1], all[i][2], all[i][3]);
-                compact2.resize((size_t)NUP);
-                parallel_chunks((int64_t)NUP, 1 << 16, [&](int64_t b, int64_t e, int) {
-                    for (int64_t u = b; u < e; u++) {
-                        const Pat q{{packed[(size_t)u].n0, packed[(size_t)u].n1, packed_row[(size_t)u].r0, packed_row[(size_t)u].r1}};
-                        compact2[(size_t)u] = make_uint2(packed[(size_t)u].w0, (unsigned)(std::lower_bound(all.begin(), all.end(), q) - all.begin()));
-                    }
-                });
-                pool_dict = true;
-                // round 6: one 4-byte word per unit where window base, pattern id and tile-row fit it (hip_plan.h; desc_dict = 2 keeps the pairs)
-                const int bb = pool_word_base_bits((int)all.size());
-                if (K.desc_dict != 2 && POOL_STRIP_ROWS <= 4 && bb >= 4 && (long long)T->tilen * 16 <= (1ll << bb)) {
-                    compact1.resize((size_t)NUP);
-                    parallel_chunks((int64_t)NUP, 1 << 16, [&](int64_t b, int64_t e, int) {
-                        for (int64_t u = b; u < e; u++) {
-                            const uint2 c = compact2[(size_t)u];
-                            compact1[(size_t)u] = (c.x & POOL_BASE_MASK) | (c.y << bb) | ((c.x >> POOL_KR_SHIFT) << POOL_WORD_KR_SHIFT);
-                        }
-                    });
-                    S.cb_bits = bb;
-                }
-            }
-        }
-        S.urow = nullptr; S.ucol = nullptr; S.pooled = pooled ? 1 : 0;
-        if (pool_dict) {
-            if (S.cb_bits > 0) rc |= plan->upload(compact1.data(), compact1.size(), reinterpret_cast<const unsigned **>(&S.udesc));
-            else rc |= plan->upload(compact2.data(), compact2.size(), reinterpret_cast<const uint2 **>(&S.udesc));
-            rc |= plan->upload(pdict.data(), pdict.size(), &S.pdict);
-        } else if (S.cb_bits > 0) {
-            rc |= plan->upload(compact.data(), compact.size(), reinterpret_cast<const unsigned **>(&S.udesc));
-            rc |= plan->upload(dict.data(), dict.size(), &S.udict);
-        } else rc |= plan->upload(packed.data(), (size_t)NUP, &S.udesc);
-        plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
-        if (!pooled) {
-            long long nder = 0, nrowunit = 0;
-            for (long long u = 0; u < NUP; u++) { nder += (packed[(size_t)u].w0 >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE; nrowunit += ((packed[(size_t)u].w0 >> UNIT_FLAG_SHIFT) & UNIT_ROWUNIT) != 0; }
-            plan->info[TILESPMV_INFO_DERIVED_UNITS] = nder;
-            set_unit_facts(nrowunit, nder);
-        }
-        if (pooled && !wide && !pool_dict) rc |= plan->upload(packed_row.data(), (size_t)NUP, &S.urow);
-        if (wide) rc |= plan->upload(packed_col.data(), (size_t)NUP, &S.ucol);
-        if (on_device) {
-            // emitted values as they are -> a scratch buffer on the device; one workgroup per task writes them to their final place in the plan's arena
-            const double t0 = now_us();
-            void *d_src = nullptr, *d_map = nullptr;
-            const size_t src_b = (size_t)NU * 16 * sizeof(val_t), map_b = pair_map.size() * sizeof(int4);
-            rc |= reserve_values();
-            hipError_t e = hipMalloc(&d_src, std::max<size_t>(src_b, 16));
-            if (e == hipSuccess) e = hipMalloc(&d_map, std::max<size_t>(map_b, 16));
-            if (e == hipSuccess) e = hipMemcpy(d_src, h_uval, src_b, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(d_map, pair_map.data(), map_b, hipMemcpyHostToDevice);
-            if (e == hipSuccess && rc == 0) e = launch_pair_values((const val_t *)d_src, const_cast<val_t *>(S.uval), (const int4 *)d_map, (int)pair_map.size(), narrow);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (e == hipSuccess && encode_check) {
-                std::vector<unsigned char> back((size_t)NUP * 16 * (size_t)value_bytes());
-                e = hipMemcpy(back.data(), S.uval, back.size(), hipMemcpyDeviceToHost);
-                if (e == hipSuccess && memcmp(back.data(), narrow == 2 ? (const void *)paired_h : narrow ? (const void *)paired_n : (const void *)paired, back.size()) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
-                else if (e == hipSuccess && K.verbose) fprintf(stderr, "tilespmv: encode check: %lld units, device value stream == host value stream\n", NUP);
-            }
-            if (d_src) (void)hipFree(d_src);
-            if (d_map) (void)hipFree(d_map);
-            if (e != hipSuccess) { fprintf(stderr, "tilespmv: value pass on the device failed: %s\n", hipGetErrorString(e)); (void)hipGetLastError(); rc = -3; }
-            plan->info[TILESPMV_INFO_UPLOAD_US] += (long long)(now_us() - t0);
-        } else if (narrow == 2) rc |= plan->upload(paired_h, (size_t)NUP * 16, reinterpret_cast<const unsigned short **>(&S.uval));
-        else if (narrow) rc |= plan->upload(paired_n, (size_t)NUP * 16, reinterpret_cast<const float **>(&S.uval));
-        else rc |= plan->upload(paired, (size_t)NUP * 16, &S.uval);
-        free_later({paired, paired_n, paired_h, h_uval}, (size_t)NUP * 16 * sizeof(val_t));   // (h_uval was read for the last time above)
-        h_uval = nullptr;
-        S.udesc_cb = S.udesc;
+    const double t0 = now_us();
+    const long long up0 = plan->info[TILESPMV_INFO_UPLOAD_US];   // (device mode: reserve() / upload() below count their own time; the stage's total replaces it at the end, not adds to it)
+    S.udict = nullptr; S.pdict = nullptr; S.urow = nullptr; S.ucol = nullptr; S.cb_bits = 0; S.pooled = pooled ? 1 : 0; pool_dict = false;
+    const bool rows = pooled && !wide;   // the units have row nibbles beside their descriptors
+    hipError_t e = hipSuccess;
+    auto fail = [&](const char *what) { fprintf(stderr, "tilespmv: plan build, encode: %s: %s\n", what, hipGetErrorString(e)); (void)hipGetLastError(); rc = -3; };
+
+    // ---- pack: the units in the padded numbering (padding units all zero), in host arrays or in device scratch
+    std::vector<UDesc> packed; std::vector<URow> packed_row; std::vector<uint4> packed_col;
+    int4 *d_map = nullptr; UDesc *d_packed = nullptr; URow *d_prow = nullptr;
+    auto send_map = [&]() {
+        e = hipMalloc((void **)&d_map, std::max<size_t>(map.size(), 1) * sizeof(int4));
+        if (e == hipSuccess && !map.empty()) e = hipMemcpy(d_map, map.data(), map.size() * sizeof(int4), hipMemcpyHostToDevice);
+    };
+    auto scratch = [&](auto **p) {
+        const size_t bytes = (size_t)std::max<long long>(NUP, 1) * sizeof(**p) + 256;
+        e = hipMalloc((void **)p, bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, 0);
+    };
+    if (DT) {
+        send_map();
+        if (e == hipSuccess) scratch(&d_packed);
+        if (e != hipSuccess) fail("scratch for the packed descriptors");
+        if (wide) rc |= plan->reserve((size_t)NUP, &S.ucol);   // (the column-offset bytes are packed straight into the plan's arena)
+        if (rows && e == hipSuccess) { scratch(&d_prow); if (e != hipSuccess) fail("scratch for the packed row nibbles"); }   // (they end up in the arena, or in the dictionary)
+        if (rc == 0 && dev_pack_desc(d_udesc, d_urow, d_ucol, d_map, (int)map.size(), d_packed, d_prow, const_cast<uint4 *>(S.ucol)) != 0) rc = -3;
+    } else {
+        packed.assign((size_t)NUP, UDesc{0u, 0u, 0u}); packed_row.assign(rows ? (size_t)NUP : 0, URow{0u, 0u}); packed_col.assign(wide ? (size_t)NUP : 0, make_uint4(0u, 0u, 0u, 0u));
+        host_pack_units(map, h_udesc, h_urow, h_ucol, packed, packed_row, packed_col);
     }
+
+    // ---- the dictionary that applies: the distinct patterns in ascending order, unless there are more than it holds (then the 20- / 12-byte form stays)
+    std::vector<uint4> dict;
+    int cb_bits = 0; size_t cap = (size_t)1 << DICT_MAX_BITS; bool over = false;
+    if (rc == 0 && rows && K.desc_dict != 0 && NUP > 0) {
+        if (DT) { if (dev_pool_dict(d_packed, d_prow, NUP, cap, dict, &over) != 0) rc = -3; }
+        else over = !host_pool_patterns(packed, packed_row, cap, dict);
+        if (rc == 0 && !over) { pool_dict = true; S.cb_bits = pool_word_bits((int)dict.size()); }
+    } else if (rc == 0 && classic_dict_form(&cb_bits, &cap)) {
+        if (DT) { if (dev_dict_patterns(d_packed, NUP, cap, dict, &over) != 0) rc = -3; }
+        else over = !host_unit_patterns(packed, cap, dict);
+        if (rc == 0 && !over) S.cb_bits = cb_bits;
+    }
+
+    // ---- place the descriptor form that resulted, and the one stream a plan may have beside it (dictionary, row nibbles or column bytes).  Host mode computes the descriptors
+    // into a staging array and uploads them first; device mode writes them into the arena with kernels that read the uploaded dictionary, so there the side stream goes first
+    // (a wide plan's column bytes already have).  The arena order of each mode is part of the plan's placement: it stays what it is.
+    auto place = [&](auto zero, auto host_desc, auto dev_fill) {   // NUP descriptors of zero's type: host_desc(u) of every unit / dev_fill(destination in the arena)
+        typedef decltype(zero) E;
+        const E **slot = reinterpret_cast<const E **>(&S.udesc);
+        if (DT) { rc |= plan->reserve((size_t)NUP, slot); if (rc == 0 && NUP > 0 && dev_fill(const_cast<E *>(*slot)) != 0) rc = -3; return; }
+        std::vector<E> h((size_t)NUP);
+        parallel_chunks((int64_t)NUP, 1 << 16, [&](int64_t b, int64_t en, int) { for (int64_t u = b; u < en; u++) h[(size_t)u] = host_desc((size_t)u); });
+        rc |= plan->upload(h.data(), h.size(), slot);
+    };
+    auto copy = [&](auto *dst, const auto *src, const char *what) { if (rc == 0 && NUP > 0 && (e = hipMemcpy(dst, src, (size_t)NUP * sizeof(*src), hipMemcpyDeviceToDevice)) != hipSuccess) fail(what); return 0; };
+    auto place_desc = [&]() {
+        const uint4 *dp = dict.data(); const int nd = (int)dict.size(), bits = S.cb_bits;
+        auto pool_id = [&](size_t u) { return pool_pattern_id(dp, nd, make_uint4(packed[u].n0, packed[u].n1, packed_row[u].r0, packed_row[u].r1)); };
+        if (pool_dict && bits > 0) place(0u, [&](size_t u) { return pool_word(packed[u].w0, pool_id(u), bits); }, [&](unsigned *out) { return dev_pool_compact(d_packed, d_prow, NUP, S.pdict, nd, bits, out); });
+        else if (pool_dict) place(uint2{0u, 0u}, [&](size_t u) { return pool_pair(packed[u].w0, pool_id(u)); }, [&](uint2 *out) { return dev_pool_compact(d_packed, d_prow, NUP, S.pdict, nd, 0, out); });
+        else if (bits > 0) {
+            const DictRanges R = dict_ranges(dict);
+            place(0u, [&](size_t u) { const UDesc &d = packed[u]; const unsigned c = d.w0 >> UNIT_SHIFT_SHIFT; return unit_word(d.w0, unit_pattern_id(dp, R.off[c], R.off[c + 1], d.n0, d.n1), bits); },
+                  [&](unsigned *out) { return dev_compact_desc(d_packed, NUP, S.udict, R, bits, out); });
+        } else if (DT) place(UDesc{0u, 0u, 0u}, [&](size_t u) { return packed[u]; }, [&](UDesc *out) { return copy(out, d_packed, "descriptor copy"); });
+        else rc |= plan->upload(packed.data(), (size_t)NUP, &S.udesc);   // (as they are: no staging copy)
+    };
+    auto place_side = [&]() {
+        if (pool_dict) rc |= plan->upload(dict.data(), dict.size(), &S.pdict);
+        else if (S.cb_bits > 0) rc |= plan->upload(dict.data(), dict.size(), &S.udict);
+        else if (rows && DT) { rc |= plan->reserve((size_t)NUP, &S.urow); copy(const_cast<URow *>(S.urow), d_prow, "row nibble copy"); }
+        else if (rows) rc |= plan->upload(packed_row.data(), (size_t)NUP, &S.urow);
+        else if (wide && !DT) rc |= plan->upload(packed_col.data(), (size_t)NUP, &S.ucol);
+    };
+    if (rc == 0 && DT) { place_side(); place_desc(); }
+    else if (rc == 0) { place_desc(); place_side(); }
+    plan->info[TILESPMV_INFO_DESC_BYTES] = desc_bytes();
+
+    // ---- classic plans: the derived units, and the facts the lean unit kernels rest on (hip_plan.h DevStream::unit_facts)
+    if (rc == 0 && !pooled) {
+        long long nder = 0, nrowunit = 0;
+        unsigned long long hist[8];
+        if (DT) { if (dev_shift_histogram(d_packed, NUP, hist) != 0 || dev_count_flag(d_packed, NUP, UNIT_ROWUNIT, &nrowunit) != 0) rc = -3; else nder = (long long)hist[UNIT_DERIVED_CODE]; }
+        else for (const UDesc &d : packed) { nder += (d.w0 >> UNIT_SHIFT_SHIFT) == UNIT_DERIVED_CODE; nrowunit += ((d.w0 >> UNIT_FLAG_SHIFT) & UNIT_ROWUNIT) != 0; }
+        if (rc == 0) { plan->info[TILESPMV_INFO_DERIVED_UNITS] = nder; set_unit_facts(nrowunit, nder); }
+    }
+
+    // ---- the value pass (the plan's largest array, permuted into groups per task): k_pair_values through the map, from EMIT's device array or (host mode) from a staged copy
+    // of h_uval as it is.  A layout-digest build and TILESPMV_ENCODE_ON_HOST=1 take the host pass instead — which stays as the checker: TILESPMV_ENCODE_CHECK=1 runs both and
+    // compares the device's stream with the host's, byte for byte (tests/test_gpu_parity.py)
+    const bool on_device = DT || (!plan->dry && NUP > 0 && !K.encode_on_host), encode_check = on_device && !DT && K.encode_check;
+    const long long G = value_group();
+    void *grouped = nullptr;
+    if (!on_device || encode_check)
+        grouped = narrow == 2 ? (void *)host_group_values<unsigned short>(map, h_uval, NUP, G, [](val_t v) { return value_half_bits((double)v); })
+                : narrow ? (void *)host_group_values<float>(map, h_uval, NUP, G, [](val_t v) { return (float)v; }) : (void *)host_group_values<val_t>(map, h_uval, NUP, G, [](val_t v) { return v; });
+    const double tv = now_us();
+    rc |= reserve_values(on_device ? nullptr : grouped);
+    if (on_device && rc == 0) {
+        val_t *d_stage = nullptr;
+        if (!DT) {
+            const size_t bytes = (size_t)NU * 16 * sizeof(val_t);
+            e = hipMalloc((void **)&d_stage, std::max<size_t>(bytes, 16));
+            if (e == hipSuccess) send_map();
+            if (e == hipSuccess) e = hipMemcpy(d_stage, h_uval, bytes, hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess) e = launch_pair_values(DT ? d_uval : d_stage, const_cast<val_t *>(S.uval), d_map, (int)map.size(), narrow);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess && encode_check) {
+            std::vector<unsigned char> back((size_t)NUP * 16 * (size_t)value_bytes());
+            e = hipMemcpy(back.data(), S.uval, back.size(), hipMemcpyDeviceToHost);
+            if (e == hipSuccess && memcmp(back.data(), grouped, back.size()) != 0) { fprintf(stderr, "tilespmv: internal error: the device's value stream differs from the host's\n"); rc = -6; }
+            else if (e == hipSuccess && K.verbose) fprintf(stderr, "tilespmv: encode check: %lld units, device value stream == host value stream\n", NUP);
+        }
+        if (d_stage) (void)hipFree(d_stage);
+        if (e != hipSuccess) fail("value pass on the device");
+    }
+    if (DT) plan->info[TILESPMV_INFO_UPLOAD_US] = up0 + (long long)(now_us() - t0);
+    else if (on_device) plan->info[TILESPMV_INFO_UPLOAD_US] += (long long)(now_us() - tv);
+    free_later({grouped, h_uval}, (size_t)NUP * 16 * sizeof(val_t));   // (h_uval was read for the last time above)
+    h_uval = nullptr;
+    for (void *q : {(void *)d_map, (void *)d_packed, (void *)d_prow, (void *)d_udesc, (void *)d_urow, (void *)d_uval, (void *)d_ucol}) if (q) (void)hipFree(q);
+    d_udesc = nullptr; d_urow = nullptr; d_uval = nullptr; d_ucol = nullptr;
+    S.udesc_cb = S.udesc;
     if (hashing()) { Hash h; h.num((long long)(plan->digest ^ d0)); h.num(NUP); h.num(S.cb_bits); h.num(S.pooled); if (pool_dict) h.num(8); stage_done(TILESPMV_STAGE_ENCODE, h); }   // (everything this stage produces is uploaded: the running upload digest covers it)
 }
 
