@@ -968,6 +968,52 @@ int tilespmv_gmres_state_read(tilespmv_gmres *s, void *stream, tilespmv_cg_state
 int tilespmv_gmres_solve(tilespmv_gmres *s, const MAT_VAL_TYPE *d_b, MAT_VAL_TYPE *d_x, double rtol, int maxiter, int check_every, void *stream,
                          tilespmv_cg_state *out);
 
+/* ---- GMRES with the Krylov basis stored as floats in the double library (new).  An inner iteration of tilespmv_gmres_* is bound by the
+ * memory, and of the 4 k + 2 ceil(k / 8) + 6 vector elements it moves per row all but 2 ceil(k / 8) + 5 are reads of the stored basis V_0..V_j; the same basis is what limits the
+ * size of system that fits.  tilespmv_gmres_create_basis(..., TILESPMV_GMRES_BASIS_FLOAT) keeps ALL ARITHMETIC, w, x, b, the Hessenberg column and every scalar in double and
+ * stores ONLY the basis vectors as 4-byte floats (a compressed basis, as in CB-GMRES).  The solution keeps double accuracy because every open recomputes b - A x in double.
+ * begin, iterate, flush, state_read, the guards, the one-writer rule of the scalars, graph capture at cycle boundaries and the single-stream rule read exactly as above; the
+ * recurrence differs in these places only:
+ *   the stored basis    Vhat_{j+1} = fl32(w'' / h_{j+1,j}), round to nearest;  Vhat_0 = fl32(r / beta).  h_{j+1,j} and beta come from the unrounded vector, as above.
+ *   what A and M^-1 multiply   the STORED vector widened back to double, bit for bit what the next dot products read, never the unrounded one: H is then the Arnoldi matrix of the
+ *                       basis the close really uses.  The fourth kernel writes Vhat and, in the same walk, its double copy: zhat = dinv o widen(Vhat) with d_dinv; without a
+ *                       preconditioner a vector vcur = widen(Vhat), which the product reads; with a block object vcur is the input of its apply.
+ *   dots, subtraction, close   (double) w (double) Vhat_i in the dots;  w -= (double) h_i widen(Vhat_i) and u = sum_i y_i widen(Vhat_i) in double.  The scalars are rounded once
+ *                       where they multiply, as above.  The three kernels that read the whole basis take four floats with one 16-byte load against two 16-byte loads of w; the order of
+ *                       every addition depends on rows and j alone (it is not the value form's order).
+ * THE FLOOR INSIDE A CYCLE: the first basis vector is fl32(r / beta), not r / beta, so inside ONE cycle the true residual cannot fall below about eps32 = 6e-8 times the residual
+ * the cycle began with, while the recurrence's rr keeps falling.  On a fast-converging system (the 67 x 67 skew stencil with diagonal 4, restart 64) the recurrence reports
+ * sqrt(rr / bb) = 5e-16 after 40 iterations where the recomputed residual is 3e-8.  Hence
+ *   tilespmv_gmres_solve   with a float basis accepts the stopping test ONLY ON A RECOMPUTED rr: when a state read passes rr <= rtol^2 bb and the host's cycle position is not
+ *                       0, it flushes, reads again and tests again; if that test fails it carries on iterating from the fresh cycle.  No second flush at the end when the decision
+ *                       was taken on a flushed state.  MAXITER and BREAKDOWN are as above.  A caller of begin / iterate who stops on rr must do the same: flush before believing it.
+ *                       With restart <= 16 the counts equal those of the double basis on the library's test systems; at restart 64 on the fast system above 34 against 27.
+ * Per row and inner iteration the float form moves 4 k + 1 basis elements of 4 bytes and 2 ceil(k / 8) + 6 doubles (the fourth kernel writes the float vector and one double copy).
+ * WORKSPACE, one hipMalloc of tilespmv_gmres_workspace_bytes(s) =
+ *     (restart + 1) B + v D + 2 (restart + 1) Q + 2 Q + 32768 + 4 * 768 + 256   bytes, every term a multiple of 256, where
+ *     B = (rows + 16) * basis_bytes rounded up to 256     one stored basis vector
+ *     D = (rows + 16) * sizeof(MAT_VAL_TYPE) rounded up to 256, and v counts the value-type vectors: w and b, and
+ *         value basis: + 1 (zhat) with d_dinv or a block object;   float basis: + 1 (vcur) without a preconditioner, + 1 (zhat) with d_dinv, + 2 (both) with a block object
+ *     Q = 8 P rounded up to 256, P = min(cap, max(1, min(1024, ceil((rows / L) / 512)))), L = 16 / sizeof(MAT_VAL_TYPE), rows / L rounded down,
+ *         cap = 256 below rows * sizeof(MAT_VAL_TYPE) = 32 MiB, 512 below 128 MiB, 1024 beyond     the partials of one sum
+ *     32768: R;  768 each: the rotations, g, y;  256: the scalars.
+ *   GMRES(64) on 16.8 M rows: 9.0 GB with the value basis, 4.8 GB with the float one.
+ *
+ *   tilespmv_gmres_create_basis   tilespmv_gmres_create (bj = NULL) or tilespmv_gmres_create_block (d_dinv = NULL) with the bytes of a stored basis element.  basis_bytes is
+ *                                 looked at first, together with restart, before any HIP call and before the plan is looked at: 0 (TILESPMV_GMRES_BASIS_VALUE) or
+ *                                 sizeof(MAT_VAL_TYPE) gives exactly the solver of those two creates — so 4 is the identity in the float library and a caller may pass 4 to either;
+ *                                 4 (TILESPMV_GMRES_BASIS_FLOAT) in the double library gives the float basis; anything else (2; 8 in the float library) and d_dinv together with
+ *                                 bj give hipErrorInvalidValue with *s = NULL and nothing allocated.  The other refusals are those of tilespmv_gmres_create.  A 2-byte basis is
+ *                                 not offered: a unit vector of 16 M rows has entries near the fp16 subnormal range and would need a scale per vector.
+ *   tilespmv_gmres_basis_bytes    bytes per stored basis element: sizeof(MAT_VAL_TYPE) or 4 (0 for NULL).
+ *   tilespmv_gmres_workspace_bytes   the size of the one hipMalloc, the formula above, for both forms (0 for NULL). */
+#define TILESPMV_GMRES_BASIS_VALUE 0   /* the value type: exactly tilespmv_gmres_create / _create_block */
+#define TILESPMV_GMRES_BASIS_FLOAT 4
+int tilespmv_gmres_create_basis(tilespmv_gmres **s, tilespmv_plan *plan, int restart, const MAT_VAL_TYPE *d_dinv /* may be NULL */,
+                                const tilespmv_block_jacobi *bj /* may be NULL */, int basis_bytes);
+int tilespmv_gmres_basis_bytes(const tilespmv_gmres *s);
+size_t tilespmv_gmres_workspace_bytes(const tilespmv_gmres *s);
+
 const char *tilespmv_version(void);
 int tilespmv_device_count(void);    /* 0 when no HIP device is visible */
 

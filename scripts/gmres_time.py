@@ -9,7 +9,14 @@ Every workload is one GPU step: a child process of its own under its own time li
 A window = device events around one call that starts a solve and runs `cycles` full cycles of `restart` inner iterations without a convergence check inside (a: gmres(tol=0,
 maxiter=cycles * restart, check_every=maxiter); b: begin + iterate(cycles * restart)); each side's set-up, closes and opens are inside its window, divided by the inner iterations
 like the rest.  Before every window the same call runs one cycle untimed.  Beside the times: the product alone on the same plan (Plan.time) and the vector elements the fused
-solver moves per inner iteration by count, averaged over a cycle — a count, not a measurement.  No ratio is fixed in advance: the table is the result."""
+solver moves per inner iteration by count, averaged over a cycle — a count, not a measurement.  No ratio is fixed in advance: the table is the result.
+
+    python scripts/gmres_time.py --basis value,float32 [--workloads cd4096:f64,cd2048:f64,cd512:f64] [--solve-rtol 1e-10] [--out profiles/gmres_cb_ab.txt]
+
+times the fused solver against ITSELF instead, with its Krylov basis stored in each of the named forms (api.GMRES(basis=...)), on the same plan in the same
+process, alternating windows as above.  Beside each form's times: its bytes per row and inner iteration by count with the re-reads — the 4 k + 1 basis elements at the basis's own
+size, the other 2 ceil(k / 8) + 5 (+ 1 with a narrow basis) at the value type's — the rate on that count, what the first form's rate would give on the other's count, and one solve
+to --solve-rtol in each form (iterations and wall-clock ms, one host read per 8 iterations)."""
 import argparse
 import os
 import subprocess
@@ -102,6 +109,85 @@ def one(wl, a):
     return 0
 
 
+def one_basis(wl, a):
+    """One workload in this process with --basis: the fused solver in each of the named forms of its stored basis on the same plan, alternating windows; prints its lines."""
+    import torch
+    from tilespmv_amd import api
+    from tilespmv_amd.operator import SparseOperator
+    if not torch.cuda.is_available():
+        raise SystemExit("gmres_time.py needs a HIP device: a time taken anywhere else says nothing about the MI355X")
+    name, ty = wl.split(":")
+    dt = np.dtype(np.float64 if ty == "f64" else np.float32)
+    tdt = torch.float64 if ty == "f64" else torch.float32
+    t0 = time.time()
+    n, rp, ci, v = build(name)
+    op = SparseOperator(n, n, rp, ci, v.astype(dt), dtype=dt, deterministic=1, placement_tries=1)
+    b = torch.zeros(n + 16, dtype=tdt, device="cuda")[:n]
+    b.copy_(torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, n).astype(dt)))
+    x = torch.zeros(n + 16, dtype=tdt, device="cuda")[:n]
+    y = torch.zeros(n + 16, dtype=tdt, device="cuda")[:n]
+    st = torch.cuda.current_stream().cuda_stream
+    m = a.restart
+    forms = a.basis.split(",")
+    solvers = {f: api.GMRES(op.A, m, basis=f) for f in forms}
+    a_ms = min(op.A.time(x.data_ptr(), y.data_ptr(), st, warmup=20, reps=100) for _ in range(3))
+    prod = a_ms * 1e-3
+
+    def window(form, iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        x.zero_()
+        solvers[form].begin(b.data_ptr(), x.data_ptr(), st)
+        solvers[form].iterate(x.data_ptr(), iters, st)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / iters, x.clone()
+
+    t = {f: [] for f in forms}
+    xs = {}
+    for r in range(a.rounds):
+        for f in forms:
+            window(f, m)
+            sec, xs[f] = window(f, a.cycles * m)
+            t[f].append(sec)
+    ks = np.arange(1, m + 1)
+    groups = (ks + 7) // 8
+    # bytes per row and inner iteration with the re-reads, mean over a cycle: every element of the value type, or the 4 k + 1 basis elements at the basis's own size
+    # (a narrow basis: one more, the value-type copy that k_gm_next writes beside the stored vector)
+    count = {f: float(np.mean((4 * ks + 1) * solvers[f].basis_bytes + (2 * groups + 5 + (solvers[f].basis_bytes != dt.itemsize)) * dt.itemsize)) for f in forms}
+    print("# %s" % torch.cuda.get_device_name(0))
+    print("%s %s restart %d: n = %d, nnz = %d, entry_ordered %d, set-up %.0f s" % (name, ty, m, n, len(ci), op.A.info()["entry_ordered"], time.time() - t0))
+    print("  product alone (Plan.time)             %.4f ms" % a_ms)
+    med = {}
+    for f in forms:
+        med[f] = float(np.median(t[f]))
+        print("  basis %-8s %d bytes per element, workspace %.1f MB, %.1f bytes per row and iteration by count (%.1f MB)   ms per iteration  %s   median %.4f  spread %.4f   rate on that count %.2f TB/s"
+              % (f, solvers[f].basis_bytes, solvers[f].workspace_bytes / 1e6, count[f], count[f] * n / 1e6, "  ".join("%.4f" % (s * 1e3) for s in t[f]), med[f] * 1e3,
+                 (max(t[f]) - min(t[f])) * 1e3, count[f] * n / max(med[f] - prod, 1e-12) / 1e12))
+    for f in forms[1:]:
+        f0 = forms[0]
+        predicted = (count[f0] * n / max(med[f0] - prod, 1e-12))      # the first form's achieved rate, applied to this form's count
+        print("  %s / %s (medians) %.3f;  by the byte counts at %s's rate, with the product: %.3f;  |x_%s - x_%s| / |x_%s| after %d iterations = %.3g"
+              % (f0, f, med[f0] / med[f], f0, med[f0] / (count[f] * n / predicted + prod), f, f0, f0, a.cycles * m,
+                 float(torch.linalg.vector_norm(xs[f] - xs[f0]) / torch.linalg.vector_norm(xs[f0]))))
+    if a.solve_rtol > 0:
+        for f in forms:
+            x.zero_()
+            solvers[f].solve(b.data_ptr(), x.data_ptr(), rtol=a.solve_rtol, maxiter=m, check_every=m, stream=st)      # (untimed: the first call)
+            x.zero_()
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            s = solvers[f].solve(b.data_ptr(), x.data_ptr(), rtol=a.solve_rtol, maxiter=a.solve_maxiter, check_every=8, stream=st)
+            torch.cuda.synchronize()
+            print("  solve to rtol %.0e, basis %-8s %d iterations, %s, sqrt(rr / bb) %.3g, %.1f ms" % (a.solve_rtol, f, s["iterations"], s["status_name"], s["relative_residual"],
+                                                                                                     (time.perf_counter() - w0) * 1e3), flush=True)
+    for s in solvers.values():
+        s.close()
+    op.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="cd4096:f64,cd4096:f32,cd512:f64")
@@ -110,17 +196,28 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=600)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--basis", default=None, help="e.g. value,float32: time the fused solver in these forms of its stored basis against each other instead of a against b")
+    ap.add_argument("--solve-rtol", type=float, default=1e-10, help="with --basis: also one solve to this tolerance in each form (0: none)")
+    ap.add_argument("--solve-maxiter", type=int, default=3000)
     ap.add_argument("--one", default=None, help="(internal) run this one workload in this process")
     a = ap.parse_args()
     if a.one:
-        return one(a.one, a)
-    lines = ["# seconds per GMRES(%d) inner iteration, fused solver (b: tilespmv_gmres_iterate) vs torch loop (a: tilespmv_amd.operator.gmres), same deterministic plan, alternating a b a b" % a.restart,
-             "# %d rounds, %d full cycles per window after one warm-up cycle, device events around each window; one process per workload" % (a.rounds, a.cycles)]
+        return one_basis(a.one, a) if a.basis else one(a.one, a)
+    if a.basis:
+        if a.workloads == ap.get_default("workloads"):
+            a.workloads = "cd4096:f64,cd2048:f64,cd512:f64"
+        lines = ["# seconds per GMRES(%d) inner iteration of the fused solver (tilespmv_gmres_iterate) with its basis stored as: %s — same deterministic plan, same process, alternating windows"
+                 % (a.restart, a.basis)]
+    else:
+        lines = ["# seconds per GMRES(%d) inner iteration, fused solver (b: tilespmv_gmres_iterate) vs torch loop (a: tilespmv_amd.operator.gmres), same deterministic plan, alternating a b a b" % a.restart]
+    lines.append("# %d rounds, %d full cycles per window after one warm-up cycle, device events around each window; one process per workload" % (a.rounds, a.cycles))
     print("\n".join(lines), flush=True)
     rc = 0
     for wl in a.workloads.split(","):
         cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--one", wl, "--restart", str(a.restart), "--cycles", str(a.cycles),
                "--rounds", str(a.rounds)]
+        if a.basis:
+            cmd += ["--basis", a.basis, "--solve-rtol", str(a.solve_rtol), "--solve-maxiter", str(a.solve_maxiter)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         print(r.stdout, flush=True)
         lines += ["", r.stdout.rstrip()]

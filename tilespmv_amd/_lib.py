@@ -216,6 +216,12 @@ def load(dtype=np.float64):
     lib.tilespmv_gmres_create_block.restype = C.c_int
     lib.tilespmv_gmres_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tilespmv_gmres_flush.restype = C.c_int
+    lib.tilespmv_gmres_create_basis.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.tilespmv_gmres_create_basis.restype = C.c_int
+    lib.tilespmv_gmres_basis_bytes.argtypes = [C.c_void_p]
+    lib.tilespmv_gmres_basis_bytes.restype = C.c_int
+    lib.tilespmv_gmres_workspace_bytes.argtypes = [C.c_void_p]
+    lib.tilespmv_gmres_workspace_bytes.restype = C.c_size_t
     lib.tilespmv_device_count.restype = C.c_int
     lib.tilespmv_plan_options_layout.restype = C.c_char_p
     lib.tilespmv_version.restype = C.c_char_p
@@ -252,4 +258,4 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_block_jacobi_create", "tilespmv_block_jacobi_destroy", "tilespmv_block_jacobi_update", "tilespmv_block_jacobi_apply", "tilespmv_block_jacobi_apply_dot",
                     "tilespmv_block_jacobi_info", "tilespmv_cg_create_block", "tilespmv_bicgstab_create_block",
                     "tilespmv_gmres_create", "tilespmv_gmres_create_block", "tilespmv_gmres_destroy", "tilespmv_gmres_begin", "tilespmv_gmres_iterate", "tilespmv_gmres_flush",
-                    "tilespmv_gmres_state_read", "tilespmv_gmres_solve"]
+                    "tilespmv_gmres_state_read", "tilespmv_gmres_solve", "tilespmv_gmres_create_basis", "tilespmv_gmres_basis_bytes", "tilespmv_gmres_workspace_bytes"]

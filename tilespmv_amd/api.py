@@ -704,20 +704,34 @@ class GMRES(_IterativeSolver):
     ``x`` HOLDS THE ITERATE ONLY AFTER A CLOSE: at the end of every ``restart``-th iteration of a cycle, after ``flush`` and after ``solve``; ``rr`` is then a recomputed
     ``|b - A x|^2``, inside a cycle the recurrence's estimate of it.  A captured ``iterate(count)`` replays correctly when captured at a cycle boundary with ``count`` a multiple of
     ``restart``.  Raises ``ValueError`` where the library returns hipErrorInvalidValue (``restart`` out of range, a shard, a non-square plan, a misaligned vector, a block
-    preconditioner of another row count) and for ``block`` together with ``d_dinv``."""
+    preconditioner of another row count, ``basis`` bytes the library does not store) and for ``block`` together with ``d_dinv``.
+
+    ``basis``: how the Krylov basis is stored (``tilespmv_gmres_create_basis``).  ``None``: the plain creates.  ``"value"`` or ``0``: the value type, the same
+    solver.  ``"float32"`` or ``4``: 4-byte floats — in the fp64 library the compressed basis (all arithmetic stays double; about half the bytes per iteration and half the
+    workspace), in the fp32 library the identity.  With the compressed basis the true residual cannot fall below about 6e-8 x the residual a cycle began with INSIDE that cycle
+    while ``rr`` keeps falling: ``solve`` accepts convergence only on a recomputed ``rr`` (it flushes and tests again); a caller of ``iterate`` who stops on ``rr`` flushes first.
+    ``basis_bytes``: bytes per stored basis element; ``workspace_bytes``: the size of the solver's one allocation."""
 
     _prefix = "tilespmv_gmres"
-    _hint = "1 <= restart <= 64; the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
+    _hint = "1 <= restart <= 64; the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows; basis bytes 0, 4 or the value type's"
+    _BASIS = {"value": 0, "float32": 4}
 
-    def __init__(self, plan, restart=30, d_dinv=None, block=None):
+    def __init__(self, plan, restart=30, d_dinv=None, block=None, basis=None):
         self.lib, self.plan, self.block, self.restart = plan.lib, plan, block, int(restart)
         h = C.c_void_p()
         bh = _block_handle(block, d_dinv, plan.lib)
-        if bh is not None:
+        if basis is not None:
+            if isinstance(basis, str) and basis not in self._BASIS:
+                raise ValueError("basis must be None, 'value', 'float32' or a number of bytes, not %r" % (basis,))
+            nbytes = self._BASIS[basis] if isinstance(basis, str) else int(basis)
+            self._check(self.lib.tilespmv_gmres_create_basis(C.byref(h), plan.h, self.restart, C.c_void_p(d_dinv or None), bh, nbytes), "tilespmv_gmres_create_basis")
+        elif bh is not None:
             self._check(self.lib.tilespmv_gmres_create_block(C.byref(h), plan.h, self.restart, bh), "tilespmv_gmres_create_block")
         else:
             self._check(self.lib.tilespmv_gmres_create(C.byref(h), plan.h, self.restart, C.c_void_p(d_dinv or None)), "tilespmv_gmres_create")
         self.h = h
+        self.basis_bytes = self.lib.tilespmv_gmres_basis_bytes(h)
+        self.workspace_bytes = self.lib.tilespmv_gmres_workspace_bytes(h)
 
     def flush(self, d_x, stream=0):
         """Close the cycle early and open the next: ``d_x`` is the current iterate and ``rr`` its recomputed residual; asynchronous, capturable."""

@@ -232,8 +232,13 @@ struct RrBbTest {
 };
 // *_solve of a single system behind the handle's null check.  begin(), read() (the solver's state_read into `out`) and iterate(count) are the solver's own entry points; d_x has
 // x_len elements.  Refusals come before any launch; one read, hence one synchronisation, per check_every iterations; the last batch is clipped to maxiter.
-template <class Test, class State, class Begin, class Read, class Iterate>
-int solve_loop(State *out, val_t *d_x, long long x_len, double rtol, int maxiter, int check_every, hipStream_t st, Begin begin, Read read, Iterate iterate)
+// confirm(accepted) is asked when a read passes the test, before CONVERGED is declared: a solver whose recurrence may run ahead of the true residual (GMRES with a narrow basis)
+// recomputes it there, fills `out` again and clears `accepted` to carry on.  The default accepts at once: the other solvers' loops are what they were.
+struct AcceptAtOnce {
+    int operator()(bool &) const { return 0; }
+};
+template <class Test, class State, class Begin, class Read, class Iterate, class Confirm = AcceptAtOnce>
+int solve_loop(State *out, val_t *d_x, long long x_len, double rtol, int maxiter, int check_every, hipStream_t st, Begin begin, Read read, Iterate iterate, Confirm confirm = Confirm())
 {
     if (!out || out->size < sizeof(State) || maxiter < 0) return (int)hipErrorInvalidValue;
     if (check_every < 1) check_every = 1;
@@ -250,7 +255,12 @@ int solve_loop(State *out, val_t *d_x, long long x_len, double rtol, int maxiter
             out->status = TILESPMV_CG_CONVERGED;
             return (int)hipStreamSynchronize(st);
         }
-        if (Test::residual(*out) <= rtol * rtol * Test::scale(*out)) { out->status = TILESPMV_CG_CONVERGED; return 0; }
+        if (Test::residual(*out) <= rtol * rtol * Test::scale(*out)) {
+            bool accepted = true;
+            rc = confirm(accepted);
+            if (rc) return rc;
+            if (accepted) { out->status = TILESPMV_CG_CONVERGED; return 0; }
+        }
         if (out->iterations >= maxiter) { out->status = TILESPMV_CG_MAXITER; return 0; }
         rc = iterate(std::min(check_every, maxiter - out->iterations));
         if (rc) return rc;

@@ -275,17 +275,19 @@ class SparseOperator:
         x, s = self._solve(lambda d: api.BiCGStab(self.A, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
         return x, _info(s)
 
-    def gmres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, restart=30, dinv=None, stream=None, precond=None):
+    def gmres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, restart=30, dinv=None, stream=None, precond=None, basis=None):
         """A x = b for a square A that need not be symmetric, by restarted GMRES in the library (``api.GMRES`` over the plan of A) — one product and four fused
         kernels per iteration, every scalar on the device, one host synchronisation per ``check_every`` iterations; the solver for what ``bicgstab`` breaks down or stagnates on
         (convection-dominated, nearly skew-symmetric).  ``b``: a contiguous torch CUDA vector of ``rows`` elements; ``restart``: 1 .. 64 iterations per cycle; ``dinv``: the inverse
         diagonal as a CUDA vector (Jacobi, applied from the right), None = unpreconditioned; ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv``.
         Stops at ``sqrt(rr / bb) <= rtol``, after ``maxiter`` iterations (default ``2 * rows``) or at a breakdown.  Returns ``(x, info)`` with ``info = {"iterations", "residual",
-        "relative_residual", "converged", "status"}`` (``residual``: ``|b - A x|`` recomputed for the returned x)."""
+        "relative_residual", "converged", "status"}`` (``residual``: ``|b - A x|`` recomputed for the returned x).  ``basis``: None, ``"value"``, ``"float32"``, 4 or 0 — how the
+        Krylov basis is stored (``api.GMRES``): ``"float32"`` on an fp64 operator halves the bytes of the basis, all arithmetic stays double and convergence is
+        accepted on a recomputed residual only."""
         self._square("gmres")
         if precond is not None and _is_tensor(b) and b.dim() == 2:
             raise ValueError("precond (block Jacobi) applies to a 1-D b only")
-        x, s = self._solve(lambda d: api.GMRES(self.A, restart, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
+        x, s = self._solve(lambda d: api.GMRES(self.A, restart, d, block=precond, basis=basis), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
         return x, _info(s)
 
     def minres(self, b, x0=None, rtol=1e-10, maxiter=None, check_every=8, minv=None, stream=None):
@@ -356,23 +358,31 @@ def bicgstab(op, b, x0=None, tol=1e-10, maxiter=None, dinv=None, check_every=1):
     return x, info
 
 
-def gmres(op, b, x0=None, tol=1e-10, maxiter=None, restart=30, dinv=None, check_every=1):
+def gmres(op, b, x0=None, tol=1e-10, maxiter=None, restart=30, dinv=None, check_every=1, basis=None):
     """``A x = b`` for a square operator by right-preconditioned restarted GMRES as a loop of torch operations: the recurrences of ``SparseOperator.gmres`` (DESIGN.md §3.13:
     classical Gram-Schmidt applied twice, the basis a 2-D tensor, ``V @ w`` for the dot products, Givens rotations on the host), without its guards — what the fused solver is
     measured against and a second opinion in tests.  ``b``: a torch CUDA vector of ``rows`` elements; ``dinv``: None or the inverse diagonal.  Stops when the recurrence's residual
     estimate is ``<= tol * |b|`` (checked every ``check_every`` iterations and at the end of a cycle) or after ``maxiter`` iterations (default ``2 * rows``).  Returns ``(x, info)``
-    with ``info = {"iterations", "residual", "relative_residual", "converged"}`` (``residual``: a recomputed ``|b - A x|``)."""
+    with ``info = {"iterations", "residual", "relative_residual", "converged"}`` (``residual``: a recomputed ``|b - A x|``).  ``basis``: as for ``SparseOperator.gmres``;
+    with ``"float32"`` (or 4) the basis is a float32 tensor, a store rounds to nearest and every use — the product, the dots, the subtraction, the close — reads it widened back
+    to ``b``'s type.  Convergence is declared at the top of a cycle, on a recomputed residual, in either form."""
     import torch
     rows, cols = op.shape
     if rows != cols:
         raise ValueError("gmres needs a square operator; this one is %d x %d" % (rows, cols))
+    if basis not in (None, "value", "float32", 0, 4):
+        raise ValueError("basis must be None, 'value', 'float32', 0 or 4, not %r" % (basis,))
+    narrow = basis in ("float32", 4) and b.dtype != torch.float32
+
+    def wide(t):
+        return t.to(b.dtype) if narrow else t
     if b.numel() != rows:
         raise ValueError("b must have %d elements" % rows)
     maxiter = 2 * rows if maxiter is None else maxiter
     m = int(restart)
     x = torch.zeros(rows, dtype=b.dtype, device=b.device) if x0 is None else x0.clone()
     norm_b = float(torch.linalg.vector_norm(b))
-    V = torch.zeros((m + 1, rows), dtype=b.dtype, device=b.device)
+    V = torch.zeros((m + 1, rows), dtype=torch.float32 if narrow else b.dtype, device=b.device)
     w = torch.empty(rows + 16, dtype=b.dtype, device=b.device)[:rows]
     it, converged = 0, norm_b == 0.0
     if converged:
@@ -389,11 +399,12 @@ def gmres(op, b, x0=None, tol=1e-10, maxiter=None, restart=30, dinv=None, check_
         g[0] = beta
         k = 0
         while k < m and it < maxiter:
-            op.matvec(V[k] if dinv is None else dinv * V[k], w)
-            h1 = V[:k + 1] @ w
-            w -= h1 @ V[:k + 1]
-            h2 = V[:k + 1] @ w
-            w -= h2 @ V[:k + 1]
+            Vk = wide(V[:k + 1])
+            op.matvec(Vk[k] if dinv is None else dinv * Vk[k], w)
+            h1 = Vk @ w
+            w -= h1 @ Vk
+            h2 = Vk @ w
+            w -= h2 @ Vk
             hh = float(torch.linalg.vector_norm(w))
             col = (h1 + h2).double().cpu().numpy()
             for i in range(k):
@@ -410,7 +421,7 @@ def gmres(op, b, x0=None, tol=1e-10, maxiter=None, restart=30, dinv=None, check_
             if (it % check_every == 0 or it == maxiter) and abs(g[k]) <= tol * norm_b:
                 break
         y = np.linalg.solve(np.triu(R[:k, :k]), g[:k])
-        u = torch.from_numpy(y).to(device=b.device, dtype=b.dtype) @ V[:k]
+        u = torch.from_numpy(y).to(device=b.device, dtype=b.dtype) @ wide(V[:k])
         x += u if dinv is None else dinv * u
     res = float(torch.linalg.vector_norm(b - op.matvec(x)))
     converged = converged or res <= tol * norm_b
