@@ -892,6 +892,57 @@ int tilespmv_block_jacobi_info(const tilespmv_block_jacobi *bj, void *stream, lo
 int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, const tilespmv_block_jacobi *bj);
 int tilespmv_bicgstab_create_block(tilespmv_bicgstab **s, tilespmv_plan *plan, const tilespmv_block_jacobi *bj);
 
+/* ---- A factorised sparse approximate inverse (FSAI) preconditioner for tilespmv_cg_* (new): for symmetric positive definite systems whose
+ * difficulty is not inside a row (the inverse diagonal) or a node (block Jacobi).  G is sparse and LOWER TRIANGULAR with G A G^T ~ I (Kolotilina-Yeremin); the preconditioner is
+ * M^-1 = G^T G, positive definite whatever A is, and applying it is two sparse products — a plan of G and a transposed plan of G, both held by the object.
+ *
+ * Input: a square CSR in DEVICE memory whose rows hold strictly ascending columns (hence no repeated entries) and every one of which stores its diagonal.  Only entries with
+ * column <= row are ever read: the object is well defined for any such input and is the FSAI of the symmetric matrix whose lower triangle that is.
+ * Pattern: row i of G holds the stored columns <= i of row i of A; where there are more than TILESPMV_FSAI_MAX_ROW of them, the TILESPMV_FSAI_MAX_ROW largest — those nearest the
+ * diagonal, the diagonal among them (such rows are counted: truncated_rows).
+ * Values: with P the m pattern columns of row i, S = A[P, P] and S y = e_m, row i of G is y / sqrt(y_m): row i of G A G^T has a unit diagonal.  S is assembled and factorised
+ * (Cholesky) in double in both builds, one group of lanes per row, and the row is rounded to the value type once; every sum has a fixed order and no value is added by an atomic:
+ * two runs give the same bytes.  A row whose factorisation meets a pivot that is not > 0 or not finite FALLS BACK to point Jacobi: zeros, with 1 / sqrt(a_ii) on the diagonal
+ * where a_ii > 0 and 1 otherwise (counted: fallback_rows, rewritten by every update).
+ *
+ *   tilespmv_fsai_create     checks the input with one kernel (hipErrorInvalidValue and nothing built where it does not hold, or for a NULL argument, rows <= 0, nnz <= 0), builds
+ *                            the pattern (a count, a scan, a fill), the values, and the two plans by tilespmv_plan_create_from_device_csr with TILESPMV_CREATE_VALUE_MAP (and
+ *                            TILESPMV_CREATE_TRANSPOSE for the second); `opts` (may be NULL: the defaults) goes to both.  Allocates and synchronises.  Other return codes: a
+ *                            hipError_t value, or the negative code of the plan builder.
+ *   tilespmv_fsai_update     new values of A on the SAME pattern (the caller's promise, as for tilespmv_plan_update_values): the value kernel into the same array of G's values,
+ *                            then tilespmv_plan_update_values on both plans.  Asynchronous on `stream`; no allocation, no host copy, no synchronisation: capturable into a hipGraph.
+ *                            The object then holds the bytes a fresh create from those values holds.
+ *   tilespmv_fsai_apply      z = G^T (G r): two tilespmv_plan_spmv calls, t = G r in a vector the object owns.  d_r and d_z are distinct device vectors of `rows` elements, 16-byte
+ *                            aligned (hipErrorInvalidValue otherwise, and nothing is launched); nothing behind element rows - 1 of either is touched.  Asynchronous, capturable.
+ *   tilespmv_fsai_apply_dot  the same, and d_partials[w] = partial sum w of r.z (double; info's dot_partials of them, at most TILESPMV_FSAI_MAX_PARTIALS: their number and the order
+ *                            of every addition are fixed by `rows` alone) in one more streaming pass — r.z itself, not |t|^2.
+ *   tilespmv_fsai_factor_csr G as a device CSR, BORROWED until destroy (row pointer of rows + 1, column indices and values of *nnz entries; the values change with every update).
+ *   tilespmv_fsai_info       synchronises `stream`; out[TILESPMV_FSAI_INFO_*].
+ *   tilespmv_cg_create_fsai  the EXISTING solver type; begin, iterate, state_read, solve and destroy are the entry points of tilespmv_cg_*.  f is borrowed until destroy and its values
+ *                            may change between solves; hipErrorInvalidValue (nothing allocated) for a NULL f or one whose rows are not the plan's.  z is a stored vector, as with
+ *                            block Jacobi.  One iteration: the product, the two products of G, and four launches (k_cg_dot, k_cg_update, the r.z partials, p = z + beta p).
+ * The object and its two plans run on ONE stream at a time (the single-stream rule of tilespmv_plan_spmv).  Out of scope: larger patterns, dropping, the nonsymmetric two-factor
+ * form, multi-RHS CG.  All but destroy return a hipError_t value unless said otherwise (0 = success). */
+typedef struct tilespmv_fsai tilespmv_fsai;
+#define TILESPMV_FSAI_MAX_ROW 64
+#define TILESPMV_FSAI_MAX_PARTIALS 1024
+enum {
+    TILESPMV_FSAI_INFO_ROWS = 0, TILESPMV_FSAI_INFO_NNZ = 1 /* of G */, TILESPMV_FSAI_INFO_LONGEST_ROW = 2 /* of G */,
+    TILESPMV_FSAI_INFO_TRUNCATED_ROWS = 3,   /* rows of A with more than TILESPMV_FSAI_MAX_ROW stored columns <= the row */
+    TILESPMV_FSAI_INFO_FALLBACK_ROWS = 4,    /* rows the last create or update replaced by point Jacobi */
+    TILESPMV_FSAI_INFO_DEVICE_BYTES = 5 /* both plans and their value maps included */, TILESPMV_FSAI_INFO_DOT_PARTIALS = 6,
+    TILESPMV_FSAI_INFO_COUNT = 7
+};
+int tilespmv_fsai_create(tilespmv_fsai **f, int rows, MAT_PTR_TYPE nnz, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal,
+                         const tilespmv_plan_options *opts /* may be NULL */, void *stream);
+void tilespmv_fsai_destroy(tilespmv_fsai *f);
+int tilespmv_fsai_update(tilespmv_fsai *f, const MAT_PTR_TYPE *d_csrRowPtr, const int *d_csrColIdx, const MAT_VAL_TYPE *d_csrVal, void *stream);
+int tilespmv_fsai_apply(tilespmv_fsai *f, const MAT_VAL_TYPE *d_r, MAT_VAL_TYPE *d_z, void *stream);   /* z = G^T (G r), z != r */
+int tilespmv_fsai_apply_dot(tilespmv_fsai *f, const MAT_VAL_TYPE *d_r, MAT_VAL_TYPE *d_z, double *d_partials, void *stream);
+int tilespmv_fsai_factor_csr(const tilespmv_fsai *f, const MAT_PTR_TYPE **d_rowPtr, const int **d_colIdx, const MAT_VAL_TYPE **d_val, MAT_PTR_TYPE *nnz);   /* G, borrowed */
+int tilespmv_fsai_info(const tilespmv_fsai *f, void *stream, long long *out /* [TILESPMV_FSAI_INFO_COUNT] */);
+int tilespmv_cg_create_fsai(tilespmv_cg **cg, tilespmv_plan *plan, tilespmv_fsai *f);
+
 /* ---- Nonsymmetric systems that BiCGStab does not solve: restarted GMRES around a resident plan (new).  A x = b for a square A that need be
  * neither symmetric nor definite, by GMRES(m), m = restart <= TILESPMV_GMRES_MAX_RESTART, right-preconditioned by M^-1 = diag(d_dinv) (tilespmv_csr_diagonal_device(..., invert = 1)
  * makes it; d_dinv = NULL: M = I) or by a block-Jacobi object.  One product per iteration, a residual norm that never increases inside a cycle, no breakdown but the lucky one and

@@ -24,6 +24,8 @@ INFO_NAMES = ["device_bytes", "stream_bytes", "nnz", "rows", "tiles", "coo_mode"
 
 BJ_INFO_NAMES = ["rows", "block_size", "blocks", "singular_blocks", "device_bytes", "dot_partials"]   # TILESPMV_BJ_INFO_* of include/tilespmv.h
 
+FSAI_INFO_NAMES = ["rows", "nnz", "longest_row", "truncated_rows", "fallback_rows", "device_bytes", "dot_partials"]   # TILESPMV_FSAI_INFO_* of include/tilespmv.h
+
 KNOB_DEFAULT = -1
 # tuning knobs of tilespmv_plan_options (include/tilespmv.h), in struct order after `autotune`
 KNOB_NAMES = ["entry_mode", "entry_ordered", "strip_cost", "split_above", "split_cap", "xcd_remap", "xcd_chunk", "csr_split", "fix_inline",
@@ -212,6 +214,22 @@ def load(dtype=np.float64):
     lib.tilespmv_cg_create_block.restype = C.c_int
     lib.tilespmv_bicgstab_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
     lib.tilespmv_bicgstab_create_block.restype = C.c_int
+    lib.tilespmv_fsai_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PlanOptions), C.c_void_p]
+    lib.tilespmv_fsai_create.restype = C.c_int
+    lib.tilespmv_fsai_destroy.argtypes = [C.c_void_p]
+    lib.tilespmv_fsai_destroy.restype = None
+    lib.tilespmv_fsai_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_fsai_update.restype = C.c_int
+    lib.tilespmv_fsai_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_fsai_apply.restype = C.c_int
+    lib.tilespmv_fsai_apply_dot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tilespmv_fsai_apply_dot.restype = C.c_int
+    lib.tilespmv_fsai_factor_csr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I]
+    lib.tilespmv_fsai_factor_csr.restype = C.c_int
+    lib.tilespmv_fsai_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.tilespmv_fsai_info.restype = C.c_int
+    lib.tilespmv_cg_create_fsai.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    lib.tilespmv_cg_create_fsai.restype = C.c_int
     lib.tilespmv_gmres_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
     lib.tilespmv_gmres_create_block.restype = C.c_int
     lib.tilespmv_gmres_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -257,5 +275,7 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_csr_abs_diagonal_device",
                     "tilespmv_block_jacobi_create", "tilespmv_block_jacobi_destroy", "tilespmv_block_jacobi_update", "tilespmv_block_jacobi_apply", "tilespmv_block_jacobi_apply_dot",
                     "tilespmv_block_jacobi_info", "tilespmv_cg_create_block", "tilespmv_bicgstab_create_block",
+                    "tilespmv_fsai_create", "tilespmv_fsai_destroy", "tilespmv_fsai_update", "tilespmv_fsai_apply", "tilespmv_fsai_apply_dot", "tilespmv_fsai_factor_csr",
+                    "tilespmv_fsai_info", "tilespmv_cg_create_fsai",
                     "tilespmv_gmres_create", "tilespmv_gmres_create_block", "tilespmv_gmres_destroy", "tilespmv_gmres_begin", "tilespmv_gmres_iterate", "tilespmv_gmres_flush",
                     "tilespmv_gmres_state_read", "tilespmv_gmres_solve", "tilespmv_gmres_create_basis", "tilespmv_gmres_basis_bytes", "tilespmv_gmres_workspace_bytes"]

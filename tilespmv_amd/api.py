@@ -506,6 +506,70 @@ class BlockJacobi(_Solver):
         return dict(zip(_lib.BJ_INFO_NAMES, [int(v) for v in out]))
 
 
+class FSAI(_Solver):
+    """``tilespmv_fsai``: a factorised sparse approximate inverse of a symmetric positive definite A — a sparse lower-triangular G on the pattern of A's lower triangle with
+    G A G^T ~ I, applied as z = G^T (G r) by two plans the object holds (include/tilespmv.h) — the ``fsai`` of ``CG``.  ``d_rp`` / ``d_ci`` (int32) / ``d_v`` are
+    device ADDRESSES of a square CSR with strictly ascending columns in every row and a stored diagonal; only its lower triangle is read.  ``knobs``: the plan options handed to
+    both plans (``deterministic=1, placement_tries=1, ...``; none: the defaults).  Vectors have ``rows`` elements and are 16-byte aligned.  Raises ``ValueError`` where the library
+    returns hipErrorInvalidValue."""
+
+    _destroy = "tilespmv_fsai_destroy"
+    _hint = "a square CSR with strictly ascending columns and a stored diagonal in every row; vectors distinct and 16-byte aligned"
+
+    def __init__(self, rows, nnz, d_rp, d_ci, d_v, dtype=np.float64, stream=0, **knobs):
+        self.lib = _lib.load(dtype)
+        self.rows, self.dtype = int(rows), np.dtype(dtype)
+        opts = _lib.PlanOptions(**knobs) if knobs else None
+        h = C.c_void_p()
+        self._check(self.lib.tilespmv_fsai_create(C.byref(h), self.rows, int(nnz), C.c_void_p(d_rp), C.c_void_p(d_ci), C.c_void_p(d_v), C.byref(opts) if opts is not None else None,
+                                                  C.c_void_p(stream)), "tilespmv_fsai_create")
+        self.h = h
+
+    def update(self, d_rp, d_ci, d_v, stream=0):
+        """New values of A on the same pattern: G's values and both plans rewritten in place; asynchronous, capturable.  After ``Plan.update_values``: this call."""
+        self._check(self.lib.tilespmv_fsai_update(self.h, C.c_void_p(d_rp), C.c_void_p(d_ci), C.c_void_p(d_v), C.c_void_p(stream)), "tilespmv_fsai_update")
+
+    def apply(self, d_r, d_z, stream=0, d_partials=None):
+        """z = G^T (G r) (z and r distinct); asynchronous, capturable.  ``d_partials``: also the ``info()["dot_partials"]`` partial sums of r.z, doubles."""
+        if d_partials is None:
+            rc = self.lib.tilespmv_fsai_apply(self.h, C.c_void_p(d_r), C.c_void_p(d_z), C.c_void_p(stream))
+        else:
+            rc = self.lib.tilespmv_fsai_apply_dot(self.h, C.c_void_p(d_r), C.c_void_p(d_z), C.c_void_p(d_partials), C.c_void_p(stream))
+        self._check(rc, "tilespmv_fsai_apply")
+
+    def factor(self, stream=0):
+        """Synchronises ``stream``; G as host copies ``(rowptr int32 [rows + 1], colidx int32 [nnz], values [nnz] of the value type)``, numpy arrays."""
+        rp, ci, v, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int()
+        self._check(self.lib.tilespmv_fsai_factor_csr(self.h, C.byref(rp), C.byref(ci), C.byref(v), C.byref(nnz)), "tilespmv_fsai_factor_csr")
+        out = (np.empty(self.rows + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32), np.empty(nnz.value, dtype=self.dtype))
+        sync, copy = self.lib.hipStreamSynchronize, self.lib.hipMemcpy           # (the HIP runtime the library is linked against)
+        sync.argtypes, sync.restype = [C.c_void_p], C.c_int
+        copy.argtypes, copy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
+        rc = sync(C.c_void_p(stream))
+        for a, src in zip(out, (rp, ci, v)):
+            rc = rc or copy(a.ctypes.data_as(C.c_void_p), src, a.nbytes, 2)      # hipMemcpyDeviceToHost
+        self._check(rc, "FSAI.factor: hipMemcpy")
+        return out
+
+    def info(self, stream=0):
+        """Synchronises ``stream``; ``{"rows", "nnz", "longest_row", "truncated_rows", "fallback_rows", "device_bytes", "dot_partials"}`` (nnz, longest_row: of G; truncated_rows:
+        rows of A with more than 64 entries at or left of the diagonal; fallback_rows: rows the last create or update replaced by point Jacobi)."""
+        out = (C.c_longlong * len(_lib.FSAI_INFO_NAMES))()
+        self._check(self.lib.tilespmv_fsai_info(self.h, C.c_void_p(stream), out), "tilespmv_fsai_info")
+        return dict(zip(_lib.FSAI_INFO_NAMES, [int(v) for v in out]))
+
+
+def _fsai_handle(fsai, d_dinv, block, lib):
+    """The handle of the ``fsai`` argument of ``CG`` (None: none given)."""
+    if fsai is None:
+        return None
+    if d_dinv or block is not None:
+        raise ValueError("fsai, block and d_dinv are mutually exclusive: one preconditioner")
+    if not isinstance(fsai, FSAI) or not fsai.h or fsai.lib is not lib:
+        raise ValueError("fsai must be an open api.FSAI of the plan's value type")
+    return fsai.h
+
+
 def _block_handle(block, d_dinv, lib):
     """The handle of the ``block`` argument of ``CG`` / ``BiCGStab`` (None: none given)."""
     if block is None:
@@ -575,19 +639,23 @@ class CG(_IterativeSolver):
     """``tilespmv_cg``: conjugate gradients around a resident plan, every scalar on the device (include/tilespmv.h).
 
     ``plan``: square and whole; it must stay open while the solver is.  ``d_dinv``: device ADDRESS of the inverse diagonal (Jacobi; borrowed), or None for plain CG.  ``block``: a
-    ``BlockJacobi`` of the plan's rows instead of ``d_dinv`` (borrowed: keep it open while the solver is).  ``b`` / ``x``
+    ``BlockJacobi`` of the plan's rows instead of ``d_dinv`` (borrowed: keep it open while the solver is).  ``fsai``: an ``FSAI`` of the plan's rows instead of
+    either (borrowed likewise).  ``b`` / ``x``
     are device addresses of ``rows`` elements, 16-byte aligned.  The solver and its plan run on one stream at a time.  Raises ``ValueError`` where the library returns
-    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a block preconditioner of another row count) and for ``block`` together with ``d_dinv``.
+    hipErrorInvalidValue (a shard, a non-square plan, a misaligned vector, a preconditioner object of another row count) and for two of ``d_dinv``, ``block`` and ``fsai`` together.
     ``begin``: r = b - A x, p = z.  ``state``: ``{"iterations", "status", "status_name", "rr", "bb", "relative_residual"}``."""
 
     _prefix = "tilespmv_cg"
     _hint = "the plan must be square and whole; vectors 16-byte aligned; a block preconditioner has the plan's rows"
 
-    def __init__(self, plan, d_dinv=None, block=None):
-        self.lib, self.plan, self.block = plan.lib, plan, block
+    def __init__(self, plan, d_dinv=None, block=None, fsai=None):
+        self.lib, self.plan, self.block, self.fsai = plan.lib, plan, block, fsai
         h = C.c_void_p()
+        fh = _fsai_handle(fsai, d_dinv, block, plan.lib)
         bh = _block_handle(block, d_dinv, plan.lib)
-        if bh is not None:
+        if fh is not None:
+            self._check(self.lib.tilespmv_cg_create_fsai(C.byref(h), plan.h, fh), "tilespmv_cg_create_fsai")
+        elif bh is not None:
             self._check(self.lib.tilespmv_cg_create_block(C.byref(h), plan.h, bh), "tilespmv_cg_create_block")
         else:
             self._check(self.lib.tilespmv_cg_create(C.byref(h), plan.h, C.c_void_p(d_dinv or None)), "tilespmv_cg_create")

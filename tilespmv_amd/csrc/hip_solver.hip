@@ -6,6 +6,7 @@
 //   k_cg_direction  reads r, p (, dinv)             beta = rho_new / rho;  p = z + beta p  (z recomputed from r and dinv, never stored)
 // With a block-Jacobi object (tilespmv_cg_create_block; hip_precond.hip) z is a stored vector: k_cg_update runs with dinv = NULL (r.r partials only), k_bj_apply forms
 // z = M^-1 r and the r.z partials, and k_cg_zstep replaces k_cg_direction — four launches, (13 + bs) n elements.  The kernels above are the same code either way.
+// An FSAI object (tilespmv_cg_create_fsai; hip_fsai.hip) takes the same stored-z path: z = G^T (G r) by its two plans and one pass for the r.z partials.
 // 11 n vector elements per iteration (13 n with Jacobi).  The launch shape and the partial sums with their fixed order of additions are those of hip_solver_common.h, and so is the
 // walk over a vector: every kernel here hands its body, written once for lane vectors and tail elements alike, to sv_dot, sv_walk_loaded (the kernels of the iteration: a trip's loads
 // before its arithmetic) or sv_walk.  The number of partials is solver_parts(n).  alpha and beta are rounded to the value type once, where they multiply.
@@ -19,6 +20,7 @@
 // positive definite) -> breakdown is set, alpha = beta = 0 in this and every later iteration, x keeps its last good value.
 #include <hip/hip_runtime.h>
 
+#include "hip_fsai.h"
 #include "hip_precond.h"
 #include "hip_solver_common.h"
 
@@ -168,31 +170,33 @@ struct tilespmv_cg {
     int np = 0;
     const val_t *dinv = nullptr;   // borrowed
     const tilespmv_block_jacobi *bj = nullptr;   // borrowed (tilespmv_cg_create_block; then dinv is NULL and z is a vector)
+    tilespmv_fsai *fsai = nullptr;               // borrowed (tilespmv_cg_create_fsai; likewise)
     void *block = nullptr;         // the one allocation: r, p, Ap (, z), the partial-sum arrays, the scalar block
     val_t *r = nullptr, *p = nullptr, *Ap = nullptr, *z = nullptr;
     double *ppap = nullptr, *prr = nullptr, *prz = nullptr, *pbb = nullptr;
     CgScal *S = nullptr;
 };
 
-// the two creates: a diagonal (d_dinv, may be NULL) or a block-Jacobi object (bj), never both
-static int cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const val_t *d_dinv, const tilespmv_block_jacobi *bj)
+// the three creates: a diagonal (d_dinv, may be NULL), a block-Jacobi object (bj) or an FSAI object (fsai), never two of them; with an object z is a stored vector
+static int cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const val_t *d_dinv, const tilespmv_block_jacobi *bj, tilespmv_fsai *fsai)
 {
     const long long n = square_system(cg, plan, d_dinv);
-    if (!n || (bj && bj->rows != n)) return (int)hipErrorInvalidValue;
+    if (!n || (bj && bj->rows != n) || (fsai && fsai->rows != n)) return (int)hipErrorInvalidValue;
     const size_t vec = vec_bytes(n), parts = SV_PARTS_BYTES;
+    const bool stored_z = bj || fsai;
     DeviceBlock blk;
-    const hipError_t e = blk.alloc((bj ? 4 : 3) * vec + 4 * parts + 256);
+    const hipError_t e = blk.alloc((stored_z ? 4 : 3) * vec + 4 * parts + 256);
     if (e != hipSuccess) return (int)e;
     auto *c = new tilespmv_cg();
-    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->bj = bj; c->block = blk.base;
+    c->plan = plan; c->n = n; c->np = solver_parts(n); c->dinv = d_dinv; c->bj = bj; c->fsai = fsai; c->block = blk.base;
     c->r = blk.take<val_t>(vec);
     c->p = blk.take<val_t>(vec);
     c->Ap = blk.take<val_t>(vec);
-    if (bj) c->z = blk.take<val_t>(vec);
+    if (stored_z) c->z = blk.take<val_t>(vec);
     c->ppap = blk.take<double>(parts);
     c->prr = blk.take<double>(parts);
     double *const rz = blk.take<double>(parts);
-    c->prz = (d_dinv || bj) ? rz : c->prr;
+    c->prz = (d_dinv || stored_z) ? rz : c->prr;
     c->pbb = blk.take<double>(parts);
     c->S = blk.take<CgScal>(256);
     *cg = c;
@@ -201,7 +205,7 @@ static int cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const val_t *d_dinv,
 
 extern "C" int tilespmv_cg_create(tilespmv_cg **cg, tilespmv_plan *plan, const MAT_VAL_TYPE *d_dinv)
 {
-    return cg_create(cg, plan, d_dinv, nullptr);
+    return cg_create(cg, plan, d_dinv, nullptr, nullptr);
 }
 
 extern "C" int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, const tilespmv_block_jacobi *bj)
@@ -210,7 +214,24 @@ extern "C" int tilespmv_cg_create_block(tilespmv_cg **cg, tilespmv_plan *plan, c
         if (cg) *cg = nullptr;
         return (int)hipErrorInvalidValue;
     }
-    return cg_create(cg, plan, nullptr, bj);
+    return cg_create(cg, plan, nullptr, bj, nullptr);
+}
+
+extern "C" int tilespmv_cg_create_fsai(tilespmv_cg **cg, tilespmv_plan *plan, tilespmv_fsai *f)
+{
+    if (!f) {
+        if (cg) *cg = nullptr;
+        return (int)hipErrorInvalidValue;
+    }
+    return cg_create(cg, plan, nullptr, nullptr, f);
+}
+
+// z = M^-1 r and the r.z partials by the solver's object (a stored z: cg->z is not NULL)
+static int cg_precondition(const tilespmv_cg *cg, val_t *z, hipStream_t st)
+{
+    if (cg->fsai) return fsai_launch(cg->fsai, cg->r, z, cg->prz, st);
+    block_jacobi_launch(cg->bj, cg->r, z, cg->prz, st);
+    return 0;
 }
 
 extern "C" void tilespmv_cg_destroy(tilespmv_cg *cg) { destroy_solver(cg); }
@@ -222,7 +243,10 @@ extern "C" int tilespmv_cg_begin(tilespmv_cg *cg, const MAT_VAL_TYPE *d_b, MAT_V
     const int rc = tilespmv_plan_spmv(cg->plan, d_x, cg->Ap, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_cg_begin, dim3(cg->np), dim3(SVB), 0, st, cg->n, d_b, cg->Ap, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->pbb);
-    if (cg->bj) block_jacobi_launch(cg->bj, cg->r, cg->p, cg->prz, st);   // p = z = M^-1 r, and the r.z partials
+    if (cg->z) {   // p = z = M^-1 r, and the r.z partials
+        const int rcz = cg_precondition(cg, cg->p, st);
+        if (rcz) return rcz;
+    }
     hipLaunchKernelGGL(k_cg_begin_fold, dim3(1), dim3(SVB), 0, st, cg->prr, cg->prz, cg->pbb, cg->np, cg->S);
     return (int)hipGetLastError();
 }
@@ -236,8 +260,9 @@ extern "C" int tilespmv_cg_iterate(tilespmv_cg *cg, MAT_VAL_TYPE *d_x, int count
         if (rc) return rc;
         hipLaunchKernelGGL(k_cg_dot, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->p, cg->Ap, cg->ppap, cg->prz, cg->np, cg->S);
         hipLaunchKernelGGL(k_cg_update, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->p, cg->Ap, d_x, cg->r, cg->dinv, cg->ppap, cg->prr, cg->prz, cg->np, cg->S);
-        if (cg->bj) {   // (k_cg_update left the r.r partials only)
-            block_jacobi_launch(cg->bj, cg->r, cg->z, cg->prz, st);
+        if (cg->z) {   // (k_cg_update left the r.r partials only)
+            const int rcz = cg_precondition(cg, cg->z, st);
+            if (rcz) return rcz;
             hipLaunchKernelGGL(k_cg_zstep, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->z, cg->p, cg->prr, cg->prz, cg->np, cg->S);
         } else
             hipLaunchKernelGGL(k_cg_direction, dim3(cg->np), dim3(SVB), 0, st, cg->n, cg->r, cg->p, cg->dinv, cg->prr, cg->prz, cg->np, cg->S);

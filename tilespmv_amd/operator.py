@@ -192,13 +192,14 @@ class SparseOperator:
         diagonal as a CUDA vector (Jacobi; ``api.csr_diagonal_device(..., invert=True)`` makes it), None = plain CG.  Stops at ``sqrt(rr / bb) <= rtol`` or after ``maxiter``
         iterations (default ``2 * rows``).  Returns ``(x, info)`` with ``info = {"iterations", "residual", "relative_residual", "converged", "status"}``.
         A contiguous 2-D ``b`` of shape (rows, k) solves k systems at once (``_cg_multi``): ``(X, [info] * k)``.
-        ``precond``: an updated ``api.BlockJacobi`` of ``rows`` rows instead of ``dinv`` (block Jacobi; a 1-D ``b`` only)."""
+        ``precond``: an updated ``api.BlockJacobi`` (block Jacobi) or an ``api.FSAI`` of ``rows`` rows instead of ``dinv``; a 1-D ``b`` only."""
         self._square("cg")
         if _is_tensor(b) and b.dim() == 2:
             if precond is not None:
-                raise ValueError("precond (block Jacobi) applies to a 1-D b only")
+                raise ValueError("precond (block Jacobi, FSAI) applies to a 1-D b only")
             return self._cg_multi(b, x0, rtol, maxiter, check_every, dinv, stream)
-        x, s = self._solve(lambda d: api.CG(self.A, d, block=precond), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
+        which = "fsai" if isinstance(precond, api.FSAI) else "block"
+        x, s = self._solve(lambda d: api.CG(self.A, d, **{which: precond}), b, x0, self.shape[0], "dinv", dinv, stream, rtol=rtol, maxiter=maxiter, check_every=check_every)
         return x, _info(s)
 
     @staticmethod
