@@ -546,6 +546,11 @@ enum {
     TILESPMV_INFO_COUNT = 35
 };
 void tilespmv_plan_info(const tilespmv_plan *plan, long long *out /* [TILESPMV_INFO_COUNT] */);
+/* Strided strips (environment knob TILESPMV_STRIP_SWEEP: unset = by rule, 0 = never, 1 = wherever the shard's structure allows): the stride S, in tile-rows, between
+ * the consecutive tile-rows of one strip of the plan's unit stream; 1 = consecutive tile-rows (every plan the knob does not reach).  Stencil-like shards whose grid lines are whole
+ * tile-rows long get S = one grid line: a strip then sweeps down the grid and reads the windows of x it shares with its previous tile-row while they are still in the caches.  The
+ * plan holds the same units, values and task records in another order; y is the unstrided plan's bit for bit. */
+int tilespmv_plan_strip_stride(const tilespmv_plan *plan);
 /* Test / audit aid: one (member offset in the plan object, bytes, FNV-1a-64 of the bytes read back from the device) triple per stream of the plan, at most max_streams of them
  * written; returns the number of streams (or -3 on a HIP error).  Two plans of one matrix and one option set — one built from a host Tile_matrix, one by
  * tilespmv_plan_create_from_csr — must agree triple for triple (tests/test_gpu_device_build.py). */

@@ -148,6 +148,9 @@ def load(dtype=np.float64):
     lib.tilespmv_plan_spmv_n.restype = C.c_int
     lib.tilespmv_plan_info.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.tilespmv_plan_info.restype = None
+    if hasattr(lib, "tilespmv_plan_strip_stride"):   # (a TILESPMV_LIB_VARIANT library of an earlier commit has no such entry)
+        lib.tilespmv_plan_strip_stride.argtypes = [C.c_void_p]
+        lib.tilespmv_plan_strip_stride.restype = C.c_int
     lib.tilespmv_plan_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.tilespmv_plan_time.restype = C.c_double
     lib.tilespmv_plan_time_reference_style.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -278,4 +281,5 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_fsai_create", "tilespmv_fsai_destroy", "tilespmv_fsai_update", "tilespmv_fsai_apply", "tilespmv_fsai_apply_dot", "tilespmv_fsai_factor_csr",
                     "tilespmv_fsai_info", "tilespmv_cg_create_fsai",
                     "tilespmv_gmres_create", "tilespmv_gmres_create_block", "tilespmv_gmres_destroy", "tilespmv_gmres_begin", "tilespmv_gmres_iterate", "tilespmv_gmres_flush",
-                    "tilespmv_gmres_state_read", "tilespmv_gmres_solve", "tilespmv_gmres_create_basis", "tilespmv_gmres_basis_bytes", "tilespmv_gmres_workspace_bytes"]
+                    "tilespmv_gmres_state_read", "tilespmv_gmres_solve", "tilespmv_gmres_create_basis", "tilespmv_gmres_basis_bytes", "tilespmv_gmres_workspace_bytes",
+                    "tilespmv_plan_strip_stride"]

@@ -407,6 +407,10 @@ class Plan:
         self.lib.tilespmv_plan_info(self.h, out)
         return {k: int(out[i]) for i, k in enumerate(_lib.INFO_NAMES)}
 
+    def strip_stride(self):
+        """S: tile-rows between the consecutive tile-rows of one strip of the unit stream, 1 = consecutive (tilespmv_plan_strip_stride; TILESPMV_STRIP_SWEEP)."""
+        return int(self.lib.tilespmv_plan_strip_stride(self.h))
+
     def stream_digests(self):
         """{member offset: (bytes, FNV-1a-64)} of every stream of the plan, read back from the device (test / audit aid)."""
         out = (C.c_ulonglong * (3 * 64))()

@@ -745,24 +745,25 @@ __global__ __launch_bounds__(256, MV_MIN_WAVES) void k_units_mv(DevStream S, int
     // waits in registers and is stored right AFTER the next batch's loads have been issued: nvec 2 fp64 0.256 -> 0.249 ms, nvec 8
     // fp32 0.494 -> 0.465 ms; with the spills it brings elsewhere (fp64 nvec 4 / 8: 6 VGPRs) it loses 5-7 %, so it is per variant.
     constexpr bool MV_DEFER_STORE = NVT == 2 || (MV_DEFER_F32_NV8 && sizeof(val_t) == 4 && NVT == 8);
+    const int ystride = __builtin_amdgcn_readfirstlane(S.strip_stride);   // tile-row k of a strip is row0 + k * ystride (hip_plan.h DevStream::strip_stride; tile-rows are ints)
     vec_t pend; int pend_kr = -1;
     auto store_vec = [&](int kr, const vec_t &o) {
-        const long long yi = ((long long)row0 + kr) * 16 + r;
-        if (yi < rowA) {
+        const unsigned yi = (unsigned)(row0 + kr * ystride) * 16u + (unsigned)r;   // (tile-row kr of the strip; rowA is an int, so a row below rowA + 16 is an unsigned)
+        if (yi < (unsigned)rowA) {
             if constexpr (sizeof(vec_t) == 16) {
                 v4u_t w; __builtin_memcpy(&w, &o, 16);
-                MV_STORE16(w, reinterpret_cast<v4u_t *>(&Yv[yi * Q]));
+                MV_STORE16(w, reinterpret_cast<v4u_t *>(&Yv[(size_t)yi * Q]));
             } else if constexpr (sizeof(vec_t) == 8) {
                 v2u_t w; __builtin_memcpy(&w, &o, 8);
-                __builtin_nontemporal_store(w, reinterpret_cast<v2u_t *>(&Yv[yi * Q]));
+                __builtin_nontemporal_store(w, reinterpret_cast<v2u_t *>(&Yv[(size_t)yi * Q]));
             } else {
-                Yv[yi * Q] = o;
+                Yv[(size_t)yi * Q] = o;
             }
         }
     };
     auto flush_pending = [&]() { if (pend_kr >= 0) { store_vec(pend_kr, pend); pend_kr = -1; } };
     auto store_row = [&](int kr) {
-        const long long yi = ((long long)row0 + kr) * 16 + r;
+        const unsigned yi = (unsigned)(row0 + kr * ystride) * 16u + (unsigned)r;   // (tile-row kr of the strip; rowA is an int, so a row below rowA + 16 is an unsigned)
         if (MV_DEFER_STORE) {
             flush_pending();
 #pragma unroll
@@ -770,18 +771,18 @@ __global__ __launch_bounds__(256, MV_MIN_WAVES) void k_units_mv(DevStream S, int
             pend_kr = kr;
             return;
         }
-        if (yi < rowA) {
+        if (yi < (unsigned)rowA) {
             vec_t o;
 #pragma unroll
             for (int j = 0; j < NV; j++) o.v[j] = acc[j];
             if constexpr (sizeof(vec_t) == 16) {  // streaming stores, as in k_units
                 v4u_t w; __builtin_memcpy(&w, &o, 16);
-                MV_STORE16(w, reinterpret_cast<v4u_t *>(&Yv[yi * Q]));
+                MV_STORE16(w, reinterpret_cast<v4u_t *>(&Yv[(size_t)yi * Q]));
             } else if constexpr (sizeof(vec_t) == 8) {
                 v2u_t w; __builtin_memcpy(&w, &o, 8);
-                __builtin_nontemporal_store(w, reinterpret_cast<v2u_t *>(&Yv[yi * Q]));
+                __builtin_nontemporal_store(w, reinterpret_cast<v2u_t *>(&Yv[(size_t)yi * Q]));
             } else {
-                Yv[yi * Q] = o;
+                Yv[(size_t)yi * Q] = o;
             }
         }
 #pragma unroll
@@ -1283,7 +1284,7 @@ __global__ __launch_bounds__(256) void k_pair_values(const val_t *__restrict__ s
         const int4 m = map[t];
         const long long so = (long long)m.x * 16, dofs = (long long)m.y * 16;
         for (int i = threadIdx.x; i < m.z * 16; i += 256) {
-            const int j = i >> 4, r = i & 15;
+            const int j = m.w + (i >> 4), r = i & 15;   // (m.w: the task-relative place of the run's first unit; a strided strip's units come as one run per tile-row)
             const long long at = dofs + (long long)(j / G * G) * 16 + G * r + (j % G);
             if (narrow == 2) dsth[at] = value_half_bits((double)src[so + i]);
             else if (narrow) dstn[at] = (float)src[so + i];

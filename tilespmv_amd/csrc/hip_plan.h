@@ -221,6 +221,10 @@ struct DevStream {
     // row unit (UNIT_ROWUNIT), bit 1 = no unit is derived (UNIT_DERIVED_CODE).  The launch reads them through unit_lean_form below.
     int unit_facts;
     int unit_lean;                        // the knob (tilespmv_plan_options.unit_lean): 0 = general kernels whatever the facts say
+    // strided strips ("strip sweep", hip_plan_stream.hip strip_sweep_stride / cut()): tile-row k of a strip is STask::row + k * strip_stride.  1 = consecutive tile-rows.  With a
+    // stride of one grid line a tile-row's "up" and centre windows of x are the centre and "down" windows of the strip's previous tile-row: the strip reads them again a few
+    // batches after it first did, from the vector L1 / its XCD's L2
+    int strip_stride = 1;
 };
 constexpr int UNIT_FACT_NO_ROWUNIT = 1, UNIT_FACT_NO_DERIVED = 2;
 // The form of the unit kernel a launch takes (TILESPMV_INFO_UNIT_LEAN): 0 = the general kernel, 1 = lean (no row units), 2 = lean without derived units.  Lean forms exist for

@@ -69,6 +69,7 @@ static Knobs resolve_knobs(const tilespmv_plan_options *opts)
     k.value_narrow = pick(o.value_narrow, "TILESPMV_VALUE_NARROW", -1);
     static const int unit_lean_env = env_int("TILESPMV_UNIT_LEAN", 1);   // (read once)
     k.unit_lean = (o.unit_lean != TILESPMV_KNOB_DEFAULT ? o.unit_lean : unit_lean_env) != 0 ? 1 : 0;
+    k.strip_sweep = std::max(-1, std::min(1, env_int("TILESPMV_STRIP_SWEEP", -1)));   // (no field of tilespmv_plan_options: its layout is pinned)
     k.deterministic = pick(o.deterministic, "TILESPMV_DETERMINISTIC", 0) > 0 ? 1 : 0;
     if (k.deterministic) {   // no stopwatch, no unordered sum: whatever the caller left unset among the timed choices is switched off
         if (k.placement_tries < 0) k.placement_tries = 1;
@@ -1056,6 +1057,11 @@ long long tilespmv_plan_stream_digests(const tilespmv_plan *plan, unsigned long 
         n++;
     }
     return n;
+}
+
+int tilespmv_plan_strip_stride(const tilespmv_plan *plan)
+{
+    return plan->kernel == TILESPMV_KERNEL_STREAM ? std::max(1, plan->st.strip_stride) : 1;
 }
 
 void tilespmv_plan_info(const tilespmv_plan *plan, long long *out)

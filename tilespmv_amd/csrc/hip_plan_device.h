@@ -35,7 +35,7 @@ int dev_emit(const DevShard &S, const DevCounts &C, const hvec<long long> &pu, c
 // word 0 of every emitted unit descriptor -> host (brick order scores the column blocks of the strips)
 int dev_fetch_word0(const uint4 *d_udesc, long long NU, hvec<unsigned> &w0);
 // ENCODE: units of task i move from [map.x, map.x + map.z) to [map.y, ..) of the packed numbering (padding units in between stay zero)
-int dev_pack_desc(const uint4 *d_udesc, const uint2 *d_urow, const uint4 *d_ucol, const int4 *d_map, int ntasks, UDesc *d_packed, URow *d_packed_row, uint4 *d_packed_col);   // d_map: device copy of the (old begin, new begin, count) triples
+int dev_pack_desc(const uint4 *d_udesc, const uint2 *d_urow, const uint4 *d_ucol, const int4 *d_map, int ntasks, UDesc *d_packed, URow *d_packed_row, uint4 *d_packed_col);   // d_map: device copy of the (old begin, the task's new begin, count, place in the task) runs
 int dev_all_narrowable(const val_t *d_uval, long long n, bool *all_float, bool *all_half);   // fp64 build, one pass: is every one of the n emitted unit values narrowable / halvable (plan_tile_ops.h)?  fp32 build: false
 int dev_shift_histogram(const UDesc *d_packed, long long NUP, unsigned long long hist[8]);   // units per shift code (word 0 >> UNIT_SHIFT_SHIFT)
 int dev_count_flag(const UDesc *d_packed, long long NUP, unsigned flag, long long *count);      // units whose flags (word 0 >> UNIT_FLAG_SHIFT) have a bit of `flag` set

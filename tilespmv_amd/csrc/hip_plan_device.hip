@@ -222,9 +222,10 @@ __global__ __launch_bounds__(256) void k_pd_pack_desc(const uint4 *__restrict__ 
     for (int t = blockIdx.x; t < ntasks; t += gridDim.x) {
         const int4 m = map[t];
         for (int j = threadIdx.x; j < m.z; j += 256) {
-            packed[(long long)m.y + j] = unit_desc12(udesc[(long long)m.x + j]);
-            if (urow) { const uint2 r = urow[(long long)m.x + j]; packed_row[(long long)m.y + j] = URow{r.x, r.y}; }
-            if (ucol) packed_col[(long long)m.y + j] = ucol[(long long)m.x + j];
+            const long long to = (long long)m.y + m.w + j;   // (m.w: the task-relative place of the run's first unit, hip_plan_stream.hip renumber_units)
+            packed[to] = unit_desc12(udesc[(long long)m.x + j]);
+            if (urow) { const uint2 r = urow[(long long)m.x + j]; packed_row[to] = URow{r.x, r.y}; }
+            if (ucol) packed_col[to] = ucol[(long long)m.x + j];
         }
     }
 }

@@ -77,6 +77,46 @@ inline void detect_strides(const Tile_matrix *T, int tr0, int tr1, bool csr_spli
 }
 
 
+// The line stride of a stencil-like shard for strided strips (StreamBuilder::strip_sweep_stride), from the same sample and the same dominance rule as detect_strides, but
+// over the distances of EVERY unit tile, the diagonal and the ones below it included: the smallest gap between two dominant distances.  Unlike s1 above this does not move when
+// the shard's tile-rows are numbered from another origin than its columns (a row block of a larger matrix), and it says when the stride is not exact: a gap of one tile-row
+// between dominant distances means grid lines that are no whole number of tile-rows long, or a line stride of one tile-row — 0 then, and where there is no structure.
+// ndominant: how many dominant distances there are (3 on a 2-D grid: up, diagonal, down; more where a plane stride or a wider stencil adds tiles).
+inline int sweep_line_stride(const Tile_matrix *T, int tr0, int tr1, bool csr_split, bool dense_mfma, int *ndominant)
+{
+    *ndominant = 0;
+    const int ntr = tr1 - tr0;
+    if (ntr < 32) return 0;
+    const int step = std::max(1, ntr / 32768);
+    std::vector<long long> ds;
+    long long sampled = 0;
+    for (int bi = tr0; bi < tr1; bi += step) {
+        sampled++;
+        long long last = LLONG_MIN;
+        for (int t = T->tile_ptr[bi]; t < T->tile_ptr[bi + 1]; t++) {
+            const int fmt = T->Format[t];
+            const bool units = fmt == TILESPMV_FMT_ELL || fmt == TILESPMV_FMT_HYB || fmt == TILESPMV_FMT_DNSCOL || fmt == TILESPMV_FMT_DNSROW ||
+                               (fmt == TILESPMV_FMT_DNS && !dense_mfma) || (fmt == TILESPMV_FMT_CSR && csr_split);
+            const long long d = (long long)T->tile_columnidx[t] - bi;
+            if (units && d != last) { ds.push_back(d); last = d; }
+        }
+    }
+    std::sort(ds.begin(), ds.end());
+    long long prev = LLONG_MIN, gap = LLONG_MAX;
+    for (size_t i = 0; i < ds.size();) {
+        size_t j = i;
+        while (j < ds.size() && ds[j] == ds[i]) j++;
+        if ((long long)(j - i) * 4 >= sampled) {   // a distance that at least a quarter of the sampled tile-rows have
+            if (prev != LLONG_MIN) gap = std::min(gap, ds[i] - prev);
+            prev = ds[i];
+            (*ndominant)++;
+        }
+        i = j;
+    }
+    return gap >= 2 && gap <= (1 << 20) ? (int)gap : 0;
+}
+
+
 // The builder, one stage per method.  Every stage reads the members earlier stages filled and, in layout-digest builds
 // (plan->dry), hashes what it produced into plan->stage_digest[stage]: tests/test_plan_stages.py pins which knob may change which stage.
 //   COUNT    per tile-row: units / entries / whole tiles / dense tiles it will emit, cost; prefix sums
@@ -110,6 +150,9 @@ struct StreamBuilder {
     bool fix_inline_on = true, entry_heavy = false, entry_dominated = false, wave_coo = false, coo_ordered = false, brick = false;
     long long total_cost = 0, est_wgs = 0;
     int target = 0, entry_mode = 0, wg_strips = 16, xs1 = 0, xs2 = 0, max_strip_rows = STRIP_MAX_ROWS;
+    int strip_stride = 1;                                       // tile-rows between the consecutive tile-rows of a strip (strip_sweep_stride below; hip_plan.h DevStream::strip_stride)
+    int split_threshold() const { return wave_coo ? std::max(split_above_in, std::min(6 * target, K.split_cap)) : std::max(6 * target, split_above_in); }   // tile-rows above this cost are cut into pieces
+    int strip_sweep_stride();
     int panel_shift = 0, x_panels = 1;                          // column panels of the merged entry lists (hip_plan.h DevStream::x_panels)
     // CUT
     std::vector<STask> tasks;
@@ -449,6 +492,8 @@ void StreamBuilder::choose()
     if (brick && xs1 == 0) detect_strides(T, tr0, tr1, csr_split, dense_mfma, &xs1, &xs2);
     if (xs1 < 2 || (K.x_window < 0 && xs2 == 0)) brick = false;   // (2-D grids: measured neutral on the 5-point 4096^2 case)
     // (strips of at most 4 tile-rows in brick plans: nlpkkt160 stand-in fp64 0.418 -> 0.414 ms, fp32 0.252 -> 0.250 in one process; 2 rows: KKT 0.408 but 7-pt 256^3 +5 %)
+    strip_stride = strip_sweep_stride();
+    if (strip_stride > 1) brick = false;   // (the sweep orders the strips of a shard itself)
     max_strip_rows = pooled ? POOL_STRIP_ROWS : brick ? 4 : STRIP_MAX_ROWS;
     if (brick && !K.xcd_from_caller) plan->xcd_chunk = 8;   // bricks are compact: smaller XCD windows keep an XCD's resident set together
     // ---- column panels of the entry lists (hip_plan.h DevStream::x_panels): scattered, entry-dominated shards whose x is several times an XCD's L2
@@ -470,8 +515,31 @@ void StreamBuilder::choose()
         Hash h;
         h.num(x_panels); h.num(panel_shift);
         for (long long v : {(long long)target, (long long)entry_mode, (long long)wg_strips, (long long)coo_ordered, (long long)xs1, (long long)xs2, (long long)brick, (long long)max_strip_rows}) h.num(v);
+        if (strip_stride > 1) h.num(strip_stride);   // (a plan without the sweep hashes what it always has)
         stage_done(TILESPMV_STAGE_CHOOSE, h);
     }
+}
+
+// Strided strips (knob strip_sweep, TILESPMV_STRIP_SWEEP): the stride S in tile-rows between the consecutive tile-rows of a strip, 1 = none.  With
+// S = one grid line a tile-row's "up" and centre windows of x are the centre and "down" windows of the strip's previous tile-row: the strip gathers them again a few batches after
+// it first did and finds them in the vector L1 / its XCD's L2, where the consecutive tile-rows of an unstrided strip wait for other workgroups to have brought them in.  Only for
+// shards where every tile-row goes into a strip of whole tile-rows of units and nothing else: a classic plan, entries per strip with no list entry left (the absorbed corners of a
+// stencil), 16 strips per workgroup, no tile-row to split, no whole or dense tile, no fallback list, nontemporal streams (by the size rule under AUTO — a LOWER bound of FINISH's
+// byte model, as in choose_value_width —, so plans that fit the Infinity Cache never change; forced streams count under knob 1), and an exact line stride (sweep_line_stride).
+int StreamBuilder::strip_sweep_stride()
+{
+    if (K.strip_sweep == 0 || pooled || csr_form >= 2 || !coo_in_tile || entry_mode != 0 || wg_strips != 16) return 1;
+    if (NC != 0 || NH != 0 || ND != 0 || NU <= 0 || K.nt_stream == 0) return 1;
+    const long long launch_min = NU * (4 + 16LL * (sizeof(val_t) == 8 ? 2 : sv)) + ((long long)colA + 16LL * ntr) * sv;   // (the narrowest value form of the build, whatever value_narrow says: the strips of a matrix do not follow the value knob)
+    if (!(launch_min > NT_STREAM_MIN_BYTES || (K.strip_sweep > 0 && K.nt_stream > 0))) return 1;
+    const int split_above = split_threshold();
+    for (int i = 0; i < ntr; i++) if (rc_[i].cost > split_above) return 1;
+    int ndominant = 0;
+    const int s1 = sweep_line_stride(T, tr0, tr1, csr_split, dense_mfma, &ndominant);
+    // by rule only where the line stride is the shard's only one (2-D grids: 5-point 4096^2 -2.7 ... -4.4 % in the fp64 library's three value forms, -15 % in the fp32 library); a
+    // 7-point 256^3 cube, whose plane neighbours the sweep does not bring any closer, loses 5.6 % in fp64 and ties in fp32: profiles/strip_sweep_ab.txt.  Knob 1 takes both
+    if (K.strip_sweep < 0 && ndominant > 3) return 1;
+    return s1 >= 2 ? s1 : 1;
 }
 
 void StreamBuilder::cut()
@@ -482,8 +550,7 @@ void StreamBuilder::cut()
         // rows above this cost are cut into pieces.  With the wavefront / workgroup entry modes a long row is no longer one strip's
         // private burden, but an unsplit one still makes its workgroup the last to finish: the threshold stops growing with the
         // strip size there (R-MAT scale 20 at strip size 3200: 0.099 ms with rows of up to 19,200 cost units kept whole)
-        const int split_cap = K.split_cap;
-        const int split_above = wave_coo ? std::max(split_above_in, std::min(6 * target, split_cap)) : std::max(6 * target, split_above_in);
+        const int split_above = split_threshold();
         const int piece = std::max(wave_coo ? std::min(2 * target, 1600) : 2 * target, split_above / 3);
         tasks.clear(); htasks.clear(); ifix.clear(); fix_late.clear(); fix.clear(); drows.clear(); npartial = npartial0;
         std::fill(row_k.begin(), row_k.end(), 0); std::fill(row_split.begin(), row_split.end(), 0);
@@ -502,7 +569,22 @@ void StreamBuilder::cut()
         // more dense tiles than that is always split, whatever the cost knobs say (TILESPMV_STRIP_COST / _SPLIT_ABOVE).
         constexpr int DENSE_PIECE = 32;
         auto must_split = [&](int i) { return rc_[i].cost > split_above || rc_[i].ndense > DENSE_PIECE; };
-        for (int i = 0; i < ntr;) {
+        // strided strips: the shard's tile-rows in blocks of STRIP_MAX_ROWS x S; strip j of a block owns its tile-rows j, j + S, j + 2 S, ... (fewer in the shard's last block).  Units
+        // are numbered strip by strip here; EMIT writes them tile-row by tile-row (pu), and renumber_units maps one onto the other, a run per tile-row
+        for (long long i0 = 0, ucur = 0; strip_stride > 1 && i0 < ntr; i0 += (long long)STRIP_MAX_ROWS * strip_stride)
+            for (int j = 0; j < strip_stride && i0 + j < ntr; j++) {
+                STask k = blank();
+                k.row = tr0 + (int)(i0 + j);
+                k.unit_begin = (int)ucur;
+                for (long long i = i0 + j; i < ntr && k.nrows < STRIP_MAX_ROWS; i += strip_stride, k.nrows++) {
+                    row_k[(size_t)i] = (unsigned char)k.nrows;
+                    if (rc_[(size_t)i].nunits == 0) k.nounit_mask |= 1u << k.nrows;
+                    ucur += rc_[(size_t)i].nunits;
+                }
+                k.unit_end = (int)ucur;
+                tasks.push_back(k);
+            }
+        for (int i = strip_stride > 1 ? ntr : 0; i < ntr;) {
             if (must_split(i)) {
                 row_split[i] = 1;
                 FixRow f{tr0 + i, npartial, 0, 0};
@@ -813,7 +895,7 @@ void host_pack_units(const std::vector<int4> &map, const std::vector<uint4> &ude
     parallel_chunks((int64_t)map.size(), 512, [&](int64_t b, int64_t e, int) {
         for (int64_t i = b; i < e; i++) {
             const int4 m = map[(size_t)i];
-            for (size_t from = (size_t)m.x, to = (size_t)m.y; from < (size_t)m.x + (size_t)m.z; from++, to++) {
+            for (size_t from = (size_t)m.x, to = (size_t)m.y + (size_t)m.w; from < (size_t)m.x + (size_t)m.z; from++, to++) {
                 packed[to] = unit_desc12(udesc[from]);
                 if (!packed_row.empty()) packed_row[to] = URow{urow[from].x, urow[from].y};
                 if (!packed_col.empty()) packed_col[to] = ucol[from];
@@ -881,8 +963,9 @@ D *host_group_values(const std::vector<int4> &map, const val_t *uval, long long 
     parallel_chunks((int64_t)map.size(), 512, [&](int64_t b, int64_t e, int) {
         for (int64_t i = b; i < e; i++) {
             const int4 m = map[(size_t)i];
-            for (long long j = 0; j < m.z; j++) {
-                const val_t *src = uval + (m.x + j) * 16;
+            for (long long q = 0; q < m.z; q++) {
+                const long long j = m.w + q;   // the unit's place in its task
+                const val_t *src = uval + (m.x + q) * 16;
                 D *dst = out + (m.y + j / G * G) * 16 + (j % G);
                 for (int r = 0; r < 16; r++) dst[G * r] = conv(src[r]);
             }
@@ -891,12 +974,12 @@ D *host_group_values(const std::vector<int4> &map, const val_t *uval, long long 
     return out;
 }
 
-// Every task's units padded to a multiple of the value group: NUP, old_begin, the (old begin, new begin, count) map that the pack step and the value pass read, and the tasks'
+// Every task's units padded to a multiple of the value group: NUP, old_begin, the (old begin, the task's new begin, count, place in the task) map of runs of units that the pack step and the value pass read, and the tasks'
 // new unit ranges.  false: more units than 32-bit unit ids address (found before anything is allocated)
 bool StreamBuilder::renumber_units(std::vector<int4> &map)
 {
     const long long G = value_group();
-    map.resize(tasks.size());
+    map.clear(); map.reserve(tasks.size() * (size_t)(strip_stride > 1 ? STRIP_MAX_ROWS : 1));
     old_begin.assign(tasks.size(), 0);
     NUP = 0;
     for (size_t i = 0; i < tasks.size(); i++) {
@@ -905,7 +988,14 @@ bool StreamBuilder::renumber_units(std::vector<int4> &map)
         NUP += (n + G - 1) / G * G;
         if (NUP > INT32_MAX) return false;
         old_begin[i] = ub;
-        map[i] = make_int4((int)ub, (int)nb, (int)n, 0);
+        if (strip_stride > 1) {   // strided strips (cut()): one run per tile-row, where EMIT put it; .w = the run's place in the task
+            long long at = 0;
+            for (int q = 0; q < k.nrows; q++) {
+                const size_t tr = (size_t)(k.row - tr0) + (size_t)q * (size_t)strip_stride;
+                if (rc_[tr].nunits > 0) map.push_back(make_int4((int)pu[tr], (int)nb, rc_[tr].nunits, (int)at));
+                at += rc_[tr].nunits;
+            }
+        } else map.push_back(make_int4((int)ub, (int)nb, (int)n, 0));
         if (n > 0) { k.unit_begin = (int)nb; k.unit_end = (int)(nb + n); }
     }
     return true;
@@ -918,6 +1008,8 @@ void StreamBuilder::encode()
     if (rc) return;
     S.uval_narrow = narrow;
     S.unit_facts = 0; S.unit_lean = K.unit_lean;   // (pooled plans keep no facts: they have no lean form)
+    S.strip_stride = strip_stride;
+    if (K.verbose && strip_stride > 1) fprintf(stderr, "tilespmv: strip sweep: a strip's tile-rows are %d tile-rows apart (one grid line)\n", strip_stride);
     // the estimate that sizes the arena blocks priced the values at sizeof(val_t); a plan of halves is up to four times smaller.  (The float form keeps the estimate — an upper
     // bound — it has always had, so that its plans are placed in memory as before.)
     if (narrow == 2) plan->size_hint -= std::min(plan->size_hint, (size_t)(NU * 16 * (sv - value_bytes())));

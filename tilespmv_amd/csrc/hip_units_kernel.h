@@ -793,24 +793,25 @@ __global__ __launch_bounds__(16 * GPB, ECOO == 1 ? 4 : ECOO == 2 ? (POOL ? POOL_
         wave_lds_fence();
         constexpr int VEC = 16 / (int)sizeof(val_t);  // values per 16-B lane store
         const lacc_t *res = &s_y[g][0][0];
-        const long long ybase = (long long)row0 * 16;
+        const int ystride = S.strip_stride;   // tile-row k of the strip is row0 + k * ystride (hip_plan.h DevStream::strip_stride); a 16-byte lane store never crosses a tile-row
         for (int i = r * VEC; i < 16 * nrows; i += 16 * VEC) {
+            const long long yi = ((long long)row0 + (long long)(i >> 4) * ystride) * 16 + (i & 15);
             if constexpr (sizeof(val_t) == sizeof(lacc_t)) {   // fp64: the 16 bytes go out as they sit in LDS (one ds_read_b128, one store)
-                if (ybase + i + VEC <= rowA) {
-                    if (NT_Y && S.y_streaming) __builtin_nontemporal_store(*reinterpret_cast<const v4u_t *>(res + i), reinterpret_cast<v4u_t *>(y + ybase + i));
-                    else *reinterpret_cast<uint4 *>(y + ybase + i) = *reinterpret_cast<const uint4 *>(res + i);
+                if (yi + VEC <= rowA) {
+                    if (NT_Y && S.y_streaming) __builtin_nontemporal_store(*reinterpret_cast<const v4u_t *>(res + i), reinterpret_cast<v4u_t *>(y + yi));
+                    else *reinterpret_cast<uint4 *>(y + yi) = *reinterpret_cast<const uint4 *>(res + i);
                 } else {
 #pragma unroll
-                    for (int q = 0; q < VEC; q++) if (ybase + i + q < rowA) y[ybase + i + q] = (val_t)res[i + q];
+                    for (int q = 0; q < VEC; q++) if (yi + q < rowA) y[yi + q] = (val_t)res[i + q];
                 }
             } else {                                           // fp32: the rows hold 16 floats each at the head of their 128 bytes (retire / flush above)
                 const val_t *rf = reinterpret_cast<const val_t *>(res) + (i >> 4) * 32 + (i & 15);
-                if (ybase + i + VEC <= rowA) {
-                    if (NT_Y && S.y_streaming) __builtin_nontemporal_store(*reinterpret_cast<const v4u_t *>(rf), reinterpret_cast<v4u_t *>(y + ybase + i));
-                    else *reinterpret_cast<uint4 *>(y + ybase + i) = *reinterpret_cast<const uint4 *>(rf);
+                if (yi + VEC <= rowA) {
+                    if (NT_Y && S.y_streaming) __builtin_nontemporal_store(*reinterpret_cast<const v4u_t *>(rf), reinterpret_cast<v4u_t *>(y + yi));
+                    else *reinterpret_cast<uint4 *>(y + yi) = *reinterpret_cast<const uint4 *>(rf);
                 } else {
 #pragma unroll
-                    for (int q = 0; q < VEC; q++) if (ybase + i + q < rowA) y[ybase + i + q] = rf[q];
+                    for (int q = 0; q < VEC; q++) if (yi + q < rowA) y[yi + q] = rf[q];
                 }
             }
         }
