@@ -551,6 +551,13 @@ void tilespmv_plan_info(const tilespmv_plan *plan, long long *out /* [TILESPMV_I
  * tile-rows long get S = one grid line: a strip then sweeps down the grid and reads the windows of x it shares with its previous tile-row while they are still in the caches.  The
  * plan holds the same units, values and task records in another order; y is the unstrided plan's bit for bit. */
 int tilespmv_plan_strip_stride(const tilespmv_plan *plan);
+/* The deep unit kernel (environment knob TILESPMV_UNIT_DEEP: unset = by rule, 0 = never, 1 = wherever the plan allows): 0, or the number of unit batches
+ * whose x gathers a wavefront of the plan's unit launch keeps in flight.  It serves plans that take a lean form (TILESPMV_INFO_UNIT_LEAN > 0) with per-strip entries, 16 strips
+ * per workgroup and nontemporal streams and hold nothing but units: no list entry, no split tile-row, no fallback launch.  The plan is the same plan byte for byte — streams,
+ * facts (tilespmv_plan_info) and y — whatever this returns.  tilespmv_plan_layout_unit_deep answers for the plan a host-only layout build of the matrix would make (no GPU
+ * needed; negative on error), as tilespmv_plan_layout_digest does for the streams. */
+int tilespmv_plan_unit_deep(const tilespmv_plan *plan);
+int tilespmv_plan_layout_unit_deep(const Tile_matrix *matrix, int rowA, int colA, MAT_PTR_TYPE nnzA, const tilespmv_plan_options *opts);
 /* Test / audit aid: one (member offset in the plan object, bytes, FNV-1a-64 of the bytes read back from the device) triple per stream of the plan, at most max_streams of them
  * written; returns the number of streams (or -3 on a HIP error).  Two plans of one matrix and one option set — one built from a host Tile_matrix, one by
  * tilespmv_plan_create_from_csr — must agree triple for triple (tests/test_gpu_device_build.py). */

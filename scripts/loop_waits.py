@@ -1,4 +1,4 @@
-"""The unit loop of every k_units / k_units_mv / k_pool_mv instantiation as the gfx950 compiler scheduled it (device assembly, no GPU):
+"""The unit loop of every k_units / k_units_mv / k_pool_mv / k_units_deep instantiation as the gfx950 compiler scheduled it (device assembly, no GPU):
     python scripts/loop_waits.py [f64|f32] [filter]
 For each kernel: the innermost loop that holds the value-stream load (the last 16-byte global load that sits in a loop: the entry phases come before the unit loop, the
 fix-up and y loops behind it load less; in the kernels of hip_kernels_half.hip, whose values are halves, the last nontemporal 8-byte load — HALF_VALUE_LOAD), its `s_waitcnt vmcnt` values in program order, its instruction count, the waits that follow the first load behind the park inside the
@@ -40,6 +40,8 @@ def _blocks(body):
 
 
 HALF_VALUE_LOAD = r"global_load_dwordx2 .*\bnt\b"   # the value-stream load of k_units_half (the x gathers are 8-byte loads too, but not nontemporal)
+NT_VALUE_LOAD = r"global_load_dwordx[24] .*\bnt\b"   # ... of k_units_deep (hip_kernels_deep.hip), every value form: the only nontemporal loads of that kernel
+DEEP_BATCHES_PER_TRIP = 4                             # its loop is one descriptor chunk per trip: DCHUNK / UNIT_DEEP_UB batches (record: profiles/unit_deep_isa.txt)
 
 
 def unit_loops(asm, kinds=("k_units",), value_load=r"global_load_dwordx4\b"):
@@ -84,8 +86,11 @@ def main():
     recs = list(unit_loops(asm, ("k_units", "k_units_mv", "k_pool_mv")).items())
     if dt == "f64":   # the kernels whose values are halves: a file of their own
         recs += list(unit_loops(device_asm("hip_kernels_half.hip", dt, os.environ.get("LOOP_WAITS_ASM_HALF", "/tmp/loop_waits_half.s")), ("k_units_half",), HALF_VALUE_LOAD).items())
+    recs += list(unit_loops(device_asm("hip_kernels_deep.hip", dt, os.environ.get("LOOP_WAITS_ASM_DEEP", "/tmp/loop_waits_deep_%s.s" % dt)), ("k_units_deep",), NT_VALUE_LOAD).items())
     for d, r in recs:
-        if flt in d:
+        if d.startswith("k_units_deep<") and flt in d:
+            print("%-62s vgpr %3d scratch %3d loop insns %4d = %d x %.1f per batch  vmcnt %s" % (d, r["vgpr"], r["scratch"], r["insns"], DEEP_BATCHES_PER_TRIP, r["insns"] / DEEP_BATCHES_PER_TRIP, ",".join(map(str, r["vmcnt"]))))
+        elif flt in d:
             print("%-62s vgpr %3d scratch %3d loop insns %4d vmcnt %-22s refill waits after the gather: %s" %
                   (d, r["vgpr"], r["scratch"], r["insns"], ",".join(map(str, r["vmcnt"])), "-" if r["refill_waits"] is None else (" | ".join(r["refill_waits"]) or "none")))
 

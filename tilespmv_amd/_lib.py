@@ -151,6 +151,11 @@ def load(dtype=np.float64):
     if hasattr(lib, "tilespmv_plan_strip_stride"):   # (a TILESPMV_LIB_VARIANT library of an earlier commit has no such entry)
         lib.tilespmv_plan_strip_stride.argtypes = [C.c_void_p]
         lib.tilespmv_plan_strip_stride.restype = C.c_int
+    if hasattr(lib, "tilespmv_plan_unit_deep"):   # (likewise)
+        lib.tilespmv_plan_unit_deep.argtypes = [C.c_void_p]
+        lib.tilespmv_plan_unit_deep.restype = C.c_int
+        lib.tilespmv_plan_layout_unit_deep.argtypes = [TP, C.c_int, C.c_int, C.c_int, C.POINTER(PlanOptions)]
+        lib.tilespmv_plan_layout_unit_deep.restype = C.c_int
     lib.tilespmv_plan_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.tilespmv_plan_time.restype = C.c_double
     lib.tilespmv_plan_time_reference_style.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -282,4 +287,4 @@ DECLARED_SYMBOLS = ["Tile_create", "Tile_create_ex", "Tile_destroy", "tilespmv_c
                     "tilespmv_fsai_info", "tilespmv_cg_create_fsai",
                     "tilespmv_gmres_create", "tilespmv_gmres_create_block", "tilespmv_gmres_destroy", "tilespmv_gmres_begin", "tilespmv_gmres_iterate", "tilespmv_gmres_flush",
                     "tilespmv_gmres_state_read", "tilespmv_gmres_solve", "tilespmv_gmres_create_basis", "tilespmv_gmres_basis_bytes", "tilespmv_gmres_workspace_bytes",
-                    "tilespmv_plan_strip_stride"]
+                    "tilespmv_plan_strip_stride", "tilespmv_plan_unit_deep", "tilespmv_plan_layout_unit_deep"]

@@ -273,6 +273,15 @@ def plan_layout_digest(tm, rowA, colA, nnzA, coo_mode=COO_AUTO, dense_mode=DENSE
     return d.value, {k: int(out[i]) for i, k in enumerate(_lib.INFO_NAMES)}
 
 
+def plan_layout_unit_deep(tm, rowA, colA, nnzA, coo_mode=COO_AUTO, dense_mode=DENSE_AUTO, kernel=0, tilerow_begin=0, tilerow_end=0, **knobs):
+    """Host-only: what ``Plan.unit_deep()`` of the plan of this matrix and these options would report (tilespmv_plan_layout_unit_deep)."""
+    opts = _lib.PlanOptions(coo_mode, dense_mode, kernel, tilerow_begin, tilerow_end, False, **knobs)
+    rc = tm._lib.tilespmv_plan_layout_unit_deep(C.byref(tm), rowA, colA, nnzA, C.byref(opts))
+    if rc < 0:
+        raise RuntimeError("tilespmv_plan_layout_unit_deep failed (%d)" % rc)
+    return int(rc)
+
+
 STAGE_NAMES = ["count", "choose", "cut", "emit", "order", "encode", "entries", "finish"]
 
 
@@ -410,6 +419,10 @@ class Plan:
     def strip_stride(self):
         """S: tile-rows between the consecutive tile-rows of one strip of the unit stream, 1 = consecutive (tilespmv_plan_strip_stride; TILESPMV_STRIP_SWEEP)."""
         return int(self.lib.tilespmv_plan_strip_stride(self.h))
+
+    def unit_deep(self):
+        """0, or the batches of x gathers the plan's unit launch keeps in flight per wavefront: the deep unit kernel (tilespmv_plan_unit_deep; TILESPMV_UNIT_DEEP)."""
+        return int(self.lib.tilespmv_plan_unit_deep(self.h))
 
     def stream_digests(self):
         """{member offset: (bytes, FNV-1a-64)} of every stream of the plan, read back from the device (test / audit aid)."""

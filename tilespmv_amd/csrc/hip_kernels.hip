@@ -1318,7 +1318,10 @@ hipError_t launch_tiles_stream(const DevPlan &P, const DevStream &S, const DevDe
         // Grids that would give fewer than half the CUs a 256-thread workgroup run 128-thread workgroups of 8 strips instead: twice the workgroups, the same strips
         // (per-strip and per-wavefront entry modes only: the workgroup mode merges the lists of its 16 strips at plan creation)
         const bool small_grid = entry_mode != 2 && !S.nt_stream && (S.ntasks + 15) / 16 < SMALL_GRID_WORKGROUPS;
-        if (const int lean = unit_lean_form(S, entry_mode, wg_strips)) {   // no row units (and no derived ones): the lean forms of hip_kernels_lean.hip, every value form
+        if (const int deep = unit_deep_form(S, entry_mode, wg_strips)) {   // a lean plan that holds nothing but units: hip_kernels_deep.hip
+            const hipError_t ed = launch_units_deep(P, S, deep, entry_mode, wg_strips, lds_pad_bytes, xc, x, y, st);
+            if (ed != hipSuccess) return ed;
+        } else if (const int lean = unit_lean_form(S, entry_mode, wg_strips)) {   // no row units (and no derived ones): the lean forms of hip_kernels_lean.hip, every value form
             const hipError_t el = launch_units_lean(P, S, lean, entry_mode, wg_strips, lds_pad_bytes, xc, x, y, st);
             if (el != hipSuccess) return el;
         } else

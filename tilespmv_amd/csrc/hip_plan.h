@@ -225,6 +225,10 @@ struct DevStream {
     // stride of one grid line a tile-row's "up" and centre windows of x are the centre and "down" windows of the strip's previous tile-row: the strip reads them again a few
     // batches after it first did, from the vector L1 / its XCD's L2
     int strip_stride = 1;
+    // the deep unit kernel (hip_kernels_deep.hip; environment knob TILESPMV_UNIT_DEEP): 1 = the knob or its rule allow it AND the plan holds nothing but units — no list entry, no
+    // split tile-row, no fallback launch (set once the whole plan is known, hip_plan.hip).  The launch reads it through unit_deep_form below.  (The struct keeps its size: the
+    // field takes what was padding, so every kernel finds its other arguments where they were.)
+    int unit_deep = 0;
 };
 constexpr int UNIT_FACT_NO_ROWUNIT = 1, UNIT_FACT_NO_DERIVED = 2;
 // The form of the unit kernel a launch takes (TILESPMV_INFO_UNIT_LEAN): 0 = the general kernel, 1 = lean (no row units), 2 = lean without derived units.  Lean forms exist for
@@ -234,6 +238,16 @@ inline int unit_lean_form(const DevStream &S, int entry_mode, int wg_strips)
     if (!S.unit_lean || S.ntasks <= 0 || S.pooled || !S.nt_stream || !(entry_mode == 0 || entry_mode == 2) || wg_strips != 16) return 0;
     if (!(S.unit_facts & UNIT_FACT_NO_ROWUNIT)) return 0;
     return (S.unit_facts & UNIT_FACT_NO_DERIVED) ? 2 : 1;
+}
+// The deep unit kernel (hip_kernels_deep.hip k_units_deep<UNIT_DEEP_UB, UNIT_DEEP_DEPTH, ..>): the gathers of UNIT_DEEP_DEPTH batches of UNIT_DEEP_UB units in flight per wavefront.
+// DESIGN.md S8 item 15 has the variants that were measured.
+constexpr int UNIT_DEEP_UB = 4, UNIT_DEEP_DEPTH = 2;
+// Whether a launch takes the deep unit kernel (tilespmv_plan_unit_deep): 0, or its depth.  It serves lean plans (either lean form, every value form, 12-byte and dictionary
+// descriptors) with per-strip entries, 16 strips per workgroup and nontemporal streams that hold nothing but units (DevStream::unit_deep).
+inline int unit_deep_form(const DevStream &S, int entry_mode, int wg_strips)
+{
+    if (!S.unit_deep || entry_mode != 0 || wg_strips != 16 || unit_lean_form(S, entry_mode, wg_strips) <= 0) return 0;
+    return UNIT_DEEP_DEPTH;
 }
 
 // Dense tiles on the matrix cores (generation 2): one wavefront per tile-row that owns dense tiles.
@@ -272,5 +286,7 @@ inline void tile_stream_sizes(int fmt, int p1, int p2, int *nv, int *ni)
 hipError_t launch_units_half(const DevPlan &P, const DevStream &S, int entry_mode, int wg_strips, int lds_pad_bytes, int xcd_chunk, const val_t *x, val_t *y, hipStream_t st);
 // hip_kernels_lean.hip: the k_units launch of a plan whose unit_lean_form is `form` > 0, called by launch_tiles_stream; hipErrorInvalidValue for any other plan
 hipError_t launch_units_lean(const DevPlan &P, const DevStream &S, int form, int entry_mode, int wg_strips, int lds_pad_bytes, int xcd_chunk, const val_t *x, val_t *y, hipStream_t st);
+// hip_kernels_deep.hip: the k_units_deep launch of a plan whose unit_deep_form is `depth` > 0, called by launch_tiles_stream in front of the lean launch; hipErrorInvalidValue for any other plan
+hipError_t launch_units_deep(const DevPlan &P, const DevStream &S, int depth, int entry_mode, int wg_strips, int lds_pad_bytes, int xcd_chunk, const val_t *x, val_t *y, hipStream_t st);
 
 }  // namespace tilespmv

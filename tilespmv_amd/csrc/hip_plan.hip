@@ -70,6 +70,7 @@ static Knobs resolve_knobs(const tilespmv_plan_options *opts)
     static const int unit_lean_env = env_int("TILESPMV_UNIT_LEAN", 1);   // (read once)
     k.unit_lean = (o.unit_lean != TILESPMV_KNOB_DEFAULT ? o.unit_lean : unit_lean_env) != 0 ? 1 : 0;
     k.strip_sweep = std::max(-1, std::min(1, env_int("TILESPMV_STRIP_SWEEP", -1)));   // (no field of tilespmv_plan_options: its layout is pinned)
+    k.unit_deep = std::max(-1, std::min(1, env_int("TILESPMV_UNIT_DEEP", -1)));       // (likewise)
     k.deterministic = pick(o.deterministic, "TILESPMV_DETERMINISTIC", 0) > 0 ? 1 : 0;
     if (k.deterministic) {   // no stopwatch, no unordered sum: whatever the caller left unset among the timed choices is switched off
         if (k.placement_tries < 0) k.placement_tries = 1;
@@ -804,6 +805,12 @@ static int plan_create_one(tilespmv_plan **out, const Tile_matrix *T, int rowA, 
     // bytes one SpMV has to move at least: the three streams + tasks + x once + y once (+ fallback)
     I[TILESPMV_INFO_STREAM_BYTES] = model_bytes + (long long)colA * sv + (long long)rows * sv +
                                     (f_nnz ? (long long)f_rec.size() * (long long)sizeof(ERec) + (long long)f_base.size() * 4 + 2LL * sv * rows + (long long)f_blk.size() * 16 : 0);   // the fallback re-reads and re-writes its rows of y
+    // The deep unit kernel (hip_plan.h unit_deep_form, knob TILESPMV_UNIT_DEEP) needs a plan that holds nothing but units: no list entry, no split tile-row, no fallback launch.
+    // By rule (knob unset) it is taken where the launch is nontemporal by size, so that small plans keep the kernels their tests name.  No structural exclusion: every class
+    // that was timed counts against the parent commit and against knob 0 at both plan positions (profiles/unit_deep_ab.txt) — 5-point 4096^2 as halves -5.1 / -8.3 %, as
+    // floats -5.1 / -4.5 %, with 8-byte values -4.3 / -4.3 %, in the fp32 library -5.4 / -5.4 %; 7-point 256^3 (unstrided) fp64 -7.0 / -0.4 %, fp32 -5.7 / -6.4 %.
+    plan->st.unit_deep = (plan->kernel == TILESPMV_KERNEL_STREAM && K.unit_deep != 0 && I[TILESPMV_INFO_LIST_ENTRIES] == 0 && fix.empty() && f_blk.empty() &&
+                          (K.unit_deep > 0 || I[TILESPMV_INFO_STREAM_BYTES] > NT_STREAM_MIN_BYTES)) ? 1 : 0;
     if (!K.dry) {
         const int tries = K.placement_tries >= 0 ? K.placement_tries : (I[TILESPMV_INFO_DEVICE_BYTES] >= (1ll << 30) ? 8 : 1);
         const double t0p = now_us();
@@ -1062,6 +1069,23 @@ long long tilespmv_plan_stream_digests(const tilespmv_plan *plan, unsigned long 
 int tilespmv_plan_strip_stride(const tilespmv_plan *plan)
 {
     return plan->kernel == TILESPMV_KERNEL_STREAM ? std::max(1, plan->st.strip_stride) : 1;
+}
+
+int tilespmv_plan_unit_deep(const tilespmv_plan *plan)
+{
+    return plan->kernel == TILESPMV_KERNEL_STREAM ? unit_deep_form(plan->st, plan->entry_mode, plan->wg_strips) : 0;
+}
+
+int tilespmv_plan_layout_unit_deep(const Tile_matrix *T, int rowA, int colA, MAT_PTR_TYPE nnzA, const tilespmv_plan_options *opts)
+{
+    Knobs K = resolve_knobs(opts);
+    K.dry = true; K.autotune = 0;
+    tilespmv_plan *p = nullptr;
+    const int rc = plan_create_one(&p, T, rowA, colA, nnzA, K);
+    if (rc != 0 || !p) return rc ? (rc < 0 ? rc : -rc) : -4;
+    const int deep = tilespmv_plan_unit_deep(p);
+    tilespmv_plan_destroy(p);
+    return deep;
 }
 
 void tilespmv_plan_info(const tilespmv_plan *plan, long long *out)

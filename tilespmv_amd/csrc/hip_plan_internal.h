@@ -66,6 +66,7 @@ struct Knobs {
     int absorb;          // 1 (default): list entries next to an ELL tile go into its padding slots (plan_tile_ops.h "absorbed list entries"); 0 = never
     int unit_lean;       // 0: general unit kernels whatever the plan's facts say; 1: the lean forms wherever they allow (hip_plan.h unit_lean_form)
     int strip_sweep;     // strided strips (hip_plan_stream.hip strip_sweep_stride; environment only: TILESPMV_STRIP_SWEEP): -1 by rule, 0 never, 1 wherever the shard's structure allows
+    int unit_deep;       // the deep unit kernel (hip_plan.h unit_deep_form; environment only: TILESPMV_UNIT_DEEP): -1 by rule, 0 never (the launch is the lean one, kernel for kernel), 1 wherever the predicate holds
     int value_narrow;    // fp64: unit values stored as floats / halves where every one survives the round trip: 0 never, 1 floats wherever eligible, 2 the narrowest form the values allow wherever eligible, -1 the narrowest form whose launch stays above NT_STREAM_MIN_BYTES
     bool value_map;      // the plan is built from stand-in values (TILESPMV_CREATE_VALUE_MAP): its layout follows the pattern alone
     int desc_dict;       // 0 = always 12-B unit descriptors; -1 = 4-B descriptors + pattern dictionary where the shard allows and it pays; 1 = wherever it allows; 2 = like 1 (pooled plans: 8-byte pairs instead of 4-byte words)

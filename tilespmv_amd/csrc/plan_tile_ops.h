@@ -382,6 +382,7 @@ TILESPMV_HD inline void put_unit(const EmitOut &O, EmitPos &p, int csr_form, uns
 TILESPMV_HD inline void emit_touched_unit(const Tile_matrix *T, int t, int rowlen, const AbsorbPlan &A, int s, int cb, unsigned kr, int csr_form, const EmitOut &O, long long u)
 {
     // its window starts `shift` columns beside the block; padding slots point at the window's lowest used column (derived units: every lane holds lane 15's column)
+    // (k_units_deep, hip_kernels_deep.hip, relies on that: there ALL 16 lanes of a derived unit gather, and 16 equal nibbles make them read lane 15's word, which is in range)
     const bool der = (A.derived >> s) & 1u;
     const int sh = der ? 0 : A.shift[s], pad = der ? (int)A.dnib[s] : A.lo[s] - sh;
     unsigned long long nibs = 0;
